@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """bench.py — denoise-loop throughput of the MI355X engine on BASELINE.json's metric.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, runs W warm-up steps, times K steps and prints the JSON line (headline fields only).  --full adds everything else the line
+  can carry (the roofline / per-kernel passes, the measured peaks and clock, e2e, host_loop, the other workloads, the multi-GPU legs, cpu_baseline),
+  each after the timed region.  --dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32; see dump_outputs).
   N > 1 without a launcher around it: the script re-executes itself as N ranks under torch.distributed.run (one process per GPU, RCCL); launched by
   `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` it is one of those ranks.  WORLD_SIZE != N is an error, and `n_gpus` in
   the line is the number of ranks that took part in the closing all-reduce, not the number asked for.
@@ -16,7 +19,7 @@ Workload at N = 1: BASELINE.json configs[1] (SD1.5 UNet, 512x512, f16, batch 8 o
 over the whole job (batch * steps / time, summed over ranks; max time over ranks).  Images shard across ranks with no data-path
 collective => weak scaling: per-GPU batch fixed.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline:     headline = the dominant kernel family (implicit-GEMM conv, 256-row tiles): achieved = sum of the launches' algorithmic
                 FLOPs (2 * output positions * IC*KH*KW * OC) / sum of their durations, measured live with HIP events recorded on the
                 backend's launch stream around every dispatch, vs the dense f16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md).  The timed
@@ -40,6 +43,7 @@ The JSON line also carries
 from __future__ import annotations
 
 import argparse
+import contextlib
 import ctypes as C
 import json
 import os
@@ -141,7 +145,15 @@ def parse():
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="HARNESS SELF-CHECK, not a measurement: run the launch / sharding / reduction logic of this script on the CPU oracle backend "
                          "with gloo and the tiny UNet (tests/test_dist_shard.py::test_bench_gpus_2_launches_two_ranks)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and per-kernel passes, measured peaks, e2e, host_loop, the other workloads, the "
+                         "multi-GPU legs, cpu_baseline (the options above choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, <= 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _file_version(path: Path) -> str:
@@ -246,12 +258,10 @@ def main():
         # one sampler iteration's model work: cond + uncond forward over the device batch (host CFG/Euler math is included
         # in the e2e number; here the H2D/D2H crossings of the reference boundary are part of the step, as in the reference)
         if flux:
-            eng.unet_forward(x, t * 0.0 + 0.5, cond, y)
-        elif fuse:
-            eng.unet_forward(x2, t2, c2, y2)
-        else:
-            eng.unet_forward(x, t, cond, y)
-            eng.unet_forward(x, t, uncond, y)
+            return {"eps": eng.unet_forward(x, t * 0.0 + 0.5, cond, y)}
+        if fuse:
+            return {"eps": eng.unet_forward(x2, t2, c2, y2)}   # (cond, uncond) interleaved per image
+        return {"eps_cond": eng.unet_forward(x, t, cond, y), "eps_uncond": eng.unet_forward(x, t, uncond, y)}
 
     def dev_sync():
         if not selftest:
@@ -278,22 +288,25 @@ def main():
     # Eager launches (hip_graph 0): the dominant family's HIP events are recorded INSIDE the timed region.  hipGraph replay (the product default): events
     # recorded inside a captured graph cannot be read back on this runtime (scripts/graph_event_probe.hip), so the timed region runs untouched and the
     # same K steps are repeated eagerly right after it with the events on (roofline.timing says which; eager_ms_per_step is that pass's wall time).
-    timing = not selftest
+    timing = args.full and not selftest
     timing_live = timing and args.hip_graph == 0
     if timing_live:
         sd.kernel_timing_enable(True)
-    sclk = SclkSampler()
+    sclk = SclkSampler() if args.full else None
     t0 = time.perf_counter()
-    with sclk:
+    with sclk or contextlib.nullcontext():
         if args.device_sampler:
-            timed_latents = trajectory(args.steps)
+            outputs = {"latents": trajectory(args.steps)}
         else:
             for _ in range(args.steps):
-                step()
+                outputs = step()
         barrier()
     dt = time.perf_counter() - t0
-    if args.device_sampler and not np.isfinite(timed_latents).all():   # a timing on NaN data is not a measurement
+    timed_latents = outputs.get("latents")
+    if timed_latents is not None and not np.isfinite(timed_latents).all():   # a timing on NaN data is not a measurement
         raise RuntimeError(f"bench: the latents sampled in the timed region are not finite ({int((~np.isfinite(timed_latents)).sum())} of {timed_latents.size} values)")
+    if args.dump_outputs:
+        dump_outputs(outputs, Path(args.dump_outputs), rank, world)
     kt = sd.kernel_timing() if timing_live else None
     if timing_live:
         sd.kernel_timing_enable(False)
@@ -355,7 +368,7 @@ def main():
                     roofline["traffic_note"] = pm["note"]
             except (ValueError, KeyError):
                 pass
-    if not selftest and rank == 0:
+    if timing and rank == 0:
         # what THIS box delivers (csrc/kernels/calib.hip, ~1 s, after the timed region): the pool's boxes differ by +-7 % with one binary, so a line is only
         # comparable with another line through these
         cal = sd.calibrate()
@@ -398,8 +411,8 @@ def main():
         "roofline": roofline,
     }
     # BASELINE.json's metric is "denoise it/s + sec/image": the second half is one whole sdm_generate_image call (noise -> 20 sampler steps ->
-    # VAE decode -> uint8 pixels) on the same device batch, run AFTER the timed region.  Default on one GPU; --e2e forces it on rank 0.
-    if rank == 0 and not args.no_e2e and (args.e2e or world == 1):
+    # VAE decode -> uint8 pixels) on the same device batch, run AFTER the timed region.  --full on one GPU; --e2e forces it on rank 0.
+    if rank == 0 and not args.no_e2e and (args.e2e or (args.full and world == 1)):
         try:
             eng.vae_decode(np.zeros((B, 16 if dit else 4, lat, lat), dtype=np.float32))  # untimed: builds the VAE weight images and plan
             t0 = time.perf_counter()
@@ -412,7 +425,7 @@ def main():
                           "vae_decode_ms": round(st["last_decode_ms"], 1)}
         except Exception as exc:  # the headline line must survive a failure of the extra leg
             out["e2e"] = {"error": str(exc)[:200]}
-    if rank == 0 and world == 1 and args.device_sampler and not selftest:
+    if timing and rank == 0 and world == 1 and args.device_sampler:
         # the PCIe-inclusive rate of the reference's boundary (host buffers in and out every step), for DESIGN.md — never the headline
         step()
         torch.cuda.synchronize()
@@ -423,7 +436,7 @@ def main():
         hl = (time.perf_counter() - t0) / 5
         out["host_loop"] = {"ms_per_step": round(hl * 1e3, 3), "it_per_s": round(B / hl, 2),
                             "note": "cond+uncond forward pair per step from host buffers (x H2D, eps D2H each step); CFG / Euler math on the host is outside this step"}
-    if rank == 0 and world == 1 and args.model == "sd15":
+    if args.full and rank == 0 and world == 1 and args.model == "sd15":
         for leg in ("sdxl", "flux", "sd35", "sdxl_b8"):
             if leg in args.skip_legs or (leg == "sdxl" and args.no_sdxl):
                 continue
@@ -431,12 +444,12 @@ def main():
                 out[leg] = model_leg(sd, backend_name, args, leg)
             except Exception as exc:
                 out[leg] = {"error": str(exc)[:200]}
-    if world > 1 and args.model in ("sd15", "sd15_tiny") and "multi" not in args.skip_legs:
+    if args.full and world > 1 and args.model in ("sd15", "sd15_tiny") and "multi" not in args.skip_legs:
         # the metric names SDXL 1024x1024 at 2 / 4 / 8 GPUs too, and the one real exchange step of the path: every rank takes part (collectives inside)
         multi = multi_gpu_legs(sd, backend_name, args, dist, rank, world, selftest)
         if rank == 0:
             out.update(multi)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not dit:  # the CPU leg is defined for the headline UNet workloads
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not dit:  # the CPU leg is defined for the headline UNet workloads
         out["cpu_baseline"] = cpu_baseline(sd, args, lat, ctx_dim)
     if rank == 0 and selftest:
         print(json.dumps(out), flush=True)
@@ -447,6 +460,22 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, d: Path, rank: int, world: int) -> None:
+    """--dump-outputs: every array the timed path returned in its last step (`latents` of the device-resident trajectory; `eps` or `eps_cond` /
+    `eps_uncond` of a --host-loop step) as float32 d/<name>.npy, `_rank<r>` appended on rank r > 0.  An array larger than its share of 64 MB is
+    written as a fixed sample instead: the flat elements at the sorted indices np.random.default_rng(0).choice(size, n, replace=False)."""
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (len(outputs) * world)
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(d / f"{name}{f'_rank{rank}' if rank else ''}.npy", a)
 
 
 def kernel_families(sd, trajectory, step):

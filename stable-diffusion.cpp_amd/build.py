@@ -134,7 +134,10 @@ def build_oracle_ref(pool):
     """oracle/_ref: the parts of the REFERENCE that compile from their own few sources where they lie (oracle/Makefile: PhiloxRNG, the CFG combine of
     src/runtime/guidance.cpp) — only where /root/reference exists (this container); the GPU box uses the prebuilt files that travel with the snapshot."""
     ref = Path(os.environ.get("SD_REFERENCE", "/root/reference"))
-    if not (ref / "src" / "runtime" / "guidance.cpp").exists():
+    try:
+        if not (ref / "src" / "runtime" / "guidance.cpp").exists():
+            return None
+    except OSError:   # a directory on the way that this user may not enter: the same as absent
         return None
     _run(["make", "-C", str(ORACLE), "ref", f"REF={ref}"])
     return ORACLE / "_ref"
