@@ -96,7 +96,6 @@ struct ggml_backend_mi355x_stats {
     int64_t view_graphs;         /* plans built for SUB-GRAPH VIEWS (sd_ggml_graph_view, src/core/ggml_extend_backend.cpp:449-463: leafs NULL / size 0) */
     int64_t plans_evicted;       /* cached plans (with their captured hipGraph) dropped by the LRU bound of the plan cache (option plan_cache_cap, default 512) */
     int64_t hoisted_mod_linears; /* DiT modulation Linears (FLUX Modulation / SD3 adaLN: one or two rows, raw q8_0 / q4_0 weights, same input vector) computed by ONE grouped weight-streaming launch ahead of their graph position */
-    int64_t jit_overlapped;      /* just-in-time weight-image rebuilds issued one Linear ahead on the side stream, overlapping the previous GEMM (option jit_overlap) */
     int64_t view_external_nodes; /* nodes of those slices treated as read outside the slice (parent use_counts > readers inside, the slice's last node and its sources) */
     int64_t qinloop_linears;     /* q8_0 / q4_0 Linears above k_qgemm16's row range planned on the pipelined 256 x 256 tile with the raw GGUF blocks dequantised INSIDE the main loop (k_gemm16<..., QT>): no f16 weight image, resident or rebuilt */
     int64_t flash_out_alias;     /* FLASH_ATTN_EXT -> VIEW -> CONT chains NOT written by the flash kernel itself because the graph allocator gave the CONT the block of a Q / K / V operand (the node runs plain, the CONT as a copy) */
@@ -131,7 +130,7 @@ GGML_MI355X_API void ggml_backend_mi355x_kernel_timing_enable(int enable);      
 GGML_MI355X_API void ggml_backend_mi355x_kernel_timing_enable_mask(uint32_t family_mask);
 GGML_MI355X_API void ggml_backend_mi355x_get_kernel_timing(struct ggml_backend_mi355x_kernel_timing* out);  /* the first timed family */
 GGML_MI355X_API int ggml_backend_mi355x_get_kernel_timings(struct ggml_backend_mi355x_kernel_timing* out, int capacity);  /* every family with launches; returns the count */
-/* options (default): "fusion" (1), "mfma_gemm" (1), "hip_graph" (1: a plan is captured into a hipGraph the second time it runs and replayed from then on; 2 = capture at the first run; eager while kernel timing is on), "flash_pattern" (1), "gemm16" (1), "gemm16_variant" (3), "gemm16_tile" (-1),
+/* options (default): "fusion" (1), "mfma_gemm" (1), "hip_graph" (1: a plan is captured into a hipGraph the second time it runs and replayed from then on; 2 = capture at the first run; eager while kernel timing is on), "flash_pattern" (1), "gemm16_variant" (3), "gemm16_tile" (-1),
  * "splitk_target" (384), "conv_tap_major" (0), "fuse_modulate" / "fuse_gate" / "fuse_gelu" / "fuse_rope" / "fuse_concat_heads" (1);
  * "splitk_mid" (0: two K slices for launches of 193..384 workgroups), "pinned_uploads" (0: set_tensor_async stages through pinned host memory so the call does
  * not wait for the stream);
@@ -159,18 +158,11 @@ GGML_MI355X_API int ggml_backend_mi355x_get_kernel_timings(struct ggml_backend_m
  * "conv_wmajor" (1: weight-major workgroup order for convs whose weight image is >= 2x their input image: every (column tile, K slice) weight chunk on one XCD),
  * "t256p_pad" (1: the pipelined 256 x 256 Linear tile also for widths that are multiples of 128 only), "tail_split" (0: row-split launches — whole rounds of 256 x 256
  * tiles + the remaining rows on small tiles; measured neutral), "ln16_rows" (1; 4 = four rows per wave in the LayerNorm -> f16 image kernel: measured slower);
- * "gemm16_swp" (0; 1 = the 256-row Linear tiles with the accumulator transposed, 16-byte epilogue accesses: correct, measured 1 % slower per SD1.5 step);
  * round 6: "qinloop_min_rows" (513: q8_0 / q4_0 Linears with at least that many activation rows whose launch takes the pipelined 256 x 256 tile read the RAW GGUF blocks and
- * dequantise them inside the GEMM's main loop — no f16 weight image, cached or rebuilt; 0 = off: cached image, or "jit_qimages" rebuild), "qgemm16_pf" (1; 2 = two
- * segments of loads in flight in k_qgemm16: measured slower), "fuse_flash_slices" (1: the proj Linears of an MMDiT / FLUX double block read their token slices out of the flash kernel's f16 image), "gemm16_t192p" (1: the pipelined 256 x 192 Linear tile where it quantises better on 256 CUs), "hoist_mod" (1), "jit_overlap" (0), "plan_cache_cap" (512), "gn_split_min" (65536);
- * "fuse_ln_reduce" (1: the slab reduce of a split-K Linear also writes the f16 operand image of the LayerNorm that reads its result);
- * flash attention: "flash_vtr" (31: bit per head-dim class — V tiles row-major in LDS, fragments by ds_read_b64_tr_b16; 0 = transposing staging pass),
- * "flash_ovl" (1: the two-block d = 40 kernel issues one block's softmax inside the other block's MFMAs; 2: also the other d <= 48 launches; 0: off),
- * "flash_nsel" (1: select-free K / V staging, bit-identical; 0 = per-chunk selects), "flash_short" (2: register-resident K / V kernel for the
- * 77-token cross-attentions, 64 < Lk <= 96 and d <= 64, with the next block's Q rows prefetched; 1 = without the prefetch; 0 = the tile kernel),
- * "flash_qb2" (1: two query blocks per wave for d <= 48), "flash_pp" (0; 1 = the 8-wave ping-pong kernel for 64 < d <= 96,
- * 2 = wherever it is legal: measured slower or equal, kept for A/B runs), "flash_pp_min_tiles" (4).
- * Wrong-result timing ablations exist only in builds with -DMI355X_EXPERIMENTS ("flash_ablate"). */
+ * dequantise them inside the GEMM's main loop — no f16 weight image, cached or rebuilt; 0 = off: cached image, or "jit_qimages" rebuild),
+ * "fuse_flash_slices" (1: the proj Linears of an MMDiT / FLUX double block read their token slices out of the flash kernel's f16 image), "gemm16_t192p" (1: the pipelined 256 x 192 Linear tile where it quantises better on 256 CUs), "hoist_mod" (1), "plan_cache_cap" (512), "gn_split_min" (65536);
+ * "fuse_ln_reduce" (1: the slab reduce of a split-K Linear also writes the f16 operand image of the LayerNorm that reads its result).
+ * An unknown key changes nothing and is named on stderr.  Wrong-result timing ablations exist only in builds with -DMI355X_EXPERIMENTS ("gemm16_abl"). */
 GGML_MI355X_API void ggml_backend_mi355x_set_option(const char* key, int value);
 /* What the calling thread's current device delivers, measured in about a second (csrc/kernels/calib.hip): an MFMA loop from registers (f16, 32x32x16: the
  * matrix pipe's ceiling at the clock the chip sustains under it, and that clock), a float4 copy and a read-only pass over 1 GiB.  bench.py reports them as

@@ -35,13 +35,12 @@ def run(lat, n, opts):
     print(f"{leg} latent {lat} batch {n} {opts}: finite per image {per}", flush=True)
     del eng
     for kk, v in opts:
-        sd.backend_set_option(kk, {"qinloop_min_rows": 513, "jit_qimages": 4096, "flash_vtr": 255, "flash_vpf": 255}.get(kk, 1))
+        sd.backend_set_option(kk, {"qinloop_min_rows": 513, "jit_qimages": 4096}.get(kk, 1))
     return fin.all()
 
 
 lat = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 run(lat, 2, [])
 for combo in ([("fuse_joint_qkv", 0), ("fuse_concat_heads", 0)], [("fuse_joint_qkv", 0), ("fuse_concat_heads", 0), ("fuse_q16", 0)], [("fuse_joint_qkv", 0), ("fuse_q16", 0)],
-              [("fuse_concat_heads", 0), ("fuse_q16", 0)], [("fuse_joint_qkv", 0), ("fuse_concat_heads", 0), ("fuse_q16", 0), ("fuse_rope", 0)], [("flash_grid", 0)],
-              [("flash_nsel", 0)], [("flash_vtr", 0)], [("flash_vpf", 0)]):
+              [("fuse_concat_heads", 0), ("fuse_q16", 0)], [("fuse_joint_qkv", 0), ("fuse_concat_heads", 0), ("fuse_q16", 0), ("fuse_rope", 0)]):
     run(lat, 2, combo)

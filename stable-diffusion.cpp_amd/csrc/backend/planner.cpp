@@ -21,6 +21,7 @@
 #include "planner.h"
 
 #include <atomic>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -160,27 +161,17 @@ void planner_get_op_maps(uint8_t* ops256, uint8_t* unary256) {
 
 namespace {
 
-struct Stats {
-    std::atomic<int64_t> graphs_computed{0}, plans_built{0}, nodes_seen{0}, kernels_planned{0}, kernels_launched{0}, fused_conv{0},
-        fused_conv_bounced{0}, fused_linear{0}, fused_norm{0}, fused_geglu{0}, fused_attention{0}, generic_matmul{0}, swizzled_weight_bytes{0}, fused_linear_geglu{0}, split_k_gemms{0}, head_major_gemms{0}, fused_modulate{0}, fused_gate{0}, fused_gelu{0}, fused_rope{0}, fused_concat_heads{0},
-        graph_replays{0}, qgemv_linears{0}, fused_chan_add{0}, fused_proj_tokens{0}, gemm_attention{0}, fused_q16{0}, split_k_inlaunch{0}, qgemm16_linears{0}, fgemv_linears{0}, fused_presilu{0}, fused_sibling_linears{0}, hoisted_kv_linears{0}, window_convs{0}, hoisted_emb_linears{0}, fused_rows16{0}, fused_cat_rows16{0}, fused_joint_qkv{0}, jit_images{0}, fused_gn_stats{0}, redirect_fallbacks{0}, fused_ln_reduce{0}, fused_concat_gn{0}, fused_conv_scale{0}, view_graphs{0}, view_external_nodes{0}, plans_evicted{0}, hoisted_mod_linears{0}, jit_overlapped{0}, qinloop_linears{0}, flash_out_alias{0}, flash_slice_images{0};
-} g_stats;
+// Counters: one atomic per int64_t field of the public ggml_backend_mi355x_stats (include/ggml-mi355x.h is the single list), addressed by field name
+constexpr size_t N_STATS = sizeof(ggml_backend_mi355x_stats) / sizeof(int64_t);
+static_assert(N_STATS * sizeof(int64_t) == sizeof(ggml_backend_mi355x_stats), "ggml_backend_mi355x_stats: int64_t fields only");
+std::atomic<int64_t> g_stat_counters[N_STATS];
+#define STAT(field) g_stat_counters[offsetof(ggml_backend_mi355x_stats, field) / sizeof(int64_t)]
 
 struct Options {
-    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, gemm16{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, jit_overlap{0}, fuse_flash_slices{1}, fuse_act_pack{1};
+    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1};
 } g_opt;
 
-// One launch (or a few) of a plan.  tag 2 marks the just-in-time weight-image rebuild of a quantised Linear (k_wswz_q, option jit_qimages): build_plan's
-// last pass issues those one Linear AHEAD on the planner's side stream (overlap_jit_steps), which needs to know where they are and what they do.
-struct Step {
-    std::function<void(hipStream_t)> fn;
-    uint8_t tag = 0;
-    std::function<void(hipStream_t)> side_fn;  // tag 2: the same launch, for the side stream (identical to fn here; kept separate so fn can be dropped)
-    Step() = default;
-    template <class F, class = typename std::enable_if<!std::is_same<typename std::decay<F>::type, Step>::value>::type>
-    Step(F&& f) : fn(std::forward<F>(f)) {}
-    void operator()(hipStream_t st) const { fn(st); }
-};
+using Step = std::function<void(hipStream_t)>;  // one launch (or a few) of a plan
 
 struct Plan {
     int n_nodes = 0;
@@ -189,10 +180,6 @@ struct Plan {
     std::vector<Step> steps;
     hipGraphExec_t graph_exec = nullptr;
     bool graph_failed         = false;
-    std::vector<hipEvent_t> events;  // fork / join events of the side-stream weight-image rebuilds (overlap_jit_steps); destroyed with the plan
-    ~Plan() {
-        for (hipEvent_t e : events) (void)hipEventDestroy(e);
-    }
     int64_t runs              = 0;  // executions so far: the hipGraph is captured when a plan comes back (one-shot graphs never pay for a capture)
     uint64_t last_use         = 0;  // Planner::tick at the last execution: the plan cache evicts the least recently used entry beyond plan_cache_cap
 };
@@ -224,7 +211,7 @@ struct Planner {
     size_t arena_cap  = 0;
     // just-in-time weight images (option jit_qimages): one device buffer per image size, shared by every quantised Linear of that size and kept
     // for the planner's lifetime (stable addresses: plans capture them)
-    std::map<size_t, void*> jit_buf;  // key: image bytes * 2 + parity (two buffers per size: the rebuild of the NEXT Linear of a size runs while the GEMM of the previous one still reads its image)
+    std::map<size_t, void*> jit_buf;  // key: image bytes * 2 + parity (two buffers per size, taken alternately: a rebuild is placed with emit_at, so the rebuild of the next Linear of a size may be enqueued in front of the GEMM that still reads the previous image)
     void* jit_buffer(size_t bytes, int parity = 0) {
         const size_t key = bytes * 2 + (size_t)(parity & 1);
         auto it = jit_buf.find(key);
@@ -234,7 +221,6 @@ struct Planner {
         jit_buf[key] = d;
         return d;
     }
-    hipStream_t side = nullptr;  // non-blocking side stream for work that may overlap the main launch stream (weight-image rebuilds)
 };
 
 namespace {
@@ -679,12 +665,12 @@ struct Builder {
             r.cnt_base = cnt_off;
             r.cnt_rel  = cnt_used;
             cnt_used += (size_t)sp.tiles;
-            g_stats.split_k_inlaunch++;
+            STAT(split_k_inlaunch)++;
         }
         r.S        = sp.S;
         r.inkernel = sp.inkernel;
         r.wsoff    = alloc(sp.ws_bytes);
-        g_stats.split_k_gemms++;
+        STAT(split_k_gemms)++;
         return r;
     }
 };
@@ -710,12 +696,12 @@ const void* get_swz_linear(Planner* P, const ggml_tensor* w, hipStream_t s, int 
     if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
     launch_wswz_linear(s, d, w->data, (int)w->type, K, R, (int64_t)w->nb[1], geglu == 2 ? -(R / 2) : geglu_pairs ? R / 2 : 0);
     P->swz[key] = {d, bytes, w->data, ggml_abi_nbytes(w)};
-    g_stats.swizzled_weight_bytes += (int64_t)bytes;
+    STAT(swizzled_weight_bytes) += (int64_t)bytes;
     return d;
 }
 // kblk32: the (32-channel block, tap, channel) image of the LDS-window kernel (conv3w.hip)
 const void* get_swz_conv(Planner* P, const ggml_tensor* w, hipStream_t s, bool kblk32 = false) {
-    const bool icb_major = g_opt.gemm16 != 0 && !gemm16_tap_major();
+    const bool icb_major = !gemm16_tap_major();
     uint64_t key = fnv(fnv(1469598103934665603ull, &w->data, sizeof(w->data)), kblk32 ? "W" : (icb_major ? "D" : "C"), 1);
     auto it      = P->swz.find(key);
     if (it != P->swz.end()) return it->second.swz;
@@ -726,7 +712,7 @@ const void* get_swz_conv(Planner* P, const ggml_tensor* w, hipStream_t s, bool k
     if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
     launch_wswz_conv(s, d, w->data, KW, KH, IC, OC, kblk32 ? 32 : (icb_major ? 64 : 0));
     P->swz[key] = {d, bytes, w->data, ggml_abi_nbytes(w)};
-    g_stats.swizzled_weight_bytes += (int64_t)bytes;
+    STAT(swizzled_weight_bytes) += (int64_t)bytes;
     return d;
 }
 
@@ -773,7 +759,7 @@ bool linear_fast_ok(const ggml_tensor* n);
 // node k = SCALE(x, s) (no bias) read only by the IM2COL of an implicit-GEMM conv: the Conv2d scale of ggml_ext_conv_2d (ggml_extend.hpp:1131-1171)
 bool scale_into_conv(const GInfo& gi, int k, float* s_out) {
     const ggml_tensor* n = gi.node(k);
-    if (xop(n) != GGML_OP_SCALE || !g_opt.gemm16 || !g_opt.fusion || !g_opt.fuse_conv_scale || (n->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
+    if (xop(n) != GGML_OP_SCALE || !g_opt.fusion || !g_opt.fuse_conv_scale || (n->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
     if (ggml_abi_op_param_f32(n, 1) != 0.f || !is_f32(n) || !contig(n) || !n->src[0] || !is_f32(n->src[0]) || !contig(n->src[0])) return false;
     const int c = gi.sole(k);
     if (c < 0 || xop(gi.node(c)) != GGML_OP_IM2COL || gi.node(c)->src[1] != n || !conv_im2col_fast_ok(gi, c)) return false;
@@ -783,7 +769,7 @@ bool scale_into_conv(const GInfo& gi, int k, float* s_out) {
 // every consumer of node i (looking through RESHAPE views) is a gen-2 GEMM that reads the f16 image.  want_conv with mul_out: a consumer may reach its
 // conv through a Conv2d-scale node (scale_into_conv) when ALL of them do, with one factor: *mul_out = that factor (1 = none)
 bool all_consumers_gemm16(const GInfo& gi, int i, bool want_conv, float* mul_out = nullptr) {
-    if (!g_opt.gemm16 || !g_opt.mfma_gemm || !g_opt.fusion) return false;
+    if (!g_opt.mfma_gemm || !g_opt.fusion) return false;
     const ggml_tensor* t = gi.node(i);
     if ((t->flags & GGML_TENSOR_FLAG_OUTPUT) || i == gi.g->n_nodes - 1) return false;
     std::vector<int> work{i};
@@ -830,7 +816,7 @@ bool linear_fast_ok(const ggml_tensor* n) {
     if (x->ne[2] > 1 && x->nb[2] != x->nb[1] * (size_t)x->ne[1]) {
         // a token slice of a [C, L, N] tensor (MMDiT block_mixing, mmdit.hpp:651-667): rows are N runs with the parent's batch stride — the
         // gemm16 pack kernel takes that stride; the first-generation path does not
-        if (!g_opt.gemm16 || x->ne[3] != 1 || x->nb[2] % 16 != 0) return false;
+        if (x->ne[3] != 1 || x->nb[2] % 16 != 0) return false;
     }
     if (x->ne[3] > 1 && x->nb[3] != x->nb[2] * (size_t)x->ne[2]) return false;
     if (!contig(n)) return false;
@@ -846,7 +832,7 @@ struct FlashSlice {
 };
 bool flash_out_token_slices(const GInfo& gi, int j2, int64_t C, int64_t Lq, int64_t N, std::vector<FlashSlice>& out) {
     out.clear();
-    if (!g_opt.gemm16 || !g_opt.mfma_gemm || !g_opt.fusion || !g_opt.fuse_flash_slices || C % 8 != 0) return false;
+    if (!g_opt.mfma_gemm || !g_opt.fusion || !g_opt.fuse_flash_slices || C % 8 != 0) return false;
     const ggml_tensor* ct = gi.node(j2);
     if ((ct->flags & GGML_TENSOR_FLAG_OUTPUT) || j2 == gi.g->n_nodes - 1) return false;
     std::vector<int> work{j2};
@@ -890,7 +876,7 @@ bool flash_out_token_slices(const GInfo& gi, int j2, int64_t C, int64_t Lq, int6
 // (SpatialTransformer proj_out, block.hpp:566-572) and nothing else.  On success *rs_out = the last RESHAPE (the conv's input tensor).
 static bool tokens_to_conv_match(const GInfo& gi, int i, int* rs_out) {
     const ggml_tensor* n = gi.node(i);
-    if (!g_opt.fuse_proj_tokens || !g_opt.gemm16 || !g_opt.fusion || xop(n) != GGML_OP_CONT || !is_f32(n) || !contig(n) || (n->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
+    if (!g_opt.fuse_proj_tokens || !g_opt.fusion || xop(n) != GGML_OP_CONT || !is_f32(n) || !contig(n) || (n->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
     const ggml_tensor* pm = n->src[0];
     if (!pm || xop(pm) != GGML_OP_PERMUTE) return false;
     const int32_t* pa = pm->op_params;
@@ -936,7 +922,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     // the projection GEMM stores straight into the CONT (f32) or CPY (f16) buffer in head-major order
     int hm_d = 0, hm_H = 0, hm_L = 0;
     bool hm_f16 = false;
-    if (g_opt.fusion && g_opt.gemm16) {
+    if (g_opt.fusion) {
         const int j1 = gi.sole(i);
         const int j2 = (j1 >= 0 && xop(gi.node(j1)) == GGML_OP_RESHAPE) ? gi.sole(j1) : -1;
         const int j3 = (j2 >= 0 && xop(gi.node(j2)) == GGML_OP_PERMUTE) ? gi.sole(j2) : -1;
@@ -991,7 +977,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
                     // f32 graph buffer; a GEMM launch reads the f16 operand image in the arena (written by x's producer or by the pack pass that runs
                     // in front of it), so the allocator handing x's released buffer to the ADD is no hazard there (it did for the to_out + x of every
                     // first attention: 16 unfused 84 .. 21 MB adds per SD1.5 forward, GGML_MI355X_PLAN_TRACE)
-                    const bool reads_x_f32 = !g_opt.gemm16 || !g_opt.relax_res_overlap || tokens <= 16;
+                    const bool reads_x_f32 = !g_opt.relax_res_overlap || tokens <= 16;
                     if ((!reads_x_f32 || !overlaps(a->data, ob, x->data, ggml_abi_nbytes(x))) && (other->data == a->data || !overlaps(a->data, ob, other->data, ob))) {
                         ep.residual = (const float*)other->data;
                         chain.push_back(r);
@@ -1007,7 +993,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     int nchw_add = -1;
     const float* nchw_res = nullptr;
     int64_t nchw_HW = 0, nchw_N = 0;
-    if (g_opt.fusion && g_opt.gemm16 && g_opt.fuse_proj_tokens && g_opt.fuse_linear_nchw && hm_d == 0 && !ep.residual && last != i && tokens > 16 && n->ne[3] == 1 && x->ne[3] == 1) {
+    if (g_opt.fusion && g_opt.fuse_proj_tokens && g_opt.fuse_linear_nchw && hm_d == 0 && !ep.residual && last != i && tokens > 16 && n->ne[3] == 1 && x->ne[3] == 1) {
         const int jp = gi.sole(last);
         const ggml_tensor* pt = jp >= 0 ? gi.node(jp) : nullptr;
         if (pt && xop(pt) == GGML_OP_PERMUTE && pt->src[0] == gi.node(last) && pt->op_params[0] == 1 && pt->op_params[1] == 0 && pt->op_params[2] == 2 && pt->op_params[3] == 3) {
@@ -1042,7 +1028,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     }
     int emit_node = i;  // graph position at which the GEMM itself is launched (operand packing always happens at i)
     // DiT gate (mmdit.hpp:540-551): Linear -> MUL(., gate[M,1,N]) -> ADD(x, .): dst = x + (acc + bias) * gate
-    if (g_opt.fusion && g_opt.gemm16 && g_opt.fuse_gate && hm_d == 0 && !ep.residual && x->ne[3] == 1 && x->ne[1] >= 32 && tokens < (1ll << 31) &&
+    if (g_opt.fusion && g_opt.fuse_gate && hm_d == 0 && !ep.residual && x->ne[3] == 1 && x->ne[1] >= 32 && tokens < (1ll << 31) &&
         gemm16_split_k(tokens, M, K, false) == 1) {  // split-K launches keep the plain epilogue (the slab reduce applies bias only)
         const int jm = gi.sole(last);
         const ggml_tensor* mt = jm >= 0 ? gi.node(jm) : nullptr;
@@ -1067,14 +1053,14 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
                     chain       = c2;
                     last        = jr;
                     emit_node   = jr;
-                    g_stats.fused_gate++;
+                    STAT(fused_gate)++;
                 }
             }
         }
     }
     // Mlp (block.hpp:249-258): fc1 -> GELU feeding only fc2: the GEMM writes gelu(acc + bias) as fc2's f16 operand image
     int gelu_out = -1;
-    if (g_opt.fusion && g_opt.gemm16 && g_opt.fuse_gelu && hm_d == 0 && !ep.residual && !ep.gate) {
+    if (g_opt.fusion && g_opt.fuse_gelu && hm_d == 0 && !ep.residual && !ep.gate) {
         const int ju = gi.sole(last);
         if (ju >= 0 && xop(gi.node(ju)) == GGML_OP_UNARY && xunary(gi.node(ju)) == GGML_UNARY_OP_GELU && gi.node(ju)->src[0] == gi.node(last) &&
             contig(gi.node(ju)) && M % 64 == 0 && all_consumers_gemm16(gi, ju, false)) {
@@ -1090,7 +1076,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     // FF1 -> GEGLU (block.hpp:193-210): [bias ADD] -> {VIEW lo, VIEW hi} ; CONT(hi) -> GELU -> MUL(lo, .) feeding only gemm16 GEMMs (FF2):
     // one kernel computes value and gate columns side by side and writes the f16 operand image of FF2
     int geglu_out = -1;
-    if (g_opt.fusion && g_opt.gemm16 && hm_d == 0 && !ep.residual && gelu_out < 0 && M % 128 == 0 && gi.consumers[last].size() == 2) {
+    if (g_opt.fusion && hm_d == 0 && !ep.residual && gelu_out < 0 && M % 128 == 0 && gi.consumers[last].size() == 2) {
         const ggml_tensor* X = gi.node(last);
         const int64_t inner  = M / 2;
         int vlo = -1, vhi = -1;
@@ -1144,9 +1130,9 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         const int wt       = (int)w->type;
         const bool silu    = xsrc != x;
         B.emit_at(emit_node, i, [=](hipStream_t st) { launch_qgemv(st, qdst, M, qx, qxs, tokens, wraw, wt, K, M, P->arena + wsoff, ep, 1.0f, silu); });
-        g_stats.qgemv_linears++;
-        g_stats.fused_linear++;
-        if (silu) g_stats.fused_presilu++;
+        STAT(qgemv_linears)++;
+        STAT(fused_linear)++;
+        if (silu) STAT(fused_presilu)++;
         return;
     }
     // f16 / f32 weights under <= 16 rows: k_fgemv (f32 weights keep f32 x f32 like ggml-cpu; the MFMA image would round them to f16)
@@ -1158,9 +1144,9 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         const int wt      = (int)w->type;
         const bool silu   = xsrc != x;
         B.emit([=](hipStream_t st) { launch_fgemv(st, fdst, M, fx, fxs, tokens, wp, wt, K, M, ep, silu); });
-        g_stats.fgemv_linears++;
-        g_stats.fused_linear++;
-        if (silu) g_stats.fused_presilu++;
+        STAT(fgemv_linears)++;
+        STAT(fused_linear)++;
+        if (silu) STAT(fused_presilu)++;
         return;
     }
     if (xsrc != x) {  // the Linear goes to a GEMM after all: run the deferred SiLU now
@@ -1171,7 +1157,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     }
     // ... and under a few hundred rows (text-stream Linears, text encoders): the raw blocks again, dequantised in registers on the way into the
     // MFMA units (k_qgemm16) — below ~300 rows a GEMM is bound by its weight stream, and the quantised stream is 1.9x / 3.6x smaller
-    const bool useq  = g_opt.gemm16 && g_opt.qgemm16 && hm_d == 0 && geglu_out < 0 && qgemm16_supported((int)w->type, tokens, K, M);
+    const bool useq  = g_opt.qgemm16 && hm_d == 0 && geglu_out < 0 && qgemm16_supported((int)w->type, tokens, K, M);
     const void* wraw = w->data;
     const int wt     = (int)w->type;
     // resident-quantised weights (option jit_qimages = least activation rows, default 4096; 1 = always, 0 = never): such a Linear gets NO cached f16 image — the image is
@@ -1180,14 +1166,14 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     // ... and above that range (round 6): the pipelined 256 x 256 GEMM tile itself takes the raw blocks — fetched by LDS-DMA into a raw ring, dequantised once per
     // workgroup into the B stage its MFMA fragments are read from (k_gemm16<..., QT>, gemm16.hip) — wherever the launch takes that tile anyway.  No f16 image exists
     // for such a weight, cached or rebuilt.  Bitwise the image path's result.  Option qinloop_min_rows (0 = off).
-    const bool qin = !useq && g_opt.gemm16 && geglu_out < 0 && hm_d == 0 && !B.hm_hoisting && nchw_add < 0 && (wt == 8 || wt == 2) &&
+    const bool qin = !useq && geglu_out < 0 && hm_d == 0 && !B.hm_hoisting && nchw_add < 0 && (wt == 8 || wt == 2) &&
                      (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, K) && aligned16(w->data) && gemm16_qinloop_supported(wt, tokens, M, K, 1, 1);
     if (qin) {
         ep.qtype      = wt;
         ep.qrow_bytes = (int64_t)w->nb[1];
-        g_stats.qinloop_linears++;
+        STAT(qinloop_linears)++;
     }
-    const bool jit = !useq && !qin && g_opt.jit_qimages > 0 && tokens >= g_opt.jit_qimages && g_opt.gemm16 && geglu_out < 0 && hm_d == 0 && !B.hm_hoisting && wswz_q_supported((int)w->type, K) &&
+    const bool jit = !useq && !qin && g_opt.jit_qimages > 0 && tokens >= g_opt.jit_qimages && geglu_out < 0 && hm_d == 0 && !B.hm_hoisting && wswz_q_supported((int)w->type, K) &&
                      (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, K) && aligned16(w->data);
     const int geglu_mode = geglu_out >= 0 ? gemm16_geglu_mode(tokens, M, K) : 0;
     const void* swz = useq ? nullptr : qin ? w->data : (jit ? B.P->jit_buffer(wswz_bytes(M, K), B.jit_seq[wswz_bytes(M, K)]++) : get_swz_linear(B.P, w, s, geglu_mode));
@@ -1195,232 +1181,227 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         void* jb          = const_cast<void*>(swz);
         const void* wsrc  = w->data;
         const int wty     = (int)w->type;
-        Step js([=](hipStream_t st) { launch_wswz_q(st, jb, wsrc, wty, K, M); });
-        js.tag     = 2;
-        js.side_fn = js.fn;
-        B.emit_at(emit_node, i, std::move(js));
-        g_stats.jit_images++;
+        B.emit_at(emit_node, i, [=](hipStream_t st) { launch_wswz_q(st, jb, wsrc, wty, K, M); });
+        STAT(jit_images)++;
     }
     float* dst      = (float*)gi.node(last)->data;
     const float* xp = (const float*)x->data;
     const int64_t xs = (int64_t)x->nb[1] / 4;
-    if (g_opt.gemm16) {
-        // gen-2: A operand = f16 image in the private arena (written by the producer, or packed here once per tensor)
-        const ggml_tensor* key = strip_reshape(x);
-        auto it = B.packed.find(key);
-        if (it == B.packed.end() || it->second.nhwc) {
-            Packed pk{B.alloc((size_t)tokens * rup64(K) * 2), rup64(K), false};
-            Planner* P = B.P;
-            const size_t off = pk.off;
-            const bool runs  = x->ne[2] > 1 && x->nb[2] != x->nb[1] * (size_t)x->ne[1];
-            const int64_t pL = runs ? x->ne[1] : 0, pbs = runs ? (int64_t)x->nb[2] / 4 : 0;
-            B.emit([=](hipStream_t st) { launch_pack_rows_f16(st, P->arena + off, xp, tokens, K, xs, pL, pbs); });
-            it = B.packed.emplace(key, pk).first;
-            if (it->second.nhwc) it->second = pk;
-        }
-        Planner* P       = B.P;
-        size_t off       = it->second.off;
-        const int64_t ld = it->second.ld;
-        if (it->second.runL > 0) {
-            // the rows sit in runs inside a wider f16 image (a token slice of an attention output, plan_single FLASH_ATTN_EXT): the plain Linear launches take the
-            // run geometry; launches that cannot (grouped head-major projections, GEGLU, the NCHW epilogue) get the rows gathered into an image of their own first
-            const int64_t rL = it->second.runL, rS = it->second.runS;
-            if (geglu_out >= 0 || hm_d > 0 || nchw_add >= 0) {
-                const size_t goff = B.alloc((size_t)tokens * ld * 2), soff = off;
-                const int64_t nrun = tokens / rL;
-                B.emit([=](hipStream_t st) {
-                    for (int64_t r = 0; r < nrun; ++r)
-                        (void)hipMemcpyAsync(P->arena + goff + (size_t)(r * rL * ld * 2), P->arena + soff + (size_t)(r * rS * ld * 2), (size_t)(rL * ld * 2), hipMemcpyDeviceToDevice, st);
-                });
-                off = goff;
-            } else {
-                ep.a_run_L = rL;
-                ep.a_run_S = rS;
-            }
-        }
-        if (nchw_add >= 0 && !useq && swz && ld == rup64(K) && geglu_out < 0 && gelu_out < 0 && !ep.gate && !redir) {
-            float* ndst             = (float*)gi.node(nchw_add)->data;
-            const int64_t HWt = nchw_HW, Nimg = nchw_N;
-            const float* resp       = nchw_res;
-            const Builder::Split sk = B.plan_split(tokens, M, rup64(K), true, true);
-            B.emit_at(emit_node, i, [=](hipStream_t st) {
-                Epilogue e2 = ep;
-                e2.residual = resp;
-                launch_gemm16_conv(st, ndst, P->arena + off, swz, HWt, 1, K, Nimg, M, 1, 1, 0, false, e2, sk.ws(P), sk.cnt(P), sk.S);
+    // A operand = f16 image in the private arena (written by the producer, or packed here once per tensor)
+    const ggml_tensor* key = strip_reshape(x);
+    auto it = B.packed.find(key);
+    if (it == B.packed.end() || it->second.nhwc) {
+        Packed pk{B.alloc((size_t)tokens * rup64(K) * 2), rup64(K), false};
+        Planner* P = B.P;
+        const size_t off = pk.off;
+        const bool runs  = x->ne[2] > 1 && x->nb[2] != x->nb[1] * (size_t)x->ne[1];
+        const int64_t pL = runs ? x->ne[1] : 0, pbs = runs ? (int64_t)x->nb[2] / 4 : 0;
+        B.emit([=](hipStream_t st) { launch_pack_rows_f16(st, P->arena + off, xp, tokens, K, xs, pL, pbs); });
+        it = B.packed.emplace(key, pk).first;
+        if (it->second.nhwc) it->second = pk;
+    }
+    Planner* P       = B.P;
+    size_t off       = it->second.off;
+    const int64_t ld = it->second.ld;
+    if (it->second.runL > 0) {
+        // the rows sit in runs inside a wider f16 image (a token slice of an attention output, plan_single FLASH_ATTN_EXT): the plain Linear launches take the
+        // run geometry; launches that cannot (grouped head-major projections, GEGLU, the NCHW epilogue) get the rows gathered into an image of their own first
+        const int64_t rL = it->second.runL, rS = it->second.runS;
+        if (geglu_out >= 0 || hm_d > 0 || nchw_add >= 0) {
+            const size_t goff = B.alloc((size_t)tokens * ld * 2), soff = off;
+            const int64_t nrun = tokens / rL;
+            B.emit([=](hipStream_t st) {
+                for (int64_t r = 0; r < nrun; ++r)
+                    (void)hipMemcpyAsync(P->arena + goff + (size_t)(r * rL * ld * 2), P->arena + soff + (size_t)(r * rS * ld * 2), (size_t)(rL * ld * 2), hipMemcpyDeviceToDevice, st);
             });
-            g_stats.fused_linear++;
-            g_stats.fused_proj_tokens++;
-            return;
-        }
-        if (nchw_add >= 0) {  // the chain was extended for nothing: give the nodes behind the bias back to the walk
-            while (!chain.empty() && chain.back() != last) chain.pop_back();
-        }
-        if (geglu_out >= 0) {
-            const size_t ooff  = B.alloc((size_t)tokens * (M / 2) * 2);
-            const float* biasp = ep.bias;
-            const Builder::Split sk = B.plan_split(tokens, M, K, false, false, true);  // stream-K or nothing
-            B.emit([=](hipStream_t st) { launch_gemm16_linear_geglu(st, P->arena + ooff, P->arena + off, ld, swz, tokens, K, M, biasp, sk.ws(P), sk.cnt(P), sk.S, geglu_mode); });
-            B.packed[gi.node(geglu_out)] = Packed{ooff, M / 2, false};
-            g_stats.fused_geglu++;
-            g_stats.fused_linear_geglu++;
-        } else if (gelu_out >= 0) {
-            const size_t ooff = B.alloc((size_t)tokens * M * 2);
-            if (useq) {
-                B.emit([=](hipStream_t st) { launch_qgemm16(st, nullptr, P->arena + ooff, M, P->arena + off, ld, tokens, wraw, wt, K, M, ep); });
-                g_stats.qgemm16_linears++;
-            } else {
-                const Builder::Split sk = B.plan_split(tokens, M, K, false, false);
-                B.emit([=](hipStream_t st) { launch_gemm16_linear(st, nullptr, P->arena + ooff, M, P->arena + off, ld, swz, tokens, K, M, M, ep, 0, 0, 0, sk.ws(P), sk.cnt(P), sk.S); });
-            }
-            B.packed[gi.node(gelu_out)] = Packed{ooff, M, false};
-            g_stats.fused_gelu++;
-        } else if (hm_d > 0) {
-            void* hdst = gi.node(last)->data;
-            g_stats.head_major_gemms++;
-            const bool f16o = hm_f16;
-            const int hd = hm_d, hH = hm_H, hL = hm_L;
-            // the f32 CONT is the Q operand of a FLASH_ATTN_EXT node and nothing else reads it (ggml_extend.hpp:1373-1376, 1437): store it as an
-            // f16 head-major image in the arena instead — the kernel rounds Q to f16 anyway; half the bytes written here and read there
-            int qflash = -1, qview = -1;
-            if (!f16o && g_opt.fuse_q16 && hd % 8 == 0) {
-                const int c1 = gi.sole(last);
-                const int c2 = (c1 >= 0 && xop(gi.node(c1)) == GGML_OP_RESHAPE) ? gi.sole(c1) : -1;
-                if (c2 >= 0 && xop(gi.node(c2)) == GGML_OP_FLASH_ATTN_EXT && gi.node(c2)->src[0] == gi.node(c1) && !gi.node(c2)->src[3] && contig(gi.node(c1)) &&
-                    gi.node(c1)->ne[0] == hd && flash_attn_supported(hd, gi.node(c2)->src[2]->ne[0])) {
-                    qflash = c2;
-                    qview  = c1;
-                }
-            }
-            const bool groupable = B.hm_grouping && !ep.residual && !ep.gate && !ep.gelu && !ep.chan_add;
-            if (qflash >= 0) {
-                const size_t qoff        = B.alloc((size_t)tokens * M * 2);
-                B.q16[gi.node(qview)]    = qoff;
-                g_stats.fused_q16++;
-                const Builder::Split sk = B.plan_split(tokens, M, K, false, false);
-                if (groupable && sk.S <= 1)
-                    B.hm_group.push_back(Builder::HmLaunch{i, last, nullptr, nullptr, qoff, true, off, ld, swz, tokens, K, M, ep, hd, hH, hL});
-                else
-                    B.emit([=](hipStream_t st) { launch_gemm16_linear(st, nullptr, P->arena + qoff, 0, P->arena + off, ld, swz, tokens, K, M, M, ep, hd, hH, hL, sk.ws(P), sk.cnt(P), sk.S); });
-            } else {
-                const Builder::Split sk = (hL >= 32 && !B.hm_hoisting) ? B.plan_split(tokens, M, K, false, false) : Builder::Split();
-                if (groupable && sk.S <= 1)
-                    B.hm_group.push_back(Builder::HmLaunch{i, last, f16o ? nullptr : (float*)hdst, f16o ? hdst : nullptr, 0, false, off, ld, swz, tokens, K, M, ep, hd, hH, hL});
-                else
-                    B.emit([=](hipStream_t st) {
-                        launch_gemm16_linear(st, f16o ? nullptr : (float*)hdst, f16o ? hdst : nullptr, 0, P->arena + off, ld, swz, tokens, K, M, M, ep, hd, hH, hL, sk.ws(P), sk.cnt(P), sk.S);
-                    });
-            }
-        } else if (useq) {
-            const int S        = ep.gate ? 1 : qgemm16_split_k(tokens, K, M);
-            const size_t wsoff = S > 1 ? B.alloc((size_t)S * tokens * M * 4) : 0;
-            B.emit_at(emit_node, i, [=](hipStream_t st) {
-                launch_qgemm16(st, redir ? (float*)(P->arena + redir_off) : dst, nullptr, 0, P->arena + off, ld, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S);
-            });
-            if (redir) B.redirect_taken.insert(gi.node(last));
-            g_stats.qgemm16_linears++;
-        } else if (g_opt.fuse_rows16 && !ep.gate && emit_node == i && M % 64 == 0 && x->ne[3] == 1 && only_consumer_is_tokens_to_conv(gi, last)) {
-            // FF2 (+bias, +residual) of a SpatialTransformer whose result only proj_out reads (block.hpp:566-572): write the 1x1 conv's f16 operand
-            // rows directly — no f32 tensor, no pack pass (the conv rounds its input to f16 anyway: same rounding point).  Option fuse_rows16,
-            // default OFF: on the SD1.5 bench forward it measured 23.34 vs 23.21 ms per step (profiles/r04h_ab_rows16.txt) — the f32 tensor the
-            // pack pass re-reads sits in the 256 MB Infinity Cache, while the f16 epilogue stores 64-byte row segments
-            const size_t ooff       = B.alloc((size_t)tokens * M * 2);
-            const Builder::Split sk = B.plan_split(tokens, M, K, false, false);
-            B.emit([=](hipStream_t st) { launch_gemm16_linear(st, nullptr, P->arena + ooff, M, P->arena + off, ld, swz, tokens, K, M, M, ep, 0, 0, 0, sk.ws(P), sk.cnt(P), sk.S); });
-            B.packed[gi.node(last)] = Packed{ooff, M, false};
-            g_stats.fused_rows16++;
+            off = goff;
         } else {
-            const Builder::Split sk = B.plan_split(tokens, M, K, false, !ep.gate);
-            // look-ahead: this output -> NORM -> MUL w -> ADD b read only by weight GEMMs (the next LayerNorm of a transformer block).  When the
-            // Linear runs split-K with the slab reduce pass, that pass also writes the LayerNorm's f16 operand image (k_splitk_reduce_ln)
-            bool ln_on       = false;
-            size_t ln_off    = 0;
-            const float *lnw = nullptr, *lnb = nullptr;
-            float lneps      = 0.f;
-            if (g_opt.fuse_ln_reduce && g_opt.fusion && sk.S > 1 && sk.S <= 4 && !sk.inkernel && !redir && !ep.gate && emit_node == i && hm_d == 0 && splitk_reduce_ln_supported(tokens, M) &&
-                !(gi.node(last)->flags & GGML_TENSOR_FLAG_OUTPUT)) {
-                const ggml_tensor* res = gi.node(last);
-                for (int k : gi.consumers[last]) {
-                    const ggml_tensor* nn = gi.node(k);
-                    if (xop(nn) != GGML_OP_NORM || nn->src[0] != res || gi.done[k] || !is_f32(nn) || !contig(nn) || !contig(res) || nn->ne[0] != M) continue;
-                    const int j1 = gi.sole(k);
-                    if (j1 < 0 || xop(gi.node(j1)) != GGML_OP_MUL || gi.node(j1)->src[0] != nn || !bias_like_row(gi.node(j1)->src[1], M) || gi.node(j1)->data != nn->data) break;
-                    const int j2 = gi.sole(j1);
-                    if (j2 < 0 || xop(gi.node(j2)) != GGML_OP_ADD || gi.node(j2)->src[0] != gi.node(j1) || !bias_like_row(gi.node(j2)->src[1], M) || gi.node(j2)->data != nn->data) break;
-                    std::vector<int> lc{k, j1, j2};
-                    if (!gi.only_noops_between(k, j1, lc) || !gi.only_noops_between(j1, j2, lc) || !all_consumers_gemm16(gi, j2, false)) break;
-                    lnw = (const float*)gi.node(j1)->src[1]->data;
-                    lnb = (const float*)gi.node(j2)->src[1]->data;
-                    // the reduce pass moves 16 bytes per lane: decided here with the addresses the launch will see
-                    if (!aligned16(dst) || !aligned16(ep.residual) || !aligned16(ep.bias) || !aligned16(lnw) || !aligned16(lnb)) break;
-                    lneps  = ggml_abi_op_param_f32(nn, 0);
-                    ln_off = B.alloc((size_t)tokens * rup64(M) * 2);
-                    ln_on  = true;
-                    B.ln_pre[res] = Builder::LnPre{ln_off, lnw, lnb, lneps};
-                    g_stats.fused_ln_reduce++;
-                    break;
-                }
-            }
-            // look-ahead (FLUX single block, flux.hpp:594-700: linear1 = [q k v | mlp], linear2(concat(attn, gelu(mlp)))): the tail columns of this
-            // output are read ONLY through VIEW -> CONT -> GELU into linear2's f16 operand image (plan_cat_rows16 registered that CONT): the GEMM's
-            // epilogue stores gelu(.) as f16 straight into the image for those column tiles and never writes their f32 values
-            bool split_on = false;
-            int64_t split_c0 = 0, split_ld = 0;
-            size_t split_off = 0;
-            if (g_opt.fusion && g_opt.fuse_cat_rows16 && g_opt.fuse_split_gelu && sk.S <= 1 && !ln_on && !ep.gate && !ep.residual && hm_d == 0 && emit_node == i && !useq && gemm16_split_col_supported(tokens, M, K)) {
-                const ggml_tensor* T = gi.node(last);
-                for (int c : gi.consumers[last]) {
-                    const ggml_tensor* v = gi.node(c);
-                    if (xop(v) != GGML_OP_VIEW || v->nb[0] != 4 || v->nb[1] != T->nb[1] || v->ne[1] * v->ne[2] * v->ne[3] != tokens) continue;
-                    const int jc = gi.sole(c);
-                    if (jc < 0 || xop(gi.node(jc)) != GGML_OP_CONT) continue;
-                    const auto cp = B.cat16_part.find(gi.node(jc));
-                    if (cp == B.cat16_part.end()) continue;
-                    const int64_t c0 = (int64_t)((const char*)v->data - (const char*)T->data) / 4;
-                    if (c0 <= 0 || c0 % 256 != 0 || c0 + v->ne[0] != M || cp->second.ld % 8 != 0 || cp->second.col % 8 != 0) continue;
-                    // the f32 columns >= c0 are never written: every OTHER reader of T has to be a VIEW confined to columns [0, c0) of the same rows
-                    // (round-4 advice: a full-width read, a second view over the tail or a graph output would see unwritten memory)
-                    bool others_ok = !(T->flags & GGML_TENSOR_FLAG_OUTPUT) && !(v->flags & GGML_TENSOR_FLAG_OUTPUT);
-                    for (int c2 : gi.consumers[last]) {
-                        if (c2 == c || !others_ok) continue;
-                        const ggml_tensor* v2 = gi.node(c2);
-                        if (xop(v2) != GGML_OP_VIEW || v2->nb[0] != 4 || v2->nb[1] != T->nb[1] || (v2->flags & GGML_TENSOR_FLAG_OUTPUT)) {
-                            others_ok = false;
-                            break;
-                        }
-                        const int64_t b2 = (int64_t)((const char*)v2->data - (const char*)T->data);
-                        const int64_t col2 = b2 >= 0 ? (b2 % (int64_t)T->nb[1]) / 4 : -1;
-                        if (b2 < 0 || b2 % 4 != 0 || col2 + v2->ne[0] > c0) others_ok = false;
-                    }
-                    if (!others_ok) continue;
-                    split_on  = true;
-                    split_c0  = c0;
-                    split_ld  = cp->second.ld;
-                    split_off = cp->second.off + (size_t)cp->second.col * 2;
-                    B.cat16[cp->second.cat].written[cp->second.part] = true;
-                    B.cat16_by_linear.insert(gi.node(jc));
-                    g_stats.fused_gelu++;
-                    break;
-                }
-            }
-            B.emit_at(emit_node, i, [=](hipStream_t st) {
-                Epilogue e2 = ep;
-                if (split_on) {
-                    e2.split_col   = split_c0;
-                    e2.split_dst16 = P->arena + split_off;
-                    e2.split_ldd16 = split_ld;
-                }
-                if (ln_on) {
-                    e2.ln_dst16 = P->arena + ln_off;
-                    e2.ln_w     = lnw;
-                    e2.ln_b     = lnb;
-                    e2.ln_eps   = lneps;
-                }
-                launch_gemm16_linear(st, redir ? (float*)(P->arena + redir_off) : dst, nullptr, 0, P->arena + off, ld, swz, tokens, K, M, M, e2, 0, 0, 0, sk.ws(P), sk.cnt(P), sk.S);
-            });
-            if (redir) B.redirect_taken.insert(gi.node(last));
+            ep.a_run_L = rL;
+            ep.a_run_S = rS;
         }
     }
-    g_stats.fused_linear++;
+    if (nchw_add >= 0 && !useq && swz && ld == rup64(K) && geglu_out < 0 && gelu_out < 0 && !ep.gate && !redir) {
+        float* ndst             = (float*)gi.node(nchw_add)->data;
+        const int64_t HWt = nchw_HW, Nimg = nchw_N;
+        const float* resp       = nchw_res;
+        const Builder::Split sk = B.plan_split(tokens, M, rup64(K), true, true);
+        B.emit_at(emit_node, i, [=](hipStream_t st) {
+            Epilogue e2 = ep;
+            e2.residual = resp;
+            launch_gemm16_conv(st, ndst, P->arena + off, swz, HWt, 1, K, Nimg, M, 1, 1, 0, false, e2, sk.ws(P), sk.cnt(P), sk.S);
+        });
+        STAT(fused_linear)++;
+        STAT(fused_proj_tokens)++;
+        return;
+    }
+    if (nchw_add >= 0) {  // the chain was extended for nothing: give the nodes behind the bias back to the walk
+        while (!chain.empty() && chain.back() != last) chain.pop_back();
+    }
+    if (geglu_out >= 0) {
+        const size_t ooff  = B.alloc((size_t)tokens * (M / 2) * 2);
+        const float* biasp = ep.bias;
+        const Builder::Split sk = B.plan_split(tokens, M, K, false, false, true);  // stream-K or nothing
+        B.emit([=](hipStream_t st) { launch_gemm16_linear_geglu(st, P->arena + ooff, P->arena + off, ld, swz, tokens, K, M, biasp, sk.ws(P), sk.cnt(P), sk.S, geglu_mode); });
+        B.packed[gi.node(geglu_out)] = Packed{ooff, M / 2, false};
+        STAT(fused_geglu)++;
+        STAT(fused_linear_geglu)++;
+    } else if (gelu_out >= 0) {
+        const size_t ooff = B.alloc((size_t)tokens * M * 2);
+        if (useq) {
+            B.emit([=](hipStream_t st) { launch_qgemm16(st, nullptr, P->arena + ooff, M, P->arena + off, ld, tokens, wraw, wt, K, M, ep); });
+            STAT(qgemm16_linears)++;
+        } else {
+            const Builder::Split sk = B.plan_split(tokens, M, K, false, false);
+            B.emit([=](hipStream_t st) { launch_gemm16_linear(st, nullptr, P->arena + ooff, M, P->arena + off, ld, swz, tokens, K, M, M, ep, 0, 0, 0, sk.ws(P), sk.cnt(P), sk.S); });
+        }
+        B.packed[gi.node(gelu_out)] = Packed{ooff, M, false};
+        STAT(fused_gelu)++;
+    } else if (hm_d > 0) {
+        void* hdst = gi.node(last)->data;
+        STAT(head_major_gemms)++;
+        const bool f16o = hm_f16;
+        const int hd = hm_d, hH = hm_H, hL = hm_L;
+        // the f32 CONT is the Q operand of a FLASH_ATTN_EXT node and nothing else reads it (ggml_extend.hpp:1373-1376, 1437): store it as an
+        // f16 head-major image in the arena instead — the kernel rounds Q to f16 anyway; half the bytes written here and read there
+        int qflash = -1, qview = -1;
+        if (!f16o && g_opt.fuse_q16 && hd % 8 == 0) {
+            const int c1 = gi.sole(last);
+            const int c2 = (c1 >= 0 && xop(gi.node(c1)) == GGML_OP_RESHAPE) ? gi.sole(c1) : -1;
+            if (c2 >= 0 && xop(gi.node(c2)) == GGML_OP_FLASH_ATTN_EXT && gi.node(c2)->src[0] == gi.node(c1) && !gi.node(c2)->src[3] && contig(gi.node(c1)) &&
+                gi.node(c1)->ne[0] == hd && flash_attn_supported(hd, gi.node(c2)->src[2]->ne[0])) {
+                qflash = c2;
+                qview  = c1;
+            }
+        }
+        const bool groupable = B.hm_grouping && !ep.residual && !ep.gate && !ep.gelu && !ep.chan_add;
+        if (qflash >= 0) {
+            const size_t qoff        = B.alloc((size_t)tokens * M * 2);
+            B.q16[gi.node(qview)]    = qoff;
+            STAT(fused_q16)++;
+            const Builder::Split sk = B.plan_split(tokens, M, K, false, false);
+            if (groupable && sk.S <= 1)
+                B.hm_group.push_back(Builder::HmLaunch{i, last, nullptr, nullptr, qoff, true, off, ld, swz, tokens, K, M, ep, hd, hH, hL});
+            else
+                B.emit([=](hipStream_t st) { launch_gemm16_linear(st, nullptr, P->arena + qoff, 0, P->arena + off, ld, swz, tokens, K, M, M, ep, hd, hH, hL, sk.ws(P), sk.cnt(P), sk.S); });
+        } else {
+            const Builder::Split sk = (hL >= 32 && !B.hm_hoisting) ? B.plan_split(tokens, M, K, false, false) : Builder::Split();
+            if (groupable && sk.S <= 1)
+                B.hm_group.push_back(Builder::HmLaunch{i, last, f16o ? nullptr : (float*)hdst, f16o ? hdst : nullptr, 0, false, off, ld, swz, tokens, K, M, ep, hd, hH, hL});
+            else
+                B.emit([=](hipStream_t st) {
+                    launch_gemm16_linear(st, f16o ? nullptr : (float*)hdst, f16o ? hdst : nullptr, 0, P->arena + off, ld, swz, tokens, K, M, M, ep, hd, hH, hL, sk.ws(P), sk.cnt(P), sk.S);
+                });
+        }
+    } else if (useq) {
+        const int S        = ep.gate ? 1 : qgemm16_split_k(tokens, K, M);
+        const size_t wsoff = S > 1 ? B.alloc((size_t)S * tokens * M * 4) : 0;
+        B.emit_at(emit_node, i, [=](hipStream_t st) {
+            launch_qgemm16(st, redir ? (float*)(P->arena + redir_off) : dst, nullptr, 0, P->arena + off, ld, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S);
+        });
+        if (redir) B.redirect_taken.insert(gi.node(last));
+        STAT(qgemm16_linears)++;
+    } else if (g_opt.fuse_rows16 && !ep.gate && emit_node == i && M % 64 == 0 && x->ne[3] == 1 && only_consumer_is_tokens_to_conv(gi, last)) {
+        // FF2 (+bias, +residual) of a SpatialTransformer whose result only proj_out reads (block.hpp:566-572): write the 1x1 conv's f16 operand
+        // rows directly — no f32 tensor, no pack pass (the conv rounds its input to f16 anyway: same rounding point).  Option fuse_rows16,
+        // default OFF: on the SD1.5 bench forward it measured 23.34 vs 23.21 ms per step (profiles/r04h_ab_rows16.txt) — the f32 tensor the
+        // pack pass re-reads sits in the 256 MB Infinity Cache, while the f16 epilogue stores 64-byte row segments
+        const size_t ooff       = B.alloc((size_t)tokens * M * 2);
+        const Builder::Split sk = B.plan_split(tokens, M, K, false, false);
+        B.emit([=](hipStream_t st) { launch_gemm16_linear(st, nullptr, P->arena + ooff, M, P->arena + off, ld, swz, tokens, K, M, M, ep, 0, 0, 0, sk.ws(P), sk.cnt(P), sk.S); });
+        B.packed[gi.node(last)] = Packed{ooff, M, false};
+        STAT(fused_rows16)++;
+    } else {
+        const Builder::Split sk = B.plan_split(tokens, M, K, false, !ep.gate);
+        // look-ahead: this output -> NORM -> MUL w -> ADD b read only by weight GEMMs (the next LayerNorm of a transformer block).  When the
+        // Linear runs split-K with the slab reduce pass, that pass also writes the LayerNorm's f16 operand image (k_splitk_reduce_ln)
+        bool ln_on       = false;
+        size_t ln_off    = 0;
+        const float *lnw = nullptr, *lnb = nullptr;
+        float lneps      = 0.f;
+        if (g_opt.fuse_ln_reduce && g_opt.fusion && sk.S > 1 && sk.S <= 4 && !sk.inkernel && !redir && !ep.gate && emit_node == i && hm_d == 0 && splitk_reduce_ln_supported(tokens, M) &&
+            !(gi.node(last)->flags & GGML_TENSOR_FLAG_OUTPUT)) {
+            const ggml_tensor* res = gi.node(last);
+            for (int k : gi.consumers[last]) {
+                const ggml_tensor* nn = gi.node(k);
+                if (xop(nn) != GGML_OP_NORM || nn->src[0] != res || gi.done[k] || !is_f32(nn) || !contig(nn) || !contig(res) || nn->ne[0] != M) continue;
+                const int j1 = gi.sole(k);
+                if (j1 < 0 || xop(gi.node(j1)) != GGML_OP_MUL || gi.node(j1)->src[0] != nn || !bias_like_row(gi.node(j1)->src[1], M) || gi.node(j1)->data != nn->data) break;
+                const int j2 = gi.sole(j1);
+                if (j2 < 0 || xop(gi.node(j2)) != GGML_OP_ADD || gi.node(j2)->src[0] != gi.node(j1) || !bias_like_row(gi.node(j2)->src[1], M) || gi.node(j2)->data != nn->data) break;
+                std::vector<int> lc{k, j1, j2};
+                if (!gi.only_noops_between(k, j1, lc) || !gi.only_noops_between(j1, j2, lc) || !all_consumers_gemm16(gi, j2, false)) break;
+                lnw = (const float*)gi.node(j1)->src[1]->data;
+                lnb = (const float*)gi.node(j2)->src[1]->data;
+                // the reduce pass moves 16 bytes per lane: decided here with the addresses the launch will see
+                if (!aligned16(dst) || !aligned16(ep.residual) || !aligned16(ep.bias) || !aligned16(lnw) || !aligned16(lnb)) break;
+                lneps  = ggml_abi_op_param_f32(nn, 0);
+                ln_off = B.alloc((size_t)tokens * rup64(M) * 2);
+                ln_on  = true;
+                B.ln_pre[res] = Builder::LnPre{ln_off, lnw, lnb, lneps};
+                STAT(fused_ln_reduce)++;
+                break;
+            }
+        }
+        // look-ahead (FLUX single block, flux.hpp:594-700: linear1 = [q k v | mlp], linear2(concat(attn, gelu(mlp)))): the tail columns of this
+        // output are read ONLY through VIEW -> CONT -> GELU into linear2's f16 operand image (plan_cat_rows16 registered that CONT): the GEMM's
+        // epilogue stores gelu(.) as f16 straight into the image for those column tiles and never writes their f32 values
+        bool split_on = false;
+        int64_t split_c0 = 0, split_ld = 0;
+        size_t split_off = 0;
+        if (g_opt.fusion && g_opt.fuse_cat_rows16 && g_opt.fuse_split_gelu && sk.S <= 1 && !ln_on && !ep.gate && !ep.residual && hm_d == 0 && emit_node == i && !useq && gemm16_split_col_supported(tokens, M, K)) {
+            const ggml_tensor* T = gi.node(last);
+            for (int c : gi.consumers[last]) {
+                const ggml_tensor* v = gi.node(c);
+                if (xop(v) != GGML_OP_VIEW || v->nb[0] != 4 || v->nb[1] != T->nb[1] || v->ne[1] * v->ne[2] * v->ne[3] != tokens) continue;
+                const int jc = gi.sole(c);
+                if (jc < 0 || xop(gi.node(jc)) != GGML_OP_CONT) continue;
+                const auto cp = B.cat16_part.find(gi.node(jc));
+                if (cp == B.cat16_part.end()) continue;
+                const int64_t c0 = (int64_t)((const char*)v->data - (const char*)T->data) / 4;
+                if (c0 <= 0 || c0 % 256 != 0 || c0 + v->ne[0] != M || cp->second.ld % 8 != 0 || cp->second.col % 8 != 0) continue;
+                // the f32 columns >= c0 are never written: every OTHER reader of T has to be a VIEW confined to columns [0, c0) of the same rows
+                // (round-4 advice: a full-width read, a second view over the tail or a graph output would see unwritten memory)
+                bool others_ok = !(T->flags & GGML_TENSOR_FLAG_OUTPUT) && !(v->flags & GGML_TENSOR_FLAG_OUTPUT);
+                for (int c2 : gi.consumers[last]) {
+                    if (c2 == c || !others_ok) continue;
+                    const ggml_tensor* v2 = gi.node(c2);
+                    if (xop(v2) != GGML_OP_VIEW || v2->nb[0] != 4 || v2->nb[1] != T->nb[1] || (v2->flags & GGML_TENSOR_FLAG_OUTPUT)) {
+                        others_ok = false;
+                        break;
+                    }
+                    const int64_t b2 = (int64_t)((const char*)v2->data - (const char*)T->data);
+                    const int64_t col2 = b2 >= 0 ? (b2 % (int64_t)T->nb[1]) / 4 : -1;
+                    if (b2 < 0 || b2 % 4 != 0 || col2 + v2->ne[0] > c0) others_ok = false;
+                }
+                if (!others_ok) continue;
+                split_on  = true;
+                split_c0  = c0;
+                split_ld  = cp->second.ld;
+                split_off = cp->second.off + (size_t)cp->second.col * 2;
+                B.cat16[cp->second.cat].written[cp->second.part] = true;
+                B.cat16_by_linear.insert(gi.node(jc));
+                STAT(fused_gelu)++;
+                break;
+            }
+        }
+        B.emit_at(emit_node, i, [=](hipStream_t st) {
+            Epilogue e2 = ep;
+            if (split_on) {
+                e2.split_col   = split_c0;
+                e2.split_dst16 = P->arena + split_off;
+                e2.split_ldd16 = split_ld;
+            }
+            if (ln_on) {
+                e2.ln_dst16 = P->arena + ln_off;
+                e2.ln_w     = lnw;
+                e2.ln_b     = lnb;
+                e2.ln_eps   = lneps;
+            }
+            launch_gemm16_linear(st, redir ? (float*)(P->arena + redir_off) : dst, nullptr, 0, P->arena + off, ld, swz, tokens, K, M, M, e2, 0, 0, 0, sk.ws(P), sk.cnt(P), sk.S);
+        });
+        if (redir) B.redirect_taken.insert(gi.node(last));
+    }
+    STAT(fused_linear)++;
 }
 
 static Step hm_single_step(Planner* P, const Builder::HmLaunch& h) {
@@ -1499,7 +1480,7 @@ void plan_sibling_group(Builder& B, int i, hipStream_t s, std::vector<int>& chai
     }
     const std::vector<Builder::HmLaunch> grp = B.hm_group;
     B.hm_group.clear();
-    g_stats.fused_sibling_linears += (int64_t)grp.size() - 1;
+    STAT(fused_sibling_linears) += (int64_t)grp.size() - 1;
     B.emit_at(emit_pos, i, [=](hipStream_t st) {
         float* dst[16]        = {};
         void* dst16[16]       = {};
@@ -1524,7 +1505,7 @@ void plan_sibling_group(Builder& B, int i, hipStream_t s, std::vector<int>& chai
 // allocated that early); the FLASH_ATTN_EXT nodes read them from there (Builder::moved).  Only contexts that are graph inputs or a REPEAT of one
 // are hoisted: nothing fused can decide later not to materialise their f32 rows.
 void plan_hoisted_kv(Builder& B, hipStream_t s) {
-    if (!g_opt.hoist_kv || !g_opt.fusion || !g_opt.gemm16 || !g_opt.fuse_siblings) return;
+    if (!g_opt.hoist_kv || !g_opt.fusion || !g_opt.fuse_siblings) return;
     GInfo& gi  = B.gi;
     Planner* P = B.P;
     struct Key {
@@ -1601,8 +1582,8 @@ void plan_hoisted_kv(Builder& B, hipStream_t s) {
                 h.dst16       = nullptr;
                 B.moved[gi.node(h.out_node)] = h.dst16_off;
             }
-            g_stats.hoisted_kv_linears += (int64_t)grp.size();
-            g_stats.fused_sibling_linears += (int64_t)grp.size() - 1;
+            STAT(hoisted_kv_linears) += (int64_t)grp.size();
+            STAT(fused_sibling_linears) += (int64_t)grp.size() - 1;
             B.deferred[j0].push_back([=](hipStream_t st) {
                 float* dst[16]        = {};
                 void* dst16[16]       = {};
@@ -1633,7 +1614,7 @@ struct EmbMember {
     int64_t M;
 };
 void plan_hoisted_emb(Builder& B, hipStream_t s) {
-    if (!g_opt.hoist_emb || !g_opt.fusion || !g_opt.gemm16 || !g_opt.fuse_chan_add) return;
+    if (!g_opt.hoist_emb || !g_opt.fusion || !g_opt.fuse_chan_add) return;
     GInfo& gi  = B.gi;
     Planner* P = B.P;
     struct Key {
@@ -1704,7 +1685,7 @@ void plan_hoisted_emb(Builder& B, hipStream_t s) {
                 bo += (size_t)m.M * 4;
             }
             P->swz[key] = {d, wbytes + bbytes + 256, nullptr, (size_t)-1};  // src range "everything": dropped on any weight rewrite / buffer free
-            g_stats.swizzled_weight_bytes += (int64_t)(wbytes + bbytes);
+            STAT(swizzled_weight_bytes) += (int64_t)(wbytes + bbytes);
         }
         const size_t ooff = B.alloc((size_t)k.rows * Mtot * 4);
         int64_t col       = 0;
@@ -1730,9 +1711,9 @@ void plan_hoisted_emb(Builder& B, hipStream_t s) {
             else
                 launch_fgemv(st, out, Mtot, ex, xs, rows, catp, wt, K, Mtot, ep, true);
         });
-        g_stats.hoisted_emb_linears += (int64_t)mem.size();
-        g_stats.fused_linear += (int64_t)mem.size();
-        g_stats.fused_presilu += (int64_t)mem.size();
+        STAT(hoisted_emb_linears) += (int64_t)mem.size();
+        STAT(fused_linear) += (int64_t)mem.size();
+        STAT(fused_presilu) += (int64_t)mem.size();
     }
 }
 
@@ -1830,10 +1811,10 @@ void plan_hoisted_mod(Builder& B, hipStream_t) {
         const int64_t xs = (int64_t)k.e->nb[1] / 4, rows = k.rows, K = k.K;
         const int wt     = k.wtype, nm = (int)mem.size();
         B.deferred[first].insert(B.deferred[first].begin(), [=](hipStream_t st) { launch_qgemv_group(st, (float*)(P->arena + ooff), Mtot, ex, xs, rows, table, nm, wt, K, 1.0f, true); });
-        g_stats.hoisted_mod_linears += (int64_t)mem.size();
-        g_stats.fused_linear += (int64_t)mem.size();
-        g_stats.fused_presilu += (int64_t)mem.size();
-        g_stats.qgemv_linears += (int64_t)mem.size();
+        STAT(hoisted_mod_linears) += (int64_t)mem.size();
+        STAT(fused_linear) += (int64_t)mem.size();
+        STAT(fused_presilu) += (int64_t)mem.size();
+        STAT(qgemv_linears) += (int64_t)mem.size();
     }
 }
 
@@ -1898,14 +1879,14 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
     Epilogue ep;
     int last = j5;
     // -> SCALE(1 / s): the second half of a Conv2d scale (ggml_ext_conv_2d: applied to the conv result BEFORE the bias) = the epilogue's accumulator scale
-    if (g_opt.fuse_conv_scale && g_opt.gemm16) {
+    if (g_opt.fuse_conv_scale) {
         const int jS = gi.sole(last);
         if (jS >= 0 && xop(gi.node(jS)) == GGML_OP_SCALE && gi.node(jS)->src[0] == gi.node(last) && ggml_abi_op_param_f32(gi.node(jS), 1) == 0.f && is_f32(gi.node(jS)) &&
             contig(gi.node(jS)) && !(gi.node(last)->flags & GGML_TENSOR_FLAG_OUTPUT) && gi.only_noops_between(last, jS, chain)) {
             ep.scale = ggml_abi_op_param_f32(gi.node(jS), 0);
             chain.push_back(jS);
             last = jS;
-            g_stats.fused_conv_scale++;
+            STAT(fused_conv_scale)++;
         }
     }
     // -> ADD bias [1,1,OC,1]
@@ -1920,7 +1901,7 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
     // token-major [OC, W*H, N] the transformer blocks read.  A 1x1 conv IS a token GEMM: rows = positions of the NHWC operand image,
     // columns = output channels — run it in Linear mode and write the CONT's layout directly (no NCHW tensor, no transpose pass).
     int token_major_out = -1;
-    if (g_opt.fuse_proj_tokens && g_opt.gemm16 && KW == 1 && s0 == 1 && B.ups.find(xs) == B.ups.end()) {
+    if (g_opt.fuse_proj_tokens && KW == 1 && s0 == 1 && B.ups.find(xs) == B.ups.end()) {
         const int jp = gi.sole(last);
         const int jc = (jp >= 0 && xop(gi.node(jp)) == GGML_OP_PERMUTE && gi.node(jp)->src[0] == gi.node(last)) ? gi.sole(jp) : -1;
         if (jc >= 0 && xop(gi.node(jc)) == GGML_OP_CONT && gi.node(jc)->src[0] == gi.node(jp) && is_f32(gi.node(jc)) && contig(gi.node(jc))) {
@@ -1943,7 +1924,7 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
     int emit_node = i;
     bool emb_arena = false;  // the chan_add operand lives in the arena (plan_hoisted_emb)
     size_t emb_off = 0;
-    if (g_opt.fuse_chan_add && g_opt.gemm16 && token_major_out < 0) {
+    if (g_opt.fuse_chan_add && token_major_out < 0) {
         const int r = gi.sole(last);
         if (r >= 0 && xop(gi.node(r)) == GGML_OP_ADD && gi.node(r)->src[0] == gi.node(last)) {
             const ggml_tensor* a = gi.node(r);
@@ -1966,7 +1947,7 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
                     chain.push_back(r);
                     last      = r;
                     emit_node = r;
-                    g_stats.fused_chan_add++;
+                    STAT(fused_chan_add)++;
                     const auto me = B.moved_emb.find(eroot);
                     if (me != B.moved_emb.end()) {  // computed by the grouped launch: read it from the arena (address resolved at launch time)
                         emb_arena  = true;
@@ -1997,7 +1978,7 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
     // look-ahead: a GroupNorm (-> MUL w -> ADD b) that reads this chain's result.  When the conv runs split-K, the slab reduce pass computes its
     // statistics while it writes the values (k_splitk_reduce_gn)
     Builder::GnPre gnp{0, nullptr, nullptr, 0, 0.f};
-    if (g_opt.fuse_gn_stats && g_opt.gemm16 && token_major_out < 0) {
+    if (g_opt.fuse_gn_stats && token_major_out < 0) {
         const ggml_tensor* res = gi.node(last);
         for (int k : gi.consumers[last]) {
             if (gnp.groups) break;
@@ -2019,7 +2000,7 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
         if ((((uintptr_t)final_dst | (uintptr_t)ep.residual) & 15) != 0) return false;
         gnp.off                    = B.alloc((size_t)N * OC * 4 * 2);
         B.gn_pre[gi.node(last)]    = gnp;
-        g_stats.fused_gn_stats++;
+        STAT(fused_gn_stats)++;
         return true;
     };
     auto gn_fill = [](Epilogue& e, const Builder::GnPre& g, char* arena, int64_t nc) {
@@ -2032,73 +2013,70 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
     };
     // 3x3 / stride 1 on 32 / 64 / 128-wide maps: the LDS-window kernel (conv3w.hip), with its own weight image
     const bool ups_in = B.ups.find(xs) != B.ups.end();
-    const int w3S     = (g_opt.gemm16 && token_major_out < 0) ? conv3w_plan(x->ne[0], x->ne[1], IC, N, OC, ks, st_, ups_in) : 0;
+    const int w3S     = (token_major_out < 0) ? conv3w_plan(x->ne[0], x->ne[1], IC, N, OC, ks, st_, ups_in) : 0;
     const void* swz   = get_swz_conv(B.P, ker, s, w3S > 0);
     if (!swz) return false;
-    if (g_opt.gemm16) {
-        // gen-2: the conv reads an f16 NHWC image from the private arena, so the graph allocator's recycling of the
-        // conv input for the chain output is harmless (no bounce).  A deferred nearest-x2 UPSCALE becomes an index shift.
-        const ggml_tensor* src = xs;
-        bool upscale           = false;
-        auto ui                = B.ups.find(xs);
-        if (ui != B.ups.end()) {
-            src     = ui->second;
-            upscale = true;
-        }
-        const int64_t SW = src->ne[0], SH = src->ne[1];
-        auto it = B.packed.find(src);
-        if (it != B.packed.end() && it->second.nhwc && it->second.mul != pre_mul) {
-            fprintf(stderr, "[ggml-mi355x] plan_conv_chain: operand image of node %d was written with factor %g, the conv wants %g\n", i, it->second.mul, pre_mul);
-            return false;
-        }
-        if (it == B.packed.end() || !it->second.nhwc) {
-            Packed pk{B.alloc((size_t)N * SW * SH * rup64(IC) * 2), rup64(IC), true, pre_mul};
-            Planner* P       = B.P;
-            const size_t off = pk.off;
-            const float* sp  = (const float*)src->data;
-            B.emit([=](hipStream_t st) { launch_nchw_to_nhwc_f16(st, P->arena + off, sp, SW * SH, IC, N, nullptr, nullptr, false, nullptr, 0, nullptr, pre_mul); });
-            B.packed[src] = pk;
-            it            = B.packed.find(src);
-        }
+    // the conv reads an f16 NHWC image from the private arena, so the graph allocator's recycling of the
+    // conv input for the chain output is harmless (no bounce).  A deferred nearest-x2 UPSCALE becomes an index shift.
+    const ggml_tensor* src = xs;
+    bool upscale           = false;
+    auto ui                = B.ups.find(xs);
+    if (ui != B.ups.end()) {
+        src     = ui->second;
+        upscale = true;
+    }
+    const int64_t SW = src->ne[0], SH = src->ne[1];
+    auto it = B.packed.find(src);
+    if (it != B.packed.end() && it->second.nhwc && it->second.mul != pre_mul) {
+        fprintf(stderr, "[ggml-mi355x] plan_conv_chain: operand image of node %d was written with factor %g, the conv wants %g\n", i, it->second.mul, pre_mul);
+        return false;
+    }
+    if (it == B.packed.end() || !it->second.nhwc) {
+        Packed pk{B.alloc((size_t)N * SW * SH * rup64(IC) * 2), rup64(IC), true, pre_mul};
         Planner* P       = B.P;
-        const size_t off = it->second.off;
-        const int64_t CW_ = upscale ? SW * 2 : SW, CH_ = upscale ? SH * 2 : SH;
-        const int64_t opos = ((CW_ + 2 * pd - ks) / st_ + 1) * ((CH_ + 2 * pd - ks) / st_ + 1) * N;
-        if (token_major_out >= 0) {
-            float* tdst          = (float*)gi.node(token_major_out)->data;
-            const int64_t tokens = SW * SH * N;
-            const int64_t lda    = it->second.ld;
-            B.emit([=](hipStream_t st) { launch_gemm16_linear(st, tdst, nullptr, 0, P->arena + off, lda, swz, tokens, IC, OC, OC, ep); });
-            g_stats.fused_conv++;
-            g_stats.fused_proj_tokens++;
-            return true;
-        }
-        if (w3S > 0) {
-            const size_t wsoff = w3S > 1 ? B.alloc((size_t)w3S * opos * OC * 4) : 0;
-            if (w3S > 1) g_stats.split_k_gemms++;
-            const bool gn_on = gn_register(w3S);
-            B.emit_at(emit_node, i, [=](hipStream_t st) {
-                Epilogue e2 = ep;
-                if (emb_arena) e2.chan_add = (const float*)(P->arena + emb_off);
-                if (gn_on) gn_fill(e2, gnp, P->arena, N * OC);
-                launch_conv3w(st, final_dst, P->arena + off, swz, SW, SH, IC, N, OC, e2, w3S > 1 ? (float*)(P->arena + wsoff) : nullptr, w3S);
-            });
-            g_stats.fused_conv++;
-            g_stats.window_convs++;
-            return true;
-        }
-        const Builder::Split sk = B.plan_split(opos, OC, rup64(IC) * ks * ks, true, true);
-        const bool gn_on        = sk.inkernel ? false : gn_register(sk.S);
+        const size_t off = pk.off;
+        const float* sp  = (const float*)src->data;
+        B.emit([=](hipStream_t st) { launch_nchw_to_nhwc_f16(st, P->arena + off, sp, SW * SH, IC, N, nullptr, nullptr, false, nullptr, 0, nullptr, pre_mul); });
+        B.packed[src] = pk;
+        it            = B.packed.find(src);
+    }
+    Planner* P       = B.P;
+    const size_t off = it->second.off;
+    const int64_t CW_ = upscale ? SW * 2 : SW, CH_ = upscale ? SH * 2 : SH;
+    const int64_t opos = ((CW_ + 2 * pd - ks) / st_ + 1) * ((CH_ + 2 * pd - ks) / st_ + 1) * N;
+    if (token_major_out >= 0) {
+        float* tdst          = (float*)gi.node(token_major_out)->data;
+        const int64_t tokens = SW * SH * N;
+        const int64_t lda    = it->second.ld;
+        B.emit([=](hipStream_t st) { launch_gemm16_linear(st, tdst, nullptr, 0, P->arena + off, lda, swz, tokens, IC, OC, OC, ep); });
+        STAT(fused_conv)++;
+        STAT(fused_proj_tokens)++;
+        return true;
+    }
+    if (w3S > 0) {
+        const size_t wsoff = w3S > 1 ? B.alloc((size_t)w3S * opos * OC * 4) : 0;
+        if (w3S > 1) STAT(split_k_gemms)++;
+        const bool gn_on = gn_register(w3S);
         B.emit_at(emit_node, i, [=](hipStream_t st) {
             Epilogue e2 = ep;
             if (emb_arena) e2.chan_add = (const float*)(P->arena + emb_off);
             if (gn_on) gn_fill(e2, gnp, P->arena, N * OC);
-            launch_gemm16_conv(st, final_dst, P->arena + off, swz, SW, SH, IC, N, OC, ks, st_, pd, upscale, e2, sk.ws(P), sk.cnt(P), sk.S);
+            launch_conv3w(st, final_dst, P->arena + off, swz, SW, SH, IC, N, OC, e2, w3S > 1 ? (float*)(P->arena + wsoff) : nullptr, w3S);
         });
-        g_stats.fused_conv++;
+        STAT(fused_conv)++;
+        STAT(window_convs)++;
         return true;
     }
-    return false;  // unreachable: option "gemm16" is always on (the first-generation kernels behind gemm16=0 were removed in round 2)
+    const Builder::Split sk = B.plan_split(opos, OC, rup64(IC) * ks * ks, true, true);
+    const bool gn_on        = sk.inkernel ? false : gn_register(sk.S);
+    B.emit_at(emit_node, i, [=](hipStream_t st) {
+        Epilogue e2 = ep;
+        if (emb_arena) e2.chan_add = (const float*)(P->arena + emb_off);
+        if (gn_on) gn_fill(e2, gnp, P->arena, N * OC);
+        launch_gemm16_conv(st, final_dst, P->arena + off, swz, SW, SH, IC, N, OC, ks, st_, pd, upscale, e2, sk.ws(P), sk.cnt(P), sk.S);
+    });
+    STAT(fused_conv)++;
+    return true;
 }
 
 // SpatialTransformer proj_out (block.hpp:566-572): tokens [C, HW, N] -> CONT(PERMUTE(1,0,2,3)) -> RESHAPE [W,H,C,N] -> 1x1 conv.  The conv's
@@ -2112,7 +2090,7 @@ bool plan_tokens_to_conv(Builder& B, int i, hipStream_t, std::vector<int>& chain
     const ggml_tensor* xr = gi.node(rs);
     const int64_t C = t->ne[0], HW = t->ne[1], N = t->ne[2];
     chain = {i};
-    g_stats.fused_proj_tokens++;
+    STAT(fused_proj_tokens)++;
     // the producing Linear already wrote these rows as an f16 image (plan_linear: residual epilogue -> f16 rows): the conv reads it as it is
     const auto pr = B.packed.find(t);
     if (pr != B.packed.end() && !pr->second.nhwc && pr->second.ld == rup64(C)) {
@@ -2199,8 +2177,8 @@ bool plan_group_norm(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
         chain.push_back(gi.sole(last));
         chain.push_back(tok_cont);
         B.packed[gi.node(tok_cont)] = Packed{off, rup64(C), false};
-        g_stats.fused_norm++;
-        g_stats.fused_proj_tokens++;
+        STAT(fused_norm)++;
+        STAT(fused_proj_tokens)++;
         return true;
     }
     float conv_mul = 1.f;
@@ -2221,13 +2199,13 @@ bool plan_group_norm(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
             if (!have) launch_gn_stats(st, sc, sh, xp, hw, C, N, groups, eps, w, b, nullptr, 0, gsp ? (float*)(P->arena + po) : nullptr);
             launch_nchw_to_nhwc_f16(st, P->arena + off, xp, hw, C, N, sc, sh, silu, nullptr, 0, nullptr, conv_mul);
         });
-        g_stats.kernels_planned++;
+        STAT(kernels_planned)++;
         B.packed[gi.node(last)] = Packed{off, rup64(C), true, conv_mul};
-        g_stats.fused_norm++;
+        STAT(fused_norm)++;
         return true;
     }
     B.emit([=](hipStream_t st) { launch_group_norm(st, dst, xp, hw, C, N, groups, eps, w, b, silu); });
-    if (last != i) g_stats.fused_norm++;
+    if (last != i) STAT(fused_norm)++;
     return true;
 }
 
@@ -2239,7 +2217,7 @@ bool plan_group_norm(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
 bool plan_concat_gn(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
     GInfo& gi            = B.gi;
     const ggml_tensor* n = gi.node(i);
-    if (!g_opt.fusion || !g_opt.gemm16 || !g_opt.fuse_concat_gn || xop(n) != GGML_OP_CONCAT || n->op_params[0] != 2 || !is_f32(n) || !contig(n) || (n->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
+    if (!g_opt.fusion || !g_opt.fuse_concat_gn || xop(n) != GGML_OP_CONCAT || n->op_params[0] != 2 || !is_f32(n) || !contig(n) || (n->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
     const ggml_tensor *a = n->src[0], *b = n->src[1];
     if (!is_f32(a) || !is_f32(b) || !contig(a) || !contig(b) || a->ne[0] != n->ne[0] || a->ne[1] != n->ne[1] || a->ne[3] != n->ne[3] || b->ne[0] != n->ne[0] || b->ne[1] != n->ne[1] ||
         b->ne[3] != n->ne[3] || a->ne[2] + b->ne[2] != n->ne[2])
@@ -2293,8 +2271,8 @@ bool plan_concat_gn(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
     if (raw) B.packed[n] = Packed{roff, rup64(C), true};
     chain = {i, jg, j1, j2};
     if (silu) chain.push_back(j3);
-    g_stats.fused_norm++;
-    g_stats.fused_concat_gn++;
+    STAT(fused_norm)++;
+    STAT(fused_concat_gn)++;
     return true;
 }
 
@@ -2344,7 +2322,7 @@ bool plan_layer_norm(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
     const int64_t xs = (int64_t)x->nb[1] / 4, ds = (int64_t)n->nb[1] / 4;
     // adaLN modulate (mmdit.hpp:368-380): NORM -> {MUL(xn, scale[C,1,N]), ADD(xn, mul)} -> ADD(., shift[C,1,N]) feeding only weight GEMMs:
     // one kernel writes norm * (1 + scale) + shift as the f16 operand image (the four f32 tensors are never materialised)
-    if (g_opt.fusion && g_opt.gemm16 && g_opt.fuse_modulate && !w && !rms && gi.consumers[i].size() == 2 && n->ne[3] == 1 && contig(n) && C % 4 == 0 && xs % 4 == 0 && aligned16(xp)) {
+    if (g_opt.fusion && g_opt.fuse_modulate && !w && !rms && gi.consumers[i].size() == 2 && n->ne[3] == 1 && contig(n) && C % 4 == 0 && xs % 4 == 0 && aligned16(xp)) {
         int jm = -1, ja = -1;
         for (int c : gi.consumers[i]) {
             const ggml_tensor* t = gi.node(c);
@@ -2377,8 +2355,8 @@ bool plan_layer_norm(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
                     launch_layer_norm_f16(st, P->arena + off, xp, C, rows, xs, eps, sc_clob ? (const float*)(P->arena + sc_off) : scalep, shiftp, false, L);
                 });
                 B.packed[gi.node(js)] = Packed{off, rup64(C), false};
-                g_stats.fused_norm++;
-                g_stats.fused_modulate++;
+                STAT(fused_norm)++;
+                STAT(fused_modulate)++;
                 return true;
             }
         }
@@ -2388,18 +2366,18 @@ bool plan_layer_norm(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
         const auto lp = B.ln_pre.find(x);
         if (lp != B.ln_pre.end() && !rms && lp->second.w == w && lp->second.b == b && lp->second.eps == eps && xs == C) {  // written by the split-K reduce of the producing Linear
             B.packed[gi.node(last)] = Packed{lp->second.off, rup64(C), false};
-            g_stats.fused_norm++;
+            STAT(fused_norm)++;
             return true;
         }
         Planner* P       = B.P;
         const size_t off = B.alloc((size_t)rows * rup64(C) * 2);
         B.emit([=](hipStream_t st) { launch_layer_norm_f16(st, P->arena + off, xp, C, rows, xs, eps, w, b, rms); });
         B.packed[gi.node(last)] = Packed{off, rup64(C), false};
-        g_stats.fused_norm++;
+        STAT(fused_norm)++;
         return true;
     }
     B.emit([=](hipStream_t st) { launch_layer_norm(st, dst, xp, C, rows, xs, ds, eps, w, b, rms); });
-    if (last != i) g_stats.fused_norm++;
+    if (last != i) STAT(fused_norm)++;
     return true;
 }
 
@@ -2440,7 +2418,7 @@ bool plan_concat_heads(Builder& B, int i, hipStream_t, std::vector<int>& chain) 
     const int64_t La = a->ne[1], Lb = b->ne[1];
     void* op = gi.node(last)->data;
     B.emit_at(last, i, [=](hipStream_t st) { launch_concat_heads(st, op, f16, ap, bp, d, H, La, Lb, N); });
-    g_stats.fused_concat_heads++;
+    STAT(fused_concat_heads)++;
     return true;
 }
 
@@ -2561,7 +2539,7 @@ bool plan_rope(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
             qoff = B.scratch(0x4a61, (size_t)ggml_abi_nelements(x) * 2);  // Q: an f16 image in arena scratch
             B.q16[gi.node(via)] = qoff;
             f16 = q16 = true;
-            g_stats.fused_q16++;
+            STAT(fused_q16)++;
         }
         const int last = f16 && !q16 ? c2.back() : add;
         const Builder::JPart pa = src.part[0], pb = src.part[1];
@@ -2572,7 +2550,7 @@ bool plan_rope(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
                                pb.w, eps, d, H, La, Lb, N, pep);
         });
         chain = c2;
-        g_stats.fused_rope++;
+        STAT(fused_rope)++;
         return true;
     }
     if (!g_opt.fusion || !g_opt.fuse_rope) return false;
@@ -2598,7 +2576,7 @@ bool plan_rope(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
     } else {
         B.emit_at(add, i, [=](hipStream_t st) { launch_rope_pairs(st, out, xv, pep); });
     }
-    g_stats.fused_rope++;
+    STAT(fused_rope)++;
     return true;
 }
 
@@ -2634,11 +2612,11 @@ bool plan_geglu(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
         const size_t off = B.alloc((size_t)tokens * rup64(inner) * 2);
         B.emit([=](hipStream_t st) { launch_geglu_f16(st, P->arena + off, xp, tokens, inner, xs); });
         B.packed[out] = Packed{off, rup64(inner), false};
-        g_stats.fused_geglu++;
+        STAT(fused_geglu)++;
         return true;
     }
     B.emit([=](hipStream_t st) { launch_geglu(st, dst, xp, tokens, inner, xs); });
-    g_stats.fused_geglu++;
+    STAT(fused_geglu)++;
     return true;
 }
 
@@ -2668,7 +2646,7 @@ bool plan_manual_attention(Builder& B, int i, hipStream_t, std::vector<int>& cha
         // composed from the MFMA GEMM instead of the exact-f32 generic matmul (38 TFLOP/s) — per head: Q rows -> f16 image, K rows -> weight
         // image on the fly, S = scale * Q K^T (f32), row softmax written as the f16 operand image, V^T -> weight image, O = P V.
         const int64_t d = q->ne[0], Lq = q->ne[1], Lk = k->ne[1], dv = vt->ne[1], HN = q->ne[2];
-        if (!g_opt.gemm16 || d % 8 != 0 || Lk % 4 != 0 || k->ne[0] != d || Lq < 64 || Lk < 64 || !aligned16(q->data) || !aligned16(k->data) || !aligned16(vt->data) ||
+        if (d % 8 != 0 || Lk % 4 != 0 || k->ne[0] != d || Lq < 64 || Lk < 64 || !aligned16(q->data) || !aligned16(k->data) || !aligned16(vt->data) ||
             q->nb[1] % 16 != 0 || k->nb[1] % 16 != 0 || vt->nb[1] % 16 != 0 || out->ne[0] != dv || out->ne[1] != Lq)
             return false;
         chain = {i, j1, j2, j3};
@@ -2700,8 +2678,8 @@ bool plan_manual_attention(Builder& B, int i, hipStream_t, std::vector<int>& cha
                 launch_gemm16_linear(st, (float*)(od + h * onb2), nullptr, 0, P->arena + o_p, Lkp, P->arena + o_v, Lq, Lk, dv, onb1 / 4, e2);
             }
         });
-        g_stats.fused_attention++;
-        g_stats.gemm_attention++;
+        STAT(fused_attention)++;
+        STAT(gemm_attention)++;
         return true;
     }
     chain = {i, j1, j2, j3};
@@ -2741,7 +2719,7 @@ bool plan_manual_attention(Builder& B, int i, hipStream_t, std::vector<int>& cha
         launch_flash_attn(st, fo, qv, kv, vv, scale);
         if (kdst != dst) (void)hipMemcpyAsync(dst, kdst, nel * 4, hipMemcpyDeviceToDevice, st);
     });
-    g_stats.fused_attention++;
+    STAT(fused_attention)++;
     return true;
 }
 
@@ -2818,7 +2796,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
             // ... and read by convs AND others (a TAESD block's output: the next block's first conv and its residual ADD): one pass writes the f32 result (in place)
             // and the convs' operand image — the separate pack pass's second read of the tensor disappears
             if (g_opt.fuse_act_pack && (u == UN_RELU || u == UN_SILU) && is_f32(n) && contig(n) && is_f32(n->src[0]) && contig(n->src[0]) && n->ne[3] >= 1 && !gi.consumers[i].empty() &&
-                g_opt.gemm16 && g_opt.mfma_gemm && g_opt.fusion) {
+                g_opt.mfma_gemm && g_opt.fusion) {
                 bool conv_reader = false, scaled = false;
                 for (int c : gi.consumers[i]) {
                     const ggml_tensor* cn = gi.node(c);
@@ -2855,7 +2833,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
             View4 a = view_of(n->src[0]), b = view_of(n->src[1]);
             View4 d = view_of(n);
             B.emit([=](hipStream_t st) { launch_mul_mat_generic(st, (float*)d.data, d.ne, d.nb, a, b); });
-            g_stats.generic_matmul++;
+            STAT(generic_matmul)++;
             return true;
         }
         case GGML_OP_IM2COL: {
@@ -2880,22 +2858,19 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
             const int64_t W = x->ne[0], H = x->ne[1], IC = x->ne[2], N = x->ne[3], OC = ker->ne[3];
             const int ks = (int)ker->ne[0], st_ = p[0], pd = p[2];
             Epilogue ep;
-            if (g_opt.gemm16) {
-                auto it = B.packed.find(x);
-                if (it == B.packed.end() || !it->second.nhwc) {
-                    Packed pk{B.alloc((size_t)N * W * H * rup64(IC) * 2), rup64(IC), true};
-                    Planner* P       = B.P;
-                    const size_t off = pk.off;
-                    B.emit([=](hipStream_t st) { launch_nchw_to_nhwc_f16(st, P->arena + off, xp, W * H, IC, N, nullptr, nullptr, false); });
-                    B.packed[x] = pk;
-                    it          = B.packed.find(x);
-                }
+            auto it = B.packed.find(x);
+            if (it == B.packed.end() || !it->second.nhwc) {
+                Packed pk{B.alloc((size_t)N * W * H * rup64(IC) * 2), rup64(IC), true};
                 Planner* P       = B.P;
-                const size_t off = it->second.off;
-                B.emit([=](hipStream_t st) { launch_gemm16_conv(st, dst, P->arena + off, swz, W, H, IC, N, OC, ks, st_, pd, false, ep); });
-                return true;
+                const size_t off = pk.off;
+                B.emit([=](hipStream_t st) { launch_nchw_to_nhwc_f16(st, P->arena + off, xp, W * H, IC, N, nullptr, nullptr, false); });
+                B.packed[x] = pk;
+                it          = B.packed.find(x);
             }
-            return false;  // unreachable (gemm16 is always on)
+            Planner* P       = B.P;
+            const size_t off = it->second.off;
+            B.emit([=](hipStream_t st) { launch_gemm16_conv(st, dst, P->arena + off, swz, W, H, IC, N, OC, ks, st_, pd, false, ep); });
+            return true;
         }
         case GGML_OP_CONCAT: {
             View4 d = view_of(n), a = view_of(n->src[0]), b = view_of(n->src[1]);
@@ -3023,7 +2998,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                                     pk.runS = Lq;
                                 }
                                 B.packed[fs.view] = pk;
-                                g_stats.flash_slice_images++;
+                                STAT(flash_slice_images)++;
                             }
                             if (ld != C) {  // zero the K padding once per launch
                                 B.emit([=](hipStream_t st) { (void)hipMemsetAsync(P->arena + off, 0, (size_t)Nimg * Lq * ld * 2, st); });
@@ -3051,13 +3026,13 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                             // the graph allocator handed the CONT the block of a Q / K / V operand that dies at the flash node (found at SD3.5-large batch 2, where the
                             // CONT got V's block: every output was NaN): writing the final layout from inside the kernel would overwrite operand rows other
                             // workgroups still read.  The node's own output never aliases its operands: run it plain, VIEW -> CONT as a copy
-                            g_stats.flash_out_alias++;
+                            STAT(flash_out_alias)++;
                             B.emit([=](hipStream_t st) { launch_flash_attn(st, fo, qfix(q), kfix(k), vfix(v), sc); });
-                            g_stats.fused_attention++;
+                            STAT(fused_attention)++;
                             return true;
                         }
                         gi.done[j1] = gi.done[j2] = 1;
-                        g_stats.fused_attention++;
+                        STAT(fused_attention)++;
                         return true;
                     }
                 }
@@ -3081,15 +3056,15 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                     });
                     for (const FlashSlice& fs : slices) {
                         B.packed[fs.view] = Packed{off + (size_t)fs.row0 * (size_t)ld * 2, ld, false};
-                        g_stats.flash_slice_images++;
+                        STAT(flash_slice_images)++;
                     }
                     B.packed[n] = Packed{off, ld, false};  // (a Linear reading all rows through a RESHAPE)
-                    g_stats.fused_attention++;
+                    STAT(fused_attention)++;
                     return true;
                 }
             }
             B.emit([=](hipStream_t st) { launch_flash_attn(st, fo, qfix(q), kfix(k), vfix(v), sc); });
-            g_stats.fused_attention++;
+            STAT(fused_attention)++;
             return true;
         }
         default:
@@ -3110,7 +3085,7 @@ static int sole_through_reshape(const GInfo& gi, int k) {
 // ONE strided read -> GELU -> f16 pass); any other part is packed from its f32 tensor when the walk reaches the CONCAT node.
 void plan_cat_rows16(Builder& B) {
     GInfo& gi = B.gi;
-    if (!g_opt.fusion || !g_opt.gemm16 || !g_opt.fuse_cat_rows16) return;
+    if (!g_opt.fusion || !g_opt.fuse_cat_rows16) return;
     for (int i = 0; i < gi.g->n_nodes; ++i) {
         const ggml_tensor* n = gi.node(i);
         if (xop(n) != GGML_OP_CONCAT || n->op_params[0] != 0 || !is_f32(n) || !contig(n) || n->ne[3] != 1 || (n->flags & GGML_TENSOR_FLAG_OUTPUT)) continue;
@@ -3182,7 +3157,7 @@ static bool concat_heads_forward(const GInfo& gi, int i, int* d_out, int* H_out,
 // (Q as an f16 image when only the flash node reads it).  All-or-nothing per stream: every reader of T has to be inside the pattern.
 void plan_joint_qkv(Builder& B) {
     GInfo& gi = B.gi;
-    if (!g_opt.fusion || !g_opt.gemm16 || !g_opt.fuse_concat_heads || !g_opt.fuse_joint_qkv || B.no_redirect) return;
+    if (!g_opt.fusion || !g_opt.fuse_concat_heads || !g_opt.fuse_joint_qkv || B.no_redirect) return;
     struct VChain {
         int cat = -1, part = -1;
         const float* w = nullptr;
@@ -3344,7 +3319,7 @@ void plan_joint_qkv(Builder& B) {
             jp.w   = st.v[q].w;
             jp.eps = st.v[q].eps;
         }
-        g_stats.fused_joint_qkv++;
+        STAT(fused_joint_qkv)++;
     }
 }
 
@@ -3355,7 +3330,7 @@ void plan_joint_qkv(Builder& B) {
 // projection rows to the flash operand (norm, token concat, rotary, f16 in one go); the mlp part is the strided GELU pass of plan_cat_rows16.
 void plan_flux_qkv(Builder& B) {
     GInfo& gi = B.gi;
-    if (!g_opt.fusion || !g_opt.gemm16 || !g_opt.fuse_rope || !g_opt.fuse_joint_qkv || B.no_redirect) return;
+    if (!g_opt.fusion || !g_opt.fuse_rope || !g_opt.fuse_joint_qkv || B.no_redirect) return;
     struct Use {
         int kind = 0;  // 1 = q / k (rope), 2 = v, 3 = mlp
         int anchor = -1, part = 0, cat = -1;
@@ -3514,70 +3489,13 @@ void plan_flux_qkv(Builder& B) {
             jp.eps = u.eps;
             (u.part == 0 ? rs.La : rs.Lb) = c.L;
         }
-        g_stats.fused_joint_qkv++;
+        STAT(fused_joint_qkv)++;
     }
 }
 
-// Just-in-time weight images one Linear AHEAD, on the side stream (option jit_overlap, round 6).  A resident-quantised Linear (jit_qimages) rebuilds its f16
-// weight image right in front of its GEMM: 152 rebuilds = 2.9 ms of the 93 ms FLUX.1-dev step, bandwidth-bound launches in between matrix-bound ones.
-// The rebuild of Linear k+1 reads static weights only, so it can run WHILE the GEMM of Linear k computes (whose last, partial round leaves CUs idle):
-// at the slot where rebuild k sat (just in front of GEMM k) the plan now waits for rebuild k — issued one slot earlier — and forks rebuild k+1 onto the
-// planner's side stream.  Hazards: rebuild k+1 writes the OTHER buffer of its size class than rebuild k (Builder::jit_seq parity), and the buffer it
-// writes was last read by a GEMM enqueued on the main stream before the fork event; the GEMM that reads it waits for the join event.  Under hipGraph
-// capture the fork / join become graph edges.  The first rebuild of a plan stays on the main stream.
-// MEASURED AND REJECTED as a default (profiles/r07h_ab_jit_overlap.txt): FLUX.1-dev 89.97 -> 92.58 ms per step (+2.9 %), SDXL batch 8 135.57 -> 135.98, results
-// bit-identical.  The rebuild does run concurrently — and takes 11.5 ms of kernel time per step instead of 6.9 while slowing the GEMM it shares the CUs and
-// the HBM / Infinity-Cache path with: the 256 x 256 GEMM tile owns its CU (144 KB of LDS, two waves per SIMD at 256 registers), so the rebuild's
-// workgroups only get CUs the GEMM's last round has left, arriving as a burst of 75 MB of writes exactly when the next GEMM wants its first tiles.
-// The option stays (default 0) so the number can be re-measured.
-void overlap_jit_steps(Planner* P, Plan* plan) {
-    if (!g_opt.jit_overlap || !P->side) return;
-    std::vector<size_t> js;
-    for (size_t i = 0; i < plan->steps.size(); ++i)
-        if (plan->steps[i].tag == 2) js.push_back(i);
-    if (js.size() < 2) return;
-    std::vector<Step> out;
-    out.reserve(plan->steps.size() + js.size());
-    std::vector<hipEvent_t> join(js.size(), nullptr);
-    size_t k = 0;
-    hipStream_t side = P->side;
-    for (size_t i = 0; i < plan->steps.size(); ++i) {
-        if (k < js.size() && i == js[k]) {
-            if (k == 0) {
-                out.push_back(std::move(plan->steps[i]));  // rebuild 0: in place, main stream
-            } else {
-                const hipEvent_t ej = join[k];
-                out.push_back(Step([=](hipStream_t st) { (void)hipStreamWaitEvent(st, ej, 0); }));
-            }
-            if (k + 1 < js.size()) {
-                hipEvent_t ef = nullptr, ej = nullptr;
-                if (hipEventCreateWithFlags(&ef, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ej, hipEventDisableTiming) != hipSuccess) {
-                    // no events: leave the remaining rebuilds where they are
-                    if (ef) (void)hipEventDestroy(ef);
-                    for (size_t r = i + 1; r < plan->steps.size(); ++r) out.push_back(std::move(plan->steps[r]));
-                    plan->steps = std::move(out);
-                    return;
-                }
-                plan->events.push_back(ef);
-                plan->events.push_back(ej);
-                join[k + 1]   = ej;
-                auto rebuild  = plan->steps[js[k + 1]].side_fn;
-                out.push_back(Step([=](hipStream_t st) {
-                    (void)hipEventRecord(ef, st);
-                    (void)hipStreamWaitEvent(side, ef, 0);
-                    rebuild(side);
-                    (void)hipEventRecord(ej, side);
-                }));
-            }
-            ++k;
-            continue;
-        }
-        out.push_back(std::move(plan->steps[i]));
-    }
-    plan->steps = std::move(out);
-    g_stats.jit_overlapped += (int64_t)js.size() - 1;
-}
-
+// (Measured, rejected and removed: the just-in-time weight-image rebuild of Linear k+1 forked onto a side stream while the GEMM of Linear k computes.  Bit-identical and
+// SLOWER, profiles/r07h_ab_jit_overlap.txt: FLUX.1-dev 89.97 -> 92.58 ms per step (+2.9 %) — the 256 x 256 GEMM tile owns its CU, so the rebuild's workgroups only get the
+// CUs the GEMM's last round has left and arrive as a burst of 75 MB of writes exactly when the next GEMM wants its first tiles.)
 bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, bool no_redirect = false) {
     Builder B(P, plan, g);
     B.no_redirect = no_redirect;
@@ -3615,7 +3533,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
             case GGML_OP_MUL_MAT:
                 if (linear_fast_ok(n)) {
                     B.hm_group.clear();
-                    B.hm_grouping = g_opt.fusion && g_opt.gemm16;
+                    B.hm_grouping = g_opt.fusion;
                     plan_linear(B, i, s, chain);
                     if (!B.hm_group.empty()) plan_sibling_group(B, i, s, chain);
                     B.hm_grouping = false;
@@ -3651,7 +3569,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                     B.packed[n] = Packed{ct.off, ct.ld, false};
                     chain       = {i};
                     ok          = true;
-                    g_stats.fused_cat_rows16++;
+                    STAT(fused_cat_rows16)++;
                     break;
                 }
                 const auto jq = B.jqkv.find(i);
@@ -3671,7 +3589,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                             qoff = B.scratch(0x4a60, (size_t)jc.d * jc.H * (La + Lb) * Nimg * 2);
                             B.q16[gi.node(c1)] = qoff;
                             q16 = f16 = true;
-                            g_stats.fused_q16++;
+                            STAT(fused_q16)++;
                         }
                     }
                     const Builder::JPart pa = jc.part[0], pb = jc.part[1];
@@ -3683,7 +3601,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                     });
                     chain = jc.chain;
                     ok    = true;
-                    g_stats.fused_concat_heads++;
+                    STAT(fused_concat_heads)++;
                     break;
                 }
                 ok = plan_concat_heads(B, i, s, chain);
@@ -3732,7 +3650,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                     });
                     chain = {i, jr, jy};
                     ok    = true;
-                    g_stats.fused_concat_heads++;
+                    STAT(fused_concat_heads)++;
                     break;
                 }
                 ok = plan_geglu(B, i, s, chain);
@@ -3800,7 +3718,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                 if (c >= 0 && scale_into_conv(gi, c, &cs)) c = gi.sole(c);  // UPSCALE -> Conv2d scale -> conv (SDXL VAE)
                 else cs = 1.f;
                 if (cs != 1.f) {
-                    if (g_opt.gemm16 && n->op_params[0] == GGML_SCALE_MODE_NEAREST && is_f32(src) && contig(src) && n->ne[0] == 2 * src->ne[0] && n->ne[1] == 2 * src->ne[1] &&
+                    if (n->op_params[0] == GGML_SCALE_MODE_NEAREST && is_f32(src) && contig(src) && n->ne[0] == 2 * src->ne[0] && n->ne[1] == 2 * src->ne[1] &&
                         n->ne[2] == src->ne[2] && n->ne[3] == src->ne[3] && gi.node(c)->src[0]->ne[0] == 3 && gi.node(c)->op_params[0] == 1) {
                         B.ups[n] = src;
                         chain    = {i};
@@ -3808,7 +3726,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                     }
                     break;
                 }
-                if (g_opt.gemm16 && n->op_params[0] == GGML_SCALE_MODE_NEAREST && is_f32(src) && contig(src) && n->ne[0] == 2 * src->ne[0] &&
+                if (n->op_params[0] == GGML_SCALE_MODE_NEAREST && is_f32(src) && contig(src) && n->ne[0] == 2 * src->ne[0] &&
                     n->ne[1] == 2 * src->ne[1] && n->ne[2] == src->ne[2] && n->ne[3] == src->ne[3] && c >= 0 && xop(gi.node(c)) == GGML_OP_IM2COL &&
                     gi.node(c)->src[1] == n && conv_im2col_fast_ok(gi, c) && gi.node(c)->src[0]->ne[0] == 3 && gi.node(c)->op_params[0] == 1) {
                     B.ups[n] = src;
@@ -3836,7 +3754,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
             if (no_redirect) return false;
             fprintf(stderr, "[ggml-mi355x] qkv redirect of node '%s' not taken by its Linear: planning without the joint-qkv pre-passes\n", kv.first->name);
             *plan = Plan{};
-            g_stats.redirect_fallbacks++;
+            STAT(redirect_fallbacks)++;
             return build_plan(P, plan, g, s, true);
         }
     if (B.cnt_used > 0) {  // tile counters of the in-launch split-K combines: zero before the first launch of every run
@@ -3844,16 +3762,15 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
         const size_t coff    = B.cnt_off, cbytes = B.cnt_used * sizeof(int);
         plan->steps.insert(plan->steps.begin(), [=](hipStream_t st) { (void)hipMemsetAsync(PP->arena + coff, 0, cbytes, st); });
     }
-    overlap_jit_steps(P, plan);
     plan->n_nodes      = g->n_nodes;
     plan->arena_needed = B.arena_off;
     if (gi.is_view) {
-        g_stats.view_graphs++;
-        g_stats.view_external_nodes += gi.n_external;
+        STAT(view_graphs)++;
+        STAT(view_external_nodes) += gi.n_external;
     }
-    g_stats.plans_built++;
-    g_stats.nodes_seen += g->n_nodes;
-    g_stats.kernels_planned += (int64_t)plan->steps.size();
+    STAT(plans_built)++;
+    STAT(nodes_seen) += g->n_nodes;
+    STAT(kernels_planned) += (int64_t)plan->steps.size();
     return true;
 }
 
@@ -3864,10 +3781,6 @@ Planner* planner_create(int device) {
     Planner* p = new Planner();
     p->device  = device;
     gemm16_init();
-    if (hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) != hipSuccess) {
-        p->side = nullptr;
-        (void)hipGetLastError();
-    }
     std::lock_guard<std::mutex> lk(g_mu);
     g_planners.push_back(p);
     return p;
@@ -3890,10 +3803,6 @@ void planner_destroy(Planner* p) {
             }
         std::lock_guard<std::mutex> lp(p->mu);
         planner_clear_locked(p);
-    }
-    if (p->side) {
-        (void)hipStreamSynchronize(p->side);
-        (void)hipStreamDestroy(p->side);
     }
     for (auto& kv : p->swz) (void)hipFree(kv.second.swz);
     for (auto& kv : p->jit_buf) (void)hipFree(kv.second);
@@ -3921,7 +3830,7 @@ void planner_forget_range(const void* ptr, size_t size) {
 
 enum ggml_status planner_compute(Planner* p, ggml_cgraph* g, hipStream_t stream) {
     std::lock_guard<std::mutex> lk(p->mu);
-    g_stats.graphs_computed++;
+    STAT(graphs_computed)++;
     const GraphKey gk  = graph_key(g);
     const uint64_t key = gk.key;
     Plan* plan         = nullptr;
@@ -3952,7 +3861,7 @@ enum ggml_status planner_compute(Planner* p, ggml_cgraph* g, hipStream_t stream)
                 (void)hipGraphExecDestroy(victim->second->graph_exec);
             }
             p->plans.erase(victim);
-            g_stats.plans_evicted++;
+            STAT(plans_evicted)++;
         }
     }
     plan->last_use = ++p->tick;
@@ -4001,8 +3910,8 @@ enum ggml_status planner_compute(Planner* p, ggml_cgraph* g, hipStream_t stream)
         }
         if (plan->graph_exec) {
             if (hipGraphLaunch(plan->graph_exec, stream) == hipSuccess) {
-                g_stats.graph_replays++;
-                g_stats.kernels_launched += (int64_t)plan->steps.size();
+                STAT(graph_replays)++;
+                STAT(kernels_launched) += (int64_t)plan->steps.size();
                 if (hipPeekAtLastError() != hipSuccess) {  // a sticky error from an earlier launch surfaces here as it does on the eager path
                     fprintf(stderr, "[ggml-mi355x] error pending after graph replay: %s\n", hipGetErrorString(hipGetLastError()));
                     return GGML_STATUS_FAILED;
@@ -4014,7 +3923,7 @@ enum ggml_status planner_compute(Planner* p, ggml_cgraph* g, hipStream_t stream)
         }
     }
     for (auto& st : plan->steps) st(stream);
-    g_stats.kernels_launched += (int64_t)plan->steps.size();
+    STAT(kernels_launched) += (int64_t)plan->steps.size();
     if (hipPeekAtLastError() != hipSuccess) {
         fprintf(stderr, "[ggml-mi355x] kernel launch error: %s\n", hipGetErrorString(hipGetLastError()));
         return GGML_STATUS_FAILED;
@@ -4116,148 +4025,104 @@ bool planner_supports_op(const ggml_tensor* n) {
 }
 
 void planner_get_stats(ggml_backend_mi355x_stats* o) {
-    o->graphs_computed       = g_stats.graphs_computed;
-    o->plans_built           = g_stats.plans_built;
-    o->nodes_seen            = g_stats.nodes_seen;
-    o->kernels_planned       = g_stats.kernels_planned;
-    o->kernels_launched      = g_stats.kernels_launched;
-    o->fused_conv            = g_stats.fused_conv;
-    o->fused_conv_bounced    = g_stats.fused_conv_bounced;
-    o->fused_linear          = g_stats.fused_linear;
-    o->fused_norm            = g_stats.fused_norm;
-    o->fused_geglu           = g_stats.fused_geglu;
-    o->fused_linear_geglu    = g_stats.fused_linear_geglu;
-    o->split_k_gemms         = g_stats.split_k_gemms;
-    o->head_major_gemms      = g_stats.head_major_gemms;
-    o->fused_modulate        = g_stats.fused_modulate;
-    o->fused_gate            = g_stats.fused_gate;
-    o->fused_gelu            = g_stats.fused_gelu;
-    o->fused_rope            = g_stats.fused_rope;
-    o->fused_concat_heads    = g_stats.fused_concat_heads;
-    o->qgemv_linears         = g_stats.qgemv_linears;
-    o->fused_chan_add        = g_stats.fused_chan_add;
-    o->fused_proj_tokens     = g_stats.fused_proj_tokens;
-    o->gemm_attention        = g_stats.gemm_attention;
-    o->fused_q16             = g_stats.fused_q16;
-    o->split_k_inlaunch      = g_stats.split_k_inlaunch;
-    o->qgemm16_linears       = g_stats.qgemm16_linears;
-    o->fgemv_linears         = g_stats.fgemv_linears;
-    o->fused_presilu         = g_stats.fused_presilu;
-    o->fused_sibling_linears = g_stats.fused_sibling_linears;
-    o->hoisted_kv_linears    = g_stats.hoisted_kv_linears;
-    o->window_convs          = g_stats.window_convs;
-    o->hoisted_emb_linears   = g_stats.hoisted_emb_linears;
-    o->fused_rows16          = g_stats.fused_rows16;
-    o->fused_cat_rows16      = g_stats.fused_cat_rows16;
-    o->fused_joint_qkv       = g_stats.fused_joint_qkv;
-    o->jit_images            = g_stats.jit_images;
-    o->fused_gn_stats        = g_stats.fused_gn_stats;
-    o->fused_ln_reduce       = g_stats.fused_ln_reduce;
-    o->redirect_fallbacks    = g_stats.redirect_fallbacks;
-    o->fused_concat_gn       = g_stats.fused_concat_gn;
-    o->fused_conv_scale      = g_stats.fused_conv_scale;
-    o->view_graphs           = g_stats.view_graphs;
-    o->view_external_nodes   = g_stats.view_external_nodes;
-    o->plans_evicted         = g_stats.plans_evicted;
-    o->hoisted_mod_linears   = g_stats.hoisted_mod_linears;
-    o->jit_overlapped        = g_stats.jit_overlapped;
-    o->qinloop_linears       = g_stats.qinloop_linears;
-    o->flash_out_alias       = g_stats.flash_out_alias;
-    o->flash_slice_images    = g_stats.flash_slice_images;
-    o->fused_attention       = g_stats.fused_attention;
-    o->generic_matmul        = g_stats.generic_matmul;
-    o->swizzled_weight_bytes = g_stats.swizzled_weight_bytes;
-    o->graph_replays         = g_stats.graph_replays;
+    int64_t* out = reinterpret_cast<int64_t*>(o);
+    for (size_t i = 0; i < N_STATS; ++i) out[i] = g_stat_counters[i].load();
 }
 
-void planner_set_option(const char* key, int value) {
-    if (!strcmp(key, "fusion")) g_opt.fusion = value;
-    else if (!strcmp(key, "mfma_gemm")) g_opt.mfma_gemm = value;
-    else if (!strcmp(key, "hip_graph")) g_opt.hip_graph = value;
-    else if (!strcmp(key, "flash_pattern")) g_opt.flash_pattern = value;
+namespace {
+// Every option key, once: the Options member it stores to, or the kernel-side setter of the variable it controls.  A default is written where its
+// variable is defined (the Options initialiser above, the g_* variable in the kernel file).  (ggml_backend_mi355x_set_option handles "pinned_uploads" itself.)
+struct OptionRow {
+    const char* key;
+    std::atomic<int> Options::*member;
+    void (*setter)(int);
+};
+#define OPT(name) {#name, &Options::name, nullptr}
+const OptionRow g_option_table[] = {
+    OPT(fusion),
+    OPT(mfma_gemm),
+    OPT(hip_graph),
+    OPT(flash_pattern),
+    {"gemm16_t320", nullptr, gemm16_set_t320},
+    {"t256p_pad", nullptr, gemm16_set_t256p_pad},
+    {"tail_split", nullptr, gemm16_set_tail_split},
+    {"conv_wmajor", nullptr, gemm16_set_conv_wmajor},
+    {"ln16_rows", nullptr, gemm16_set_ln16_rows},
+    {"t320_linear_max_split", nullptr, gemm16_set_t320_linear_max_split},
+    OPT(qgemv),
+    OPT(fuse_q16),
+    {"streamk", nullptr, gemm16_set_streamk},
+    {"geglu16", nullptr, gemm16_set_geglu16},
+    {"bn64_max_tiles", nullptr, gemm16_set_bn64_max},
+    {"conv3w_prio", nullptr, conv3w_set_prio},
+    {"t256p_min_nt_sk", nullptr, gemm16_set_t256p_min_nt_sk},
+    {"t256p_min_tiles_sk", nullptr, gemm16_set_t256p_min_tiles_sk},
+    {"conv3w", nullptr, conv3w_set},
+    OPT(hoist_emb),
+    OPT(fuse_rows16),
+    OPT(fuse_cat_rows16),
+    OPT(fuse_gn_stats),
+    OPT(fuse_joint_qkv),
+    OPT(fuse_ln_reduce),
+    OPT(jit_qimages),
+    {"qinloop_min_rows", nullptr, gemm16_set_qinloop_min_rows},
+    OPT(fuse_flash_slices),
+    {"gemm16_t192p", nullptr, gemm16_set_t192p},
+    {"conv3w_min_blocks", nullptr, conv3w_set_min_blocks},
+    {"conv3w_min_blocks_deep", nullptr, conv3w_set_min_blocks_deep},
+    {"gemm16_bn64", nullptr, gemm16_set_bn64},
+    OPT(qgemm16),
+    {"qgemv_max_rows", nullptr, qgemv_set_max_rows},
+    OPT(fgemv),
+    OPT(fuse_siblings),
+    OPT(hoist_kv),
+    {"fgemv_max_rows", nullptr, fgemv_set_max_rows},
+    {"qgemm16_max_rows", nullptr, qgemm16_set_max_rows},
+    {"qgemm16_rb", nullptr, qgemm16_set_rb},
+    {"splitk_inkernel", nullptr, gemm16_set_splitk_inkernel},
+    {"splitk_in_target", nullptr, gemm16_set_splitk_in_target},
+    OPT(fuse_chan_add),
+    OPT(fuse_proj_tokens),
+    OPT(fuse_modulate),
+    OPT(fuse_gate),
+    OPT(relax_res_overlap),
+    OPT(fuse_split_gelu),
+    OPT(fuse_concat_gn),
+    OPT(fuse_gn_tokens),
+    OPT(fuse_linear_nchw),
+    OPT(fuse_conv_scale),
+    OPT(fuse_act_pack),  // ReLU / SiLU read only by convs: applied while their operand image is packed
+    OPT(hoist_mod),  // DiT modulation Linears (same one / two rows, raw q8_0 / q4_0 weights) as one grouped weight-streaming launch
+    OPT(plan_cache_cap),  // plans (and captured hipGraphs) kept per backend instance, LRU beyond that (default 512)
+    OPT(ignore_use_counts),  // test hook: a host whose sub-graph views carry no use_counts table
+    OPT(fuse_gelu),
+    OPT(fuse_rope),
+    OPT(fuse_concat_heads),
+    {"gemm16_variant", nullptr, gemm16_set_variant},
+    {"conv_tap_major", nullptr, gemm16_set_tap_major},
+    {"gemm16_tile", nullptr, gemm16_set_tile},
+    {"splitk_mid", nullptr, gemm16_set_splitk_mid},
+    {"splitk_target", nullptr, gemm16_set_splitk_target},
+    {"gn_split_min", nullptr, gemm16_set_gn_split_min},
 #ifdef MI355X_EXPERIMENTS
-    else if (!strcmp(key, "flash_ablate")) flash_attn_set_ablate(value);
-    else if (!strcmp(key, "gemm16_abl")) gemm16_set_abl(value);
+    {"gemm16_abl", nullptr, gemm16_set_abl},
 #endif
-    else if (!strcmp(key, "gemm16_t320")) gemm16_set_t320(value);
-    else if (!strcmp(key, "t256p_pad")) gemm16_set_t256p_pad(value);
-    else if (!strcmp(key, "tail_split")) gemm16_set_tail_split(value);
-    else if (!strcmp(key, "conv_wmajor")) gemm16_set_conv_wmajor(value);
-    else if (!strcmp(key, "ln16_rows")) gemm16_set_ln16_rows(value);
-    else if (!strcmp(key, "t320_linear_max_split")) gemm16_set_t320_linear_max_split(value);
-    else if (!strcmp(key, "qgemv")) g_opt.qgemv = value;
-    else if (!strcmp(key, "fuse_q16")) g_opt.fuse_q16 = value;
-    else if (!strcmp(key, "flash_grid")) flash_attn_set_grid(value);
-    else if (!strcmp(key, "flash_qb2")) flash_attn_set_qb2(value);
-    else if (!strcmp(key, "flash_pp")) flash_attn_set_pp(value);
-    else if (!strcmp(key, "flash_vpf")) flash_attn_set_vpf(value);
-    else if (!strcmp(key, "flash_vtr")) flash_attn_set_vtr(value);
-    else if (!strcmp(key, "flash_ovl")) flash_attn_set_ovl(value);
-    else if (!strcmp(key, "flash_nsel")) flash_attn_set_nsel(value);
-    else if (!strcmp(key, "flash_pk")) flash_attn_set_pk(value);
-    else if (!strcmp(key, "flash_sm")) flash_attn_set_sm(value);
-    else if (!strcmp(key, "flash_qb64")) flash_attn_set_qb64(value);
-    else if (!strcmp(key, "flash_short")) flash_attn_set_short(value);
-    else if (!strcmp(key, "gemm16_swp")) gemm16_set_swp(value);
-    else if (!strcmp(key, "streamk")) gemm16_set_streamk(value);
-    else if (!strcmp(key, "geglu16")) gemm16_set_geglu16(value);
-    else if (!strcmp(key, "bn64_max_tiles")) gemm16_set_bn64_max(value);
-    else if (!strcmp(key, "conv3w_prio")) conv3w_set_prio(value);
-    else if (!strcmp(key, "t256p_min_nt_sk")) gemm16_set_t256p_min_nt_sk(value);
-    else if (!strcmp(key, "t256p_min_tiles_sk")) gemm16_set_t256p_min_tiles_sk(value);
-    else if (!strcmp(key, "flash_pp_min_tiles")) flash_attn_set_pp_min_tiles(value);
-    else if (!strcmp(key, "conv3w")) conv3w_set(value);
-    else if (!strcmp(key, "hoist_emb")) g_opt.hoist_emb = value;
-    else if (!strcmp(key, "fuse_rows16")) g_opt.fuse_rows16 = value;
-    else if (!strcmp(key, "fuse_cat_rows16")) g_opt.fuse_cat_rows16 = value;
-    else if (!strcmp(key, "fuse_gn_stats")) g_opt.fuse_gn_stats = value;
-    else if (!strcmp(key, "fuse_joint_qkv")) g_opt.fuse_joint_qkv = value;
-    else if (!strcmp(key, "fuse_ln_reduce")) g_opt.fuse_ln_reduce = value;
-    else if (!strcmp(key, "jit_qimages")) g_opt.jit_qimages = value;
-    else if (!strcmp(key, "qinloop_min_rows")) gemm16_set_qinloop_min_rows(value);
-    else if (!strcmp(key, "fuse_flash_slices")) g_opt.fuse_flash_slices = value;
-    else if (!strcmp(key, "gemm16_t192p")) gemm16_set_t192p(value);
-    else if (!strcmp(key, "conv3w_min_blocks")) conv3w_set_min_blocks(value);
-    else if (!strcmp(key, "conv3w_min_blocks_deep")) conv3w_set_min_blocks_deep(value);
-    else if (!strcmp(key, "gemm16_bn64")) gemm16_set_bn64(value);
-    else if (!strcmp(key, "qgemm16")) g_opt.qgemm16 = value;
-    else if (!strcmp(key, "qgemv_max_rows")) qgemv_set_max_rows(value);
-    else if (!strcmp(key, "fgemv")) g_opt.fgemv = value;
-    else if (!strcmp(key, "fuse_siblings")) g_opt.fuse_siblings = value;
-    else if (!strcmp(key, "hoist_kv")) g_opt.hoist_kv = value;
-    else if (!strcmp(key, "fgemv_max_rows")) fgemv_set_max_rows(value);
-    else if (!strcmp(key, "qgemm16_max_rows")) qgemm16_set_max_rows(value);
-    else if (!strcmp(key, "qgemm16_pf")) qgemm16_set_pf(value);
-    else if (!strcmp(key, "qgemm16_rb")) qgemm16_set_rb(value);
-    else if (!strcmp(key, "splitk_inkernel")) gemm16_set_splitk_inkernel(value);
-    else if (!strcmp(key, "splitk_in_target")) gemm16_set_splitk_in_target(value);
-    else if (!strcmp(key, "flash_mslot")) flash_attn_set_mslot(value);
-    else if (!strcmp(key, "flash_mslot64")) flash_attn_set_mslot64(value);
-    else if (!strcmp(key, "fuse_chan_add")) g_opt.fuse_chan_add = value;
-    else if (!strcmp(key, "fuse_proj_tokens")) g_opt.fuse_proj_tokens = value;
-    else if (!strcmp(key, "gemm16")) (void)value;  // kept for old scripts: the gemm16 path is the only one (first-generation kernels removed)
-    else if (!strcmp(key, "fuse_modulate")) g_opt.fuse_modulate = value;
-    else if (!strcmp(key, "fuse_gate")) g_opt.fuse_gate = value;
-    else if (!strcmp(key, "relax_res_overlap")) g_opt.relax_res_overlap = value;
-    else if (!strcmp(key, "fuse_split_gelu")) g_opt.fuse_split_gelu = value;
-    else if (!strcmp(key, "fuse_concat_gn")) g_opt.fuse_concat_gn = value;
-    else if (!strcmp(key, "fuse_gn_tokens")) g_opt.fuse_gn_tokens = value;
-    else if (!strcmp(key, "fuse_linear_nchw")) g_opt.fuse_linear_nchw = value;
-    else if (!strcmp(key, "fuse_conv_scale")) g_opt.fuse_conv_scale = value;
-    else if (!strcmp(key, "jit_overlap")) g_opt.jit_overlap = value;  // just-in-time weight images rebuilt one Linear ahead on the side stream (overlap_jit_steps)
-    else if (!strcmp(key, "fuse_act_pack")) g_opt.fuse_act_pack = value;  // ReLU / SiLU read only by convs: applied while their operand image is packed
-    else if (!strcmp(key, "hoist_mod")) g_opt.hoist_mod = value;  // DiT modulation Linears (same one / two rows, raw q8_0 / q4_0 weights) as one grouped weight-streaming launch
-    else if (!strcmp(key, "plan_cache_cap")) g_opt.plan_cache_cap = value;  // plans (and captured hipGraphs) kept per backend instance, LRU beyond that (default 512)
-    else if (!strcmp(key, "ignore_use_counts")) g_opt.ignore_use_counts = value;  // test hook: a host whose sub-graph views carry no use_counts table
-    else if (!strcmp(key, "fuse_gelu")) g_opt.fuse_gelu = value;
-    else if (!strcmp(key, "fuse_rope")) g_opt.fuse_rope = value;
-    else if (!strcmp(key, "fuse_concat_heads")) g_opt.fuse_concat_heads = value;
-    else if (!strcmp(key, "gemm16_variant")) gemm16_set_variant(value);
-    else if (!strcmp(key, "conv_tap_major")) gemm16_set_tap_major(value);
-    else if (!strcmp(key, "gemm16_tile")) gemm16_set_tile(value);
-    else if (!strcmp(key, "splitk_mid")) gemm16_set_splitk_mid(value);
-    else if (!strcmp(key, "splitk_target")) gemm16_set_splitk_target(value);
-    else if (!strcmp(key, "gn_split_min")) gemm16_set_gn_split_min(value);
+};
+#undef OPT
+}  // namespace
+
+void planner_set_option(const char* key, int value) {
+    const OptionRow* row = nullptr;
+    for (const OptionRow& r : g_option_table)
+        if (!strcmp(key, r.key)) row = &r;
+    if (!row) {  // a mistyped or retired key must not pass for a measurement of something
+        fprintf(stderr, "ggml-mi355x: unknown backend option \"%s\" (ignored)\n", key);
+        return;
+    }
+    if (row->member)
+        (g_opt.*row->member) = value;
+    else
+        row->setter(value);
     // options change what a plan contains: drop cached plans
     std::lock_guard<std::mutex> lk(g_mu);
     for (Planner* p : g_planners) {

@@ -59,11 +59,10 @@ namespace mi355x {
 //     chunk of stages kt + 6 / kt + 7 is issued every even iteration behind the A pieces of stage kt + 4.  The LDS-DMA queue retires in order, so ONE counted
 //     wait per iteration — vmcnt(2 A + 2 A + raw pieces) — covers both the A stage and the raw chunk that the next barrier publishes.
 // The result is bitwise the same as the image path's on the same tile (same operand values, same summation order).
-template <int BM, int BN, bool CONV, int BK, int NST, int WR, int WC, int PIPE = 0, bool SWP = false, bool SK = false, int QT = 0>
+template <int BM, int BN, bool CONV, int BK, int NST, int WR, int WC, int PIPE = 0, bool SK = false, int QT = 0>
 __global__ __launch_bounds__(WR * WC * 64, PIPE ? 2 : 2) void k_gemm16(G16Args g) {
-    static_assert(!SWP || !CONV, "SWP: the Linear kernels with the accumulator transposed (g16_common.h, epi_linear_swp)");
-    static_assert(!SK || (PIPE == 1 && !CONV && !SWP), "stream-K is written for the pipelined Linear tiles");
-    static_assert(QT == 0 || ((QT == 8 || QT == 4) && PIPE == 1 && !CONV && !SWP && !SK && BM == 256 && (BN == 256 || BN == 192) && WR * WC == 8), "in-loop dequantisation: pipelined 256 x 256 / 256 x 192 Linear tiles");
+    static_assert(!SK || (PIPE == 1 && !CONV), "stream-K is written for the pipelined Linear tiles");
+    static_assert(QT == 0 || ((QT == 8 || QT == 4) && PIPE == 1 && !CONV && !SK && BM == 256 && (BN == 256 || BN == 192) && WR * WC == 8), "in-loop dequantisation: pipelined 256 x 256 / 256 x 192 Linear tiles");
     constexpr int NW  = WR * WC;
     constexpr int RB  = BM / WR / 32;  // 32-row blocks per wave
     constexpr int CB  = BN / WC / 32;  // 32-col blocks per wave
@@ -361,7 +360,7 @@ __global__ __launch_bounds__(WR * WC * 64, PIPE ? 2 : 2) void k_gemm16(G16Args g
             for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb) {
-                    if (CONV || SWP)
+                    if (CONV)
                         acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[cb], af[rb], acc[rb][cb], 0, 0, 0);  // D[oc][pos]
                     else
                         acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[rb], bf[cb], acc[rb][cb], 0, 0, 0);  // D[row][col]
@@ -392,7 +391,7 @@ __global__ __launch_bounds__(WR * WC * 64, PIPE ? 2 : 2) void k_gemm16(G16Args g
                 asm volatile("" ::"v"(a), "v"(b));
                 return;
             }
-            if (CONV || SWP)
+            if (CONV)
                 acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, acc[rb][cb], 0, 0, 0);  // D[oc][pos]
             else
                 acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[rb][cb], 0, 0, 0);  // D[row][col]
@@ -991,9 +990,7 @@ __global__ __launch_bounds__(WR * WC * 64, PIPE ? 2 : 2) void k_gemm16(G16Args g
     }
 
     // ---- epilogue: one compact variant per workgroup (all conditions are launch- or workgroup-uniform)
-    if constexpr (SWP) {
-        epi_dispatch_linear_swp(acc, g, row0, col0, wr, wc, lane);
-    } else if (!CONV) {
+    if (!CONV) {
         // column-range epilogue (Epilogue::split_col): this tile belongs to the f32 output or to the f16 gelu tensor.  Compiled into the pipelined
         // 256 x 256 tile only (the epilogue code exists twice there): gemm16_split_col_supported tells the planner which launches take that tile
         if (PIPE == 1 && BN == 256 && g.split_col > 0) {
@@ -1155,7 +1152,6 @@ static int g16_pick_tile(int64_t rows, int64_t M, int geglu, bool conv, int spli
 bool gemm16_split_col_supported(int64_t rows, int64_t M, int64_t K);
 int gemm16_geglu_mode(int64_t rows, int64_t M, int64_t K);
 static bool g16_use_bn64(int64_t rows, int64_t M, int mul);
-static int g_g16_swp = 0;  // option "gemm16_swp": 1 = big-token Linear tiles with the accumulator transposed (16-byte epilogue accesses; measured slower: profiles/r05a_ab_gemm16_swp_rejected.txt)
 // ---- stream-K policy (option "streamk", default 0 = off: measured 2.8 % slower, profiles/r05i_*).  A Linear that g16_pick_tile sends to a one-workgroup-per-CU pipelined tile (T320 / T256P) and
 // whose tile count leaves the last round mostly empty runs as ONE round of persistent workgroups over equal (tile, K-tile) unit ranges instead
 // (k_gemm16<..., SK>).  Returns the grid (= CUs), or 0.  rows / M / K of ONE weight; not for grouped (multi) launches, GEGLU, or K-split launches.
@@ -1169,7 +1165,7 @@ static int g16_num_cus() {
     return n;
 }
 static int g16_streamk_grid(int64_t rows, int64_t M, int64_t K, bool geglu, int* tiles_out = nullptr, int* bn_out = nullptr, int* dp_out = nullptr) {
-    if (!g_g16_streamk || g_g16_variant != 3 || !g16_bk32() || g_g16_force_tile >= 0 || g_g16_swp) return 0;
+    if (!g_g16_streamk || g_g16_variant != 3 || !g16_bk32() || g_g16_force_tile >= 0) return 0;
     const int64_t nt = rup64(K, 64) / 32;
     if (!geglu && gemm16_split_k(rows, M, K, false) > 1) return 0;
     const int tile = g16_pick_tile(rows, M, geglu ? gemm16_geglu_mode(rows, M, K) : 0, false, 0, nt, 1);
@@ -1202,17 +1198,6 @@ static int g16_streamk_grid(int64_t rows, int64_t M, int64_t K, bool geglu, int*
     return cus;
 }
 
-void gemm16_set_swp(int v) { g_g16_swp = v; }
-// can this launch's epilogue run on the transposed accumulator?  (f32 +bias +residual | f16 rows (+GELU) | GEGLU; whole 32-column blocks; vector alignment)
-static bool g16_swp_ok(const G16Args& g) {
-    if (!g_g16_swp || g.split_k > 1 || g.multi > 1 || g.hm_d > 0 || g.ep.gate || g.C % 32 != 0) return false;
-    auto al = [](const void* p, int a) { return (((uintptr_t)p) & (uintptr_t)(a - 1)) == 0; };
-    if (g.ep.bias && !al(g.ep.bias, 16)) return false;
-    if (g.geglu_inner > 0) return g.dst16 && !g.dst && !g.ep.residual && g.geglu_inner % 32 == 0 && g.ldd16 % 4 == 0 && al(g.dst16, 8);
-    if (g.dst16) return !g.dst && !g.ep.residual && g.ldd16 % 4 == 0 && al(g.dst16, 8);
-    return g.dst && !g.ep.gelu && g.ldd % 4 == 0 && al(g.dst, 16) && (!g.ep.residual || al(g.ep.residual, 16));
-}
-
 // weight image layout of a GEGLU FF1 of this shape (M = 2 * inner columns): 2 = 16-column interleave (the launch takes a tile with an odd number of
 // column blocks per wave: 256 x 160 / 256 x 320), 1 = 128-column pairing.  Option "geglu16" (1): 0 = always pairing (round-3 behaviour)
 static int g_g16_geglu16 = 1;
@@ -1228,7 +1213,7 @@ static int g_g16_qinloop_min_rows = 513;
 void gemm16_set_qinloop_min_rows(int v) { g_g16_qinloop_min_rows = v; }
 bool gemm16_qinloop_supported(int wtype, int64_t rows, int64_t M, int64_t K, int mul, int split) {
     if (g_g16_qinloop_min_rows <= 0 || rows < g_g16_qinloop_min_rows || (wtype != 8 && wtype != 2)) return false;
-    if (g_g16_variant != 3 || !g16_bk32() || g_g16_swp || g_g16_force_tile >= 0 || g_g16_streamk) return false;
+    if (g_g16_variant != 3 || !g16_bk32() || g_g16_force_tile >= 0 || g_g16_streamk) return false;
     if (K % 64 != 0 || K < 192 || g16_use_bn64(rows, M, mul)) return false;
     const int64_t nt = K / 32;
     if (split > 1 || gemm16_split_k(rows, M, K, false) > 1) return false;  // (K slices: not yet)
@@ -1237,7 +1222,7 @@ bool gemm16_qinloop_supported(int wtype, int64_t rows, int64_t M, int64_t K, int
 }
 // a Linear of this shape runs on the pipelined 256 x 256 tile without K slices: the launches that may carry Epilogue::split_col
 bool gemm16_split_col_supported(int64_t rows, int64_t M, int64_t K) {
-    if (g_g16_variant != 3 || !g16_bk32() || g_g16_swp || M % 256 != 0 || M % 160 == 0 || g16_use_bn64(rows, M, 1)) return false;
+    if (g_g16_variant != 3 || !g16_bk32() || M % 256 != 0 || M % 160 == 0 || g16_use_bn64(rows, M, 1)) return false;
     const int64_t nt = rup64(K, 64) / 32;
     return gemm16_split_k(rows, M, K, false) == 1 && g16_pick_tile(rows, M, false, false, 0, nt, 1) == G16_T256P;
 }
@@ -1277,7 +1262,7 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                 KScope ks_(s, KF_LINEAR, flops, bytes);
                 if (tile == G16_T256P) {
                     g.ncol_tiles = (int)((g.C + 255) / 256);
-                    k_gemm16<256, 256, false, 32, 4, 4, 2, 1, false, true><<<dim3((unsigned)g.sk_grid, 1), 512, 0, s>>>(g);
+                    k_gemm16<256, 256, false, 32, 4, 4, 2, 1, true><<<dim3((unsigned)g.sk_grid, 1), 512, 0, s>>>(g);
                 } else {
                     fprintf(stderr, "ggml-mi355x: stream-K launch planned for a shape that does not take a pipelined tile\n");
                     abort();
@@ -1326,12 +1311,6 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                     return;
                 }
 #endif
-                if constexpr (!CONV_) {
-                    if (g16_swp_ok(g)) {
-                        k_gemm16<256, 320, false, 32, 4, 4, 2, 1, true><<<dim3((unsigned)(rt256 * g.ncol_tiles * mul), ny), 512, 0, s>>>(g);
-                        return;
-                    }
-                }
                 k_gemm16<256, 320, CONV_, 32, 4, 4, 2, 1><<<dim3((unsigned)(rt256 * g.ncol_tiles * mul), ny), 512, 0, s>>>(g);
             } else if (tile == G16_T256P) {
                 g.ncol_tiles = (int)((g.C + 255) / 256);
@@ -1339,9 +1318,9 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                     if (g.qt) {  // raw quantised rows, dequantised in the main loop
                         const dim3 grid((unsigned)(rt256 * g.ncol_tiles * mul), ny);
                         if (g.qt == 8)
-                            k_gemm16<256, 256, false, 32, 4, 4, 2, 1, false, false, 8><<<grid, 512, 0, s>>>(g);
+                            k_gemm16<256, 256, false, 32, 4, 4, 2, 1, false, 8><<<grid, 512, 0, s>>>(g);
                         else
-                            k_gemm16<256, 256, false, 32, 4, 4, 2, 1, false, false, 4><<<grid, 512, 0, s>>>(g);
+                            k_gemm16<256, 256, false, 32, 4, 4, 2, 1, false, 4><<<grid, 512, 0, s>>>(g);
                         return;
                     }
                     if (g.C % 256 != 0) g.wblk_lim = (int)(rup64(g.C, 128) / 32);
@@ -1363,10 +1342,6 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                         return;
                     }
 #endif
-                    if (g16_swp_ok(g)) {
-                        k_gemm16<256, 256, false, 32, 4, 4, 2, 1, true><<<dim3((unsigned)(rt256 * g.ncol_tiles * mul), ny), 512, 0, s>>>(g);
-                        return;
-                    }
                 }
                 k_gemm16<256, 256, CONV_, 32, 4, 4, 2, 1><<<dim3((unsigned)(rt256 * g.ncol_tiles * mul), ny), 512, 0, s>>>(g);
             } else if (tile == G16_T192P) {
@@ -1375,9 +1350,9 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                 if constexpr (!CONV_) {
                     const dim3 grid((unsigned)(rt256 * g.ncol_tiles * mul), ny);
                     if (g.qt == 8)
-                        k_gemm16<256, 192, false, 32, 4, 4, 2, 1, false, false, 8><<<grid, 512, 0, s>>>(g);
+                        k_gemm16<256, 192, false, 32, 4, 4, 2, 1, false, 8><<<grid, 512, 0, s>>>(g);
                     else if (g.qt)
-                        k_gemm16<256, 192, false, 32, 4, 4, 2, 1, false, false, 4><<<grid, 512, 0, s>>>(g);
+                        k_gemm16<256, 192, false, 32, 4, 4, 2, 1, false, 4><<<grid, 512, 0, s>>>(g);
                     else
                         k_gemm16<256, 192, false, 32, 4, 4, 2, 1><<<grid, 512, 0, s>>>(g);
                 }
@@ -1386,12 +1361,6 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                 k_gemm16<256, 160, CONV_, 32, 3, 4, 1><<<dim3((unsigned)(rt256 * g.ncol_tiles * mul), ny), 256, 0, s>>>(g);
             } else if (tile == G16_T160N) {
                 g.ncol_tiles = (int)(g.C / 160);
-                if constexpr (!CONV_) {
-                    if (g16_swp_ok(g) && g.geglu_inner == 0) {  // 160-column tiles: five column blocks per wave, no GEGLU pairing
-                        k_gemm16<256, 160, false, 32, 3, 8, 1, 0, true><<<dim3((unsigned)(rt256 * g.ncol_tiles * mul), ny), 512, 0, s>>>(g);
-                        return;
-                    }
-                }
                 k_gemm16<256, 160, CONV_, 32, 3, 8, 1><<<dim3((unsigned)(rt256 * g.ncol_tiles * mul), ny), 512, 0, s>>>(g);
             } else if (tile == G16_T256W) {
                 k_gemm16<256, 128, CONV_, 32, 3, 2, 2><<<dim3((unsigned)(rt256 * g.ncol_tiles * mul), ny), 256, 0, s>>>(g);

@@ -232,7 +232,6 @@ int qgemm16_split_k(int64_t rows, int64_t K, int64_t M);
 bool wswz_q_supported(int wtype, int64_t K);
 void launch_wswz_q(hipStream_t s, void* dst, const void* wraw, int wtype, int64_t K, int64_t R);
 void qgemm16_set_max_rows(int v);
-void qgemm16_set_pf(int v);  // segments of global loads in flight in k_qgemm16 (1 / 2)
 void launch_qgemm16(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const void* a16, int64_t lda, int64_t rows, const void* wraw, int wtype, int64_t K,
                     int64_t M, const Epilogue& ep, float* splitk_ws = nullptr, int splitk_S = 1);
 // dst[i] = sum_s ws[s * n + i] + bias[i % C] + residual[i] (gemm16.hip's k_splitk_reduce on a row-major [rows][C] output)
@@ -252,28 +251,10 @@ struct FlashOut {
     void* dst16      = nullptr;
     int64_t ld16     = 0;
 };
-#ifdef MI355X_EXPERIMENTS
-void flash_attn_set_ablate(int v);
-#endif
-void flash_attn_set_grid(int v);   // option "flash_grid"
-void flash_attn_set_qb2(int v);    // option "flash_qb2": 1 = two query blocks per wave for the d = 40 max-slot launches (default), 2 = for every d <= 48 launch, 0 = off
-void flash_attn_set_pp(int v);     // option "flash_pp": the 8-wave ping-pong kernel (default 0: measured slower; 1 = d in (64, 96], 2 = wherever legal)
-void flash_attn_set_vpf(int v);    // option "flash_vpf": bit mask of head-dim classes (1: d <= 48, 2: <= 64, 4: <= 96, 8: <= 128, 16: above) whose kernel issues its LDS fragment reads ahead of the MFMAs
-void flash_attn_set_vtr(int v);    // option "flash_vtr": same bits: row-major V tiles read with the transposing LDS read (ds_read_b64_tr_b16)
-void flash_attn_set_ovl(int v);    // option "flash_ovl": 1 = overlapped issue order in the two-block d = 40 kernel (default), 2 = also the other d <= 48 two-block launches, 0 = phase by phase
-void flash_attn_set_nsel(int v);   // option "flash_nsel": 1 = select-free K / V staging in the d = 40 two-block, d = 64 and d = 128 kernels (default since round 4: bit-identical, -3..6 % per launch)
-void flash_attn_set_sm(int v);     // option "flash_sm": softmax arithmetic variant of the d = 64 / d = 128 one-block kernels (2 = accumulator-initialised max, 4 = v_dot2 row sums, 6 = both)
-void flash_attn_set_pk(int v);     // option "flash_pk": 1 = running-max subtraction and row sums as packed f32 operations (two scores per instruction; measured slower); 0 = scalar (default)
-void flash_attn_set_qb64(int v);   // option "flash_qb64": N > 0 = two query blocks per wave at d = 64 for launches with at least N workgroups of 256 queries; 0 = off
-void flash_attn_set_short(int v);  // option "flash_short": k_flash_short (K / V register-resident) for 64 < Lk <= 96, d <= 64: 0 = off, 1 = on, 2 = with the next block's Q prefetched (default)
 void gemm16_set_t256p_min_nt_sk(int v);     // option "t256p_min_nt_sk" (64): least 32-wide K stages of a Linear that stream-K could run for it to take the 256 x 256 tile
 void gemm16_set_t256p_min_tiles_sk(int v);  // option "t256p_min_tiles_sk" (192): least tiles, same condition
 bool gemm16_split_col_supported(int64_t rows, int64_t M, int64_t K);  // a Linear of this shape may carry Epilogue::split_col (it takes the pipelined 256 x 256 tile, no K slices)
 void gemm16_set_streamk(int v);    // option "streamk" (0; 1 = launches of two rounds or more, 2 = every candidate): Linears whose tile count leaves the last round of a one-workgroup-per-CU tile mostly empty run as one round of persistent workgroups over equal (tile, K-tile) ranges
-void gemm16_set_swp(int v);        // option "gemm16_swp": 1 = transposed-accumulator epilogue for the big-token Linear tiles (measured round 4: correct, 1 % slower per step; default 0)
-void flash_attn_set_pp_min_tiles(int v);  // option "flash_pp_min_tiles"
-void flash_attn_set_mslot64(int v);  // option "flash_mslot64" (0): d = 64 launches with the running max in a padded k-slot (1) and the row sums in a ones column of V (2)
-void flash_attn_set_mslot(int v);  // option "flash_mslot"
 void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale);
 
 

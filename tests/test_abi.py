@@ -26,6 +26,20 @@ def test_backend_plugin_exports(sd):
     assert not missing, missing
 
 
+def test_backend_stats_mirror_matches_the_public_struct(sd):
+    """sdcpp_amd._BACKEND_STAT_FIELDS mirrors struct ggml_backend_mi355x_stats field by field, in order: get_stats writes the C struct into the
+    ctypes one, so a missing name would let it write past the end and a swapped pair would report one counter under the other's name."""
+    txt = (ROOT / "include" / "ggml-mi355x.h").read_text()
+    body = re.search(r"struct\s+ggml_backend_mi355x_stats\s*\{(.*?)\n\};", txt, re.S)
+    assert body, "struct ggml_backend_mi355x_stats not found in include/ggml-mi355x.h"
+    decls = [d.strip() for d in re.sub(r"/\*.*?\*/", "", body.group(1), flags=re.S).split(";") if d.strip()]
+    assert all(re.fullmatch(r"int64_t\s+\w+", d) for d in decls), [d for d in decls if not re.fullmatch(r"int64_t\s+\w+", d)]
+    fields = [d.split()[1] for d in decls]
+    assert len(fields) > 40 and len(set(fields)) == len(fields)
+    assert fields == list(sd._BACKEND_STAT_FIELDS)
+    assert C.sizeof(sd.BackendStats) == 8 * len(fields)
+
+
 def test_backend_plugin_loads_without_gpu_and_reports_no_device(sd):
     lib = C.CDLL(str(sd.BACKEND_LIB))
     lib.ggml_backend_score.restype = C.c_int
