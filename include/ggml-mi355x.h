@@ -100,6 +100,10 @@ struct ggml_backend_mi355x_stats {
     int64_t qinloop_linears;     /* q8_0 / q4_0 Linears above k_qgemm16's row range planned on the pipelined 256 x 256 tile with the raw GGUF blocks dequantised INSIDE the main loop (k_gemm16<..., QT>): no f16 weight image, resident or rebuilt */
     int64_t flash_out_alias;     /* FLASH_ATTN_EXT -> VIEW -> CONT chains NOT written by the flash kernel itself because the graph allocator gave the CONT the block of a Q / K / V operand (the node runs plain, the CONT as a copy) */
     int64_t flash_slice_images;  /* token-slice views of an attention output registered on the flash kernel's f16 operand image (their Linears read runs of rows out of it: no f32 tensor, no pack pass) */
+    int64_t flash_short_launches;   /* launch_flash_attn calls that took k_flash_short (65 .. 96 keys held in registers, one-pass softmax) */
+    int64_t flash_qb2_launches;     /* ... that took the two-query-block max-slot kernel k_flash_attn<48, 2, FAST, MSLOT, QB = 2, NSEL> */
+    int64_t flash_mslot_launches;   /* ... that took the one-block max-slot kernel (d = 40, f16 K / V) */
+    int64_t flash_generic_launches; /* ... that took a !FAST instantiation (generic staging: f32 or strided K / V, d % 8 != 0) */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and

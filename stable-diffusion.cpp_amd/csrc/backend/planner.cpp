@@ -4027,6 +4027,11 @@ bool planner_supports_op(const ggml_tensor* n) {
 void planner_get_stats(ggml_backend_mi355x_stats* o) {
     int64_t* out = reinterpret_cast<int64_t*>(o);
     for (size_t i = 0; i < N_STATS; ++i) out[i] = g_stat_counters[i].load();
+    // counted where launch_flash_attn chooses its kernel (per launch call, not per plan)
+    o->flash_short_launches   = flash_attn_variant_launches(FLASH_VAR_SHORT);
+    o->flash_qb2_launches     = flash_attn_variant_launches(FLASH_VAR_QB2);
+    o->flash_mslot_launches   = flash_attn_variant_launches(FLASH_VAR_MSLOT);
+    o->flash_generic_launches = flash_attn_variant_launches(FLASH_VAR_GENERIC);
 }
 
 namespace {

@@ -16,6 +16,7 @@
 // Staging is split (cdna_hip_programming.md T14): the 16-byte global loads of tile t+1 are issued into registers
 // BEFORE the MFMAs of tile t and written to LDS after the next barrier, so HBM/L2 latency hides under compute.
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -455,7 +456,7 @@ __global__ __launch_bounds__(256, DKP <= 64 ? (FAST ? 2 : FA_OCC_SMALL) : (DKP <
                     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
                     const float m_new = fminf((float)(_Float16)fminf(m_run[b] + (kt == 0 ? tmax : fmaxf(tmax, 0.f)), 65504.f), 65504.f);
                     const float delta = m_new - m_run[b];
-                    const float alpha = __builtin_amdgcn_exp2f(-delta);
+                    const float alpha = kt == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta);  // first tile: see the one-block path
                     m_run[b]          = m_new;
 #pragma unroll
                     for (int kb = 0; kb < 2; ++kb)
@@ -620,7 +621,9 @@ __global__ __launch_bounds__(256, DKP <= 64 ? (FAST ? 2 : FA_OCC_SMALL) : (DKP <
                         // score of the row into NaN; any consistent offset is a valid softmax shift
                         const float m_new = fminf((float)(_Float16)fminf(m_run[b] + (kt == 0 ? tmax : fmaxf(tmax, 0.f)), 65504.f), 65504.f);
                         const float delta = m_new - m_run[b];
-                        alpha             = __builtin_amdgcn_exp2f(-delta);
+                        // first tile: the accumulators are still zero and delta is the row's whole first max, of either sign: below -128 log2 units
+                        // 2^-delta is inf, and 0 * inf turned the row into NaN.  Later moves only go up (delta >= 0, alpha <= 1)
+                        alpha             = kt == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta);
                         m_run[b]          = m_new;
 #pragma unroll
                         for (int kb = 0; kb < 2; ++kb)
@@ -953,6 +956,11 @@ __global__ __launch_bounds__(256, 2) void k_flash_short(FAArgs g) {
 
 bool flash_attn_supported(int64_t D, int64_t DV) { return D == DV && D >= 8 && D <= 160; }
 
+namespace {
+std::atomic<int64_t> g_variant_launches[FLASH_VAR_COUNT];
+}
+int64_t flash_attn_variant_launches(int variant) { return variant >= 0 && variant < FLASH_VAR_COUNT ? g_variant_launches[variant].load() : 0; }
+
 void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale) {
     KScope ks_(s, KF_FLASH, 4.0 * (double)q.ne[1] * (double)k.ne[1] * (double)q.ne[2] * (double)q.ne[0], 0.0);  // 4 * Lq * Lk * (H*N) * d
     FAArgs g;
@@ -999,6 +1007,7 @@ void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const
         const int64_t nblk = (int64_t)((g.Lq + 31) / 32) * q.ne[2];
         g.qi  = (int)std::max<int64_t>(1, std::min<int64_t>(8, nblk / 4096));
         dim3 gs((unsigned)((g.Lq + 128 * g.qi - 1) / (128 * g.qi)), (unsigned)q.ne[2]);
+        g_variant_launches[FLASH_VAR_SHORT]++;
 #define FS_CASE(DKP_)                                                     \
     do {                                                                  \
         if (g.q_f16 && g.dst16)                                           \
@@ -1023,6 +1032,12 @@ void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const
     const int NT        = (g.Lk + FA_KT - 1) / FA_KT;
     const bool qb2      = fast && D == 40 && NT >= 4 && g.Lq >= 192 && wg256 >= 512;
     const int QWG       = qb2 ? 256 : 128;
+    if (qb2)
+        g_variant_launches[FLASH_VAR_QB2]++;
+    else if (!fast)
+        g_variant_launches[FLASH_VAR_GENERIC]++;
+    else if (D == 40)
+        g_variant_launches[FLASH_VAR_MSLOT]++;
     dim3 grid((unsigned)((g.Lq + QWG - 1) / QWG), (unsigned)q.ne[2]);
     if (out.H > 0 && q.ne[2] % out.H == 0) {  // XCD-grouped 1-D grid (see the kernel)
         g.grp   = out.H;

@@ -256,6 +256,9 @@ void gemm16_set_t256p_min_tiles_sk(int v);  // option "t256p_min_tiles_sk" (192)
 bool gemm16_split_col_supported(int64_t rows, int64_t M, int64_t K);  // a Linear of this shape may carry Epilogue::split_col (it takes the pipelined 256 x 256 tile, no K slices)
 void gemm16_set_streamk(int v);    // option "streamk" (0; 1 = launches of two rounds or more, 2 = every candidate): Linears whose tile count leaves the last round of a one-workgroup-per-CU tile mostly empty run as one round of persistent workgroups over equal (tile, K-tile) ranges
 void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale);
+// which instantiation launch_flash_attn chose, counted per call (statistics flash_*_launches; the other FAST tile kernels are not counted)
+enum FlashVariant { FLASH_VAR_SHORT = 0, FLASH_VAR_QB2, FLASH_VAR_MSLOT, FLASH_VAR_GENERIC, FLASH_VAR_COUNT };
+int64_t flash_attn_variant_launches(int variant);
 
 
 // calib.hip: what this box delivers (bench.py roofline.measured_peaks)

@@ -616,3 +616,70 @@ def test_weight_major_order_is_a_bijection_and_keeps_a_weight_chunk_on_one_xcd(n
             bid, ks = wg_order(x, y, gx, ncol, 0)
             xcds.setdefault((bid % ncol, ks), set()).add((y * gx + x) % 8)
     assert max(len(v) for v in xcds.values()) > 1 or nrow * ncol <= 8
+
+
+# ---- attention scores that move the deferred running max (tests/attn_scores.py): what the GPU cases of tests/test_gpu_attention_scores.py
+# do to k_flash_attn's max rule, proven on the NumPy model.  Conditions on the INPUTS: they say nothing about a kernel.
+import attn_scores as AS
+
+_TILE_CASES = ([("node",) + c for c in AS.FLASH_NODE_CASES] + [("manual",) + c for c in AS.MANUAL_CASES])
+
+
+def _model_heads(HN):
+    return min(HN, 4)   # the families are the same in every head: the conditions are checked on the first few
+
+
+@pytest.mark.parametrize("kind", AS.KINDS)
+@pytest.mark.parametrize("path,d,Lq,Lk,HN", _TILE_CASES)
+def test_attention_score_families_move_the_deferred_max(path, d, Lq, Lk, HN, kind):
+    """ramp* / spike* cross the bar of FA_THR = 8 log2 units after tile 0 at least twice, at least once with a split vote (some rows of a 32-query
+    block over the bar, others not); descend / offset_* never do; P stays finite and below 2^8 times the f16 rounding of the max slot.
+    (ramp3 over Lk = 130 cannot cross — attn_scores.ramp_can_move — and is required to make no move.)"""
+    rng = np.random.default_rng(20 + d)
+    q, k, v = AS.make_heads(kind, Lq, Lk, d, _model_heads(HN), rng)
+    k, v = AS.f16r(k), AS.f16r(v)
+    scale = 1.0 / np.sqrt(d)
+    out, moves, split, pmax = AS.deferred_model(q, k, v, scale, mslot=AS.uses_max_slot(d, Lk, fast=path == "node"))
+    assert np.isfinite(out).all() and np.isfinite(pmax)
+    assert pmax <= 256 * 1.07
+    if kind in AS.MOVING and AS.ramp_can_move(kind, Lk):
+        assert moves >= 2 and split >= 1, (moves, split)
+    else:
+        assert moves == 0 and split == 0, (moves, split)
+    assert AS.rel_l2(out, AS.exact(q, k, v, scale)) < 5e-4    # the tiled model itself: P in f16 only (2^-11 per term)
+
+
+@pytest.mark.parametrize("path,d,Lq,Lk,HN", _TILE_CASES)
+def test_standard_normal_scores_never_move_the_deferred_max(path, d, Lq, Lk, HN):
+    """the statement the families exist for: standard-normal q, k scaled by 1/sqrt(d) make ZERO moves after tile 0"""
+    rng = np.random.default_rng(1234)
+    q, k, v = AS.make_heads("randn", Lq, Lk, d, _model_heads(HN), rng)
+    _, moves, _, pmax = AS.deferred_model(q, AS.f16r(k), AS.f16r(v), 1.0 / np.sqrt(d), mslot=AS.uses_max_slot(d, Lk, fast=path == "node"))
+    assert moves == 0 and pmax <= 256
+
+
+@pytest.mark.parametrize("kind", AS.KINDS)
+@pytest.mark.parametrize("d,Lq,Lk,HN", AS.SHORT_CASES + AS.GEMM_CASES)
+def test_attention_score_families_one_pass_models(d, Lq, Lk, HN, kind):
+    """k_flash_short / the d > 160 composition take the true row max: no move to prove.  The families still leave the standard-normal regime (scores
+    spread over more than FA_THR log2 units in ramp12 and the spikes; ramp3 rises 3 per 64 keys and cannot over <= 132) and the operand-rounding models stay finite and near the exact softmax."""
+    rng = np.random.default_rng(20 + d)
+    q, k, v = AS.make_heads(kind, Lq, Lk, d, HN, rng)
+    k, v = AS.f16r(k), AS.f16r(v)
+    scale = 1.0 / np.sqrt(d)
+    out = (AS.onepass_model if d <= 64 else AS.gemm_model)(q, k, v, scale)
+    assert np.isfinite(out).all()
+    assert AS.rel_l2(out, AS.exact(q, k, v, scale)) < 1e-2
+    if kind in AS.MOVING and kind != "ramp3":
+        s = np.einsum("hqd,hkd->hqk", q.astype(np.float64), k) * scale * AS.LOG2E
+        assert (s.max(-1) - np.median(s, -1)).max() > 8.0
+
+
+def test_spike_rows_need_their_own_alpha():
+    """spike_last: the gain of the last key over the running max differs per query row (0 for i % 7 == 0, no move, upward from there)"""
+    d, Lq, Lk = 40, 96, 333
+    q, k, v = AS.make("spike_last", Lq, Lk, d, np.random.default_rng(3))
+    s = (q.astype(np.float64) @ AS.f16r(k).T) / np.sqrt(d) * AS.LOG2E
+    gain = s[:, -1] - s[:, :320].max(-1)
+    assert (gain[np.arange(Lq) % 7 == 0] < 8).all() and (gain[np.arange(Lq) % 7 >= 3] > 8).all()
+    assert len(np.unique(np.round(gain[:32], 3))) > 16
