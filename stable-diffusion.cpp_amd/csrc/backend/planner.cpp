@@ -168,7 +168,7 @@ std::atomic<int64_t> g_stat_counters[N_STATS];
 #define STAT(field) g_stat_counters[offsetof(ggml_backend_mi355x_stats, field) / sizeof(int64_t)]
 
 struct Options {
-    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1};
+    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1}, fuse_gn_epilogue{1};
 } g_opt;
 
 using Step = std::function<void(hipStream_t)>;  // one launch (or a few) of a plan
@@ -483,6 +483,21 @@ struct Packed {
     int64_t runL = 0, runS = 0;
 };
 
+// node j's result is read by a GROUP_NORM not yet planned, directly or through a channel CONCAT (a UNet skip connection): the consumers that can take
+// their statistics from a conv epilogue's GnRec side band (plan_group_norm, plan_concat_gn)
+static bool feeds_group_norm(const GInfo& gi, int j) {
+    const ggml_tensor* res = gi.node(j);
+    for (int k : gi.consumers[j]) {
+        const ggml_tensor* c = gi.node(k);
+        if (gi.done[k]) continue;
+        if (xop(c) == GGML_OP_GROUP_NORM && c->src[0] == res) return true;
+        if (xop(c) == GGML_OP_CONCAT && c->op_params[0] == 2 && (c->src[0] == res || c->src[1] == res))
+            for (int k2 : gi.consumers[k])
+                if (xop(gi.node(k2)) == GGML_OP_GROUP_NORM && gi.node(k2)->src[0] == c) return true;
+    }
+    return false;
+}
+
 struct Builder {
     Planner* P;
     Plan* plan;
@@ -533,6 +548,10 @@ struct Builder {
         float eps;
     };
     std::unordered_map<const ggml_tensor*, GnPre> gn_pre;
+    // unsplit conv output -> arena offset of the GroupNorm side band its epilogue filled (GnRec, kernels.h; plan_conv_chain look-ahead).  plan_group_norm and
+    // plan_concat_gn (both sources listed) run k_gn_finalize over the records instead of a statistics pass over the tensor.  The arena is never recycled inside
+    // a plan, so the records of a skip tensor are still there when its CONCAT is planned many nodes later
+    std::unordered_map<const ggml_tensor*, size_t> gn_rec;
     // split-K Linear output -> f16 operand image of the LayerNorm that reads it, already written by the slab reduce (plan_linear look-ahead;
     // plan_layer_norm skips its launch when weight / bias / eps agree)
     struct LnPre {
@@ -1225,9 +1244,15 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         const int64_t HWt = nchw_HW, Nimg = nchw_N;
         const float* resp       = nchw_res;
         const Builder::Split sk = B.plan_split(tokens, M, rup64(K), true, true);
+        // a GroupNorm (or a skip CONCAT a GroupNorm reads) on the NCHW sum: the unsplit launch fills the side band (cf. plan_conv_chain)
+        const bool rec_want = g_opt.fuse_gn_epilogue && feeds_group_norm(gi, nchw_add);
+        const bool rec_on  = sk.S <= 1 && rec_want && gemm16_conv_gn_rec_supported(HWt, Nimg, M, rup64(K), 1);
+        const size_t rec_o = rec_on ? B.alloc((size_t)Nimg * (HWt / GN_REC_CHUNK) * M * sizeof(GnRec)) : 0;
+        if (rec_on) B.gn_rec[gi.node(nchw_add)] = rec_o;
         B.emit_at(emit_node, i, [=](hipStream_t st) {
             Epilogue e2 = ep;
             e2.residual = resp;
+            if (rec_on) e2.gn_rec = (GnRec*)(P->arena + rec_o);
             launch_gemm16_conv(st, ndst, P->arena + off, swz, HWt, 1, K, Nimg, M, 1, 1, 0, false, e2, sk.ws(P), sk.cnt(P), sk.S);
         });
         STAT(fused_linear)++;
@@ -1993,6 +2018,9 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
             gnp = Builder::GnPre{0, (const float*)gi.node(j1)->src[1]->data, (const float*)gi.node(j2)->src[1]->data, g->op_params[0], ggml_abi_op_param_f32(g, 1)};
         }
     }
+    // the same look-ahead for the UNSPLIT window conv: a GroupNorm chain on the result, or a channel CONCAT of it that a GroupNorm reads (the skip connections
+    // plan_concat_gn takes) — its epilogue fills the per-channel side band (Epilogue::gn_rec) and the GroupNorm's statistics pass becomes k_gn_finalize
+    const bool rec_want = g_opt.fuse_gn_epilogue && g_opt.fusion && token_major_out < 0 && feeds_group_norm(gi, last);
     auto gn_register = [&](int S) -> bool {  // called once the split factor is known
         if (S <= 1 || !gnp.groups) return false;
         // k_splitk_reduce_gn moves 16 bytes per lane: decided HERE, with the addresses the launch will see, so that plan_group_norm never skips a
@@ -2057,10 +2085,16 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
         const size_t wsoff = w3S > 1 ? B.alloc((size_t)w3S * opos * OC * 4) : 0;
         if (w3S > 1) STAT(split_k_gemms)++;
         const bool gn_on = gn_register(w3S);
+        // side band: the conditions launch_conv3w checks (unsplit, whole GN_REC_CHUNK tiles per image)
+        const int64_t ohw  = opos / N;
+        const bool rec_on  = w3S == 1 && rec_want && conv3w_gn_rec_supported(ohw, OC, N);
+        const size_t rec_o = rec_on ? B.alloc((size_t)N * (ohw / GN_REC_CHUNK) * OC * sizeof(GnRec)) : 0;
+        if (rec_on) B.gn_rec[gi.node(last)] = rec_o;
         B.emit_at(emit_node, i, [=](hipStream_t st) {
             Epilogue e2 = ep;
             if (emb_arena) e2.chan_add = (const float*)(P->arena + emb_off);
             if (gn_on) gn_fill(e2, gnp, P->arena, N * OC);
+            if (rec_on) e2.gn_rec = (GnRec*)(P->arena + rec_o);
             launch_conv3w(st, final_dst, P->arena + off, swz, SW, SH, IC, N, OC, e2, w3S > 1 ? (float*)(P->arena + wsoff) : nullptr, w3S);
         });
         STAT(fused_conv)++;
@@ -2069,10 +2103,16 @@ bool plan_conv_chain(Builder& B, int i, hipStream_t s, std::vector<int>& chain) 
     }
     const Builder::Split sk = B.plan_split(opos, OC, rup64(IC) * ks * ks, true, true);
     const bool gn_on        = sk.inkernel ? false : gn_register(sk.S);
+    // side band from the unsplit 256-row tiles (the 1x1 proj_out / skip convs, the stride-2 down-sample): the conditions g16_launch checks
+    const int64_t ohw  = opos / N;
+    const bool rec_on  = sk.S <= 1 && rec_want && gemm16_conv_gn_rec_supported(ohw, N, OC, rup64(IC), ks);
+    const size_t rec_o = rec_on ? B.alloc((size_t)N * (ohw / GN_REC_CHUNK) * OC * sizeof(GnRec)) : 0;
+    if (rec_on) B.gn_rec[gi.node(last)] = rec_o;
     B.emit_at(emit_node, i, [=](hipStream_t st) {
         Epilogue e2 = ep;
         if (emb_arena) e2.chan_add = (const float*)(P->arena + emb_off);
         if (gn_on) gn_fill(e2, gnp, P->arena, N * OC);
+        if (rec_on) e2.gn_rec = (GnRec*)(P->arena + rec_o);
         launch_gemm16_conv(st, final_dst, P->arena + off, swz, SW, SH, IC, N, OC, ks, st_, pd, upscale, e2, sk.ws(P), sk.cnt(P), sk.S);
     });
     STAT(fused_conv)++;
@@ -2166,12 +2206,17 @@ bool plan_group_norm(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
         const bool have  = pre != B.gn_pre.end() && pre->second.w == w && pre->second.b == b && pre->second.groups == groups && pre->second.eps == eps;
         const size_t so  = have ? pre->second.off : B.alloc((size_t)N * C * 4 * 2);
         const size_t off = B.alloc((size_t)N * hw * rup64(C) * 2);
-        const int gsp    = have ? 0 : gn_stats_split(hw, C, N, groups);  // few large slabs: several workgroups per (image, group), partial sums in arena scratch
+        const auto rec   = B.gn_rec.find(x);  // per-channel records from the producing conv's epilogue: finalize instead of a pass over x
+        const bool byrec = !have && g_opt.fuse_gn_epilogue && rec != B.gn_rec.end();
+        const size_t ro  = byrec ? rec->second : 0;
+        const int gsp    = (have || byrec) ? 0 : gn_stats_split(hw, C, N, groups);  // few large slabs: several workgroups per (image, group), partial sums in arena scratch
         const size_t po  = gsp ? B.alloc((size_t)N * groups * gsp * 2 * 4) : 0;
+        if (byrec) STAT(fused_gn_epilogue)++;
         B.emit([=](hipStream_t st) {
             float* sc = (float*)(P->arena + so);
             float* sh = sc + N * C;
-            if (!have) launch_gn_stats(st, sc, sh, xp, hw, C, N, groups, eps, w, b, nullptr, 0, gsp ? (float*)(P->arena + po) : nullptr);
+            if (byrec) launch_gn_finalize(st, sc, sh, (const GnRec*)(P->arena + ro), nullptr, hw, C, C, N, groups, eps, w, b);
+            else if (!have) launch_gn_stats(st, sc, sh, xp, hw, C, N, groups, eps, w, b, nullptr, 0, gsp ? (float*)(P->arena + po) : nullptr);
             launch_nchw_to_nhwc_f16(st, P->arena + off, xp, hw, C, N, sc, sh, false);
         });
         chain.push_back(gi.sole(last));
@@ -2191,12 +2236,17 @@ bool plan_group_norm(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
         const bool have     = pre != B.gn_pre.end() && pre->second.w == w && pre->second.b == b && pre->second.groups == groups && pre->second.eps == eps;
         const size_t so     = have ? pre->second.off : B.alloc((size_t)N * C * 4 * 2);
         const size_t off    = B.alloc((size_t)N * hw * rup64(C) * 2);
-        const int gsp       = have ? 0 : gn_stats_split(hw, C, N, groups);
+        const auto rec      = B.gn_rec.find(x);
+        const bool byrec    = !have && g_opt.fuse_gn_epilogue && rec != B.gn_rec.end();
+        const size_t ro     = byrec ? rec->second : 0;
+        const int gsp       = (have || byrec) ? 0 : gn_stats_split(hw, C, N, groups);
         const size_t po     = gsp ? B.alloc((size_t)N * groups * gsp * 2 * 4) : 0;
+        if (byrec) STAT(fused_gn_epilogue)++;
         B.emit([=](hipStream_t st) {
             float* sc = (float*)(P->arena + so);
             float* sh = sc + N * C;
-            if (!have) launch_gn_stats(st, sc, sh, xp, hw, C, N, groups, eps, w, b, nullptr, 0, gsp ? (float*)(P->arena + po) : nullptr);
+            if (byrec) launch_gn_finalize(st, sc, sh, (const GnRec*)(P->arena + ro), nullptr, hw, C, C, N, groups, eps, w, b);
+            else if (!have) launch_gn_stats(st, sc, sh, xp, hw, C, N, groups, eps, w, b, nullptr, 0, gsp ? (float*)(P->arena + po) : nullptr);
             launch_nchw_to_nhwc_f16(st, P->arena + off, xp, hw, C, N, sc, sh, silu, nullptr, 0, nullptr, conv_mul);
         });
         STAT(kernels_planned)++;
@@ -2261,10 +2311,16 @@ bool plan_concat_gn(Builder& B, int i, hipStream_t, std::vector<int>& chain) {
     const size_t roff = jc >= 0 ? B.alloc((size_t)N * hw * rup64(C) * 2) : 0;
     const float *ap = (const float*)a->data, *bp = (const float*)b->data;
     const bool raw  = jc >= 0;
+    // both sources came out of conv epilogues that filled a side band: the two-source statistics are finalized from the records (groups may straddle the sources)
+    const auto ra = B.gn_rec.find(a), rb = B.gn_rec.find(b);
+    const bool byrec = g_opt.fuse_gn_epilogue && ra != B.gn_rec.end() && rb != B.gn_rec.end();
+    const size_t roa = byrec ? ra->second : 0, rob = byrec ? rb->second : 0;
+    if (byrec) STAT(fused_gn_epilogue)++;
     B.emit([=](hipStream_t st) {
         float* sc = (float*)(P->arena + so);
         float* sh = sc + N * C;
-        launch_gn_stats(st, sc, sh, ap, hw, C, N, groups, eps, w, bb, bp, C1);
+        if (byrec) launch_gn_finalize(st, sc, sh, (const GnRec*)(P->arena + roa), (const GnRec*)(P->arena + rob), hw, C, C1, N, groups, eps, w, bb);
+        else launch_gn_stats(st, sc, sh, ap, hw, C, N, groups, eps, w, bb, bp, C1);
         launch_nchw_to_nhwc_f16(st, P->arena + off, ap, hw, C, N, sc, sh, silu, bp, C1, raw ? (void*)(P->arena + roff) : nullptr);
     });
     B.packed[gi.node(last)] = Packed{off, rup64(C), true};
@@ -4067,6 +4123,7 @@ const OptionRow g_option_table[] = {
     OPT(fuse_rows16),
     OPT(fuse_cat_rows16),
     OPT(fuse_gn_stats),
+    OPT(fuse_gn_epilogue),  // unsplit window convs fill a per-channel GroupNorm side band in their epilogue; the statistics pass becomes k_gn_finalize
     OPT(fuse_joint_qkv),
     OPT(fuse_ln_reduce),
     OPT(jit_qimages),

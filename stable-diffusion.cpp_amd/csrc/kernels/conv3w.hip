@@ -301,6 +301,18 @@ __global__ __launch_bounds__(512, 2) void k_conv3w(G16Args g) {
         C3_MAIN(NPBMAX);
     }
 
+    // ---- epilogue with the GroupNorm side band (launch-uniform; unsplit launches only): the same stores + one GnRec per channel of this tile.  The records
+    // of the four wave rows meet in the window buffer the last channel block did NOT read: its last reader passed the barrier of the previous block's tap 8 and
+    // no DMA is in flight towards it, so no barrier is needed in front of the writes
+    if (g.ep.gn_rec) {
+        static_assert(4 * BN * (int)sizeof(GnRec) <= WBUF, "the tile's records fit one window buffer");
+        GnRec* lds = (GnRec*)(smem + (wb ^ 1) * WBUF);
+        if (g.ep.residual)
+            epi_conv_gn<true, BN, 4, 2, CB>(acc, g, row0, col0, wr, wc, lane, lds);
+        else
+            epi_conv_gn<false, BN, 4, 2, CB>(acc, g, row0, col0, wr, wc, lane, lds);
+        return;
+    }
     // ---- epilogue (shared with the round-2 conv): NCHW f32 scatter + bias (+ per-(image, channel) embedding add) (+ residual)
     if (g.ep.residual)
         epi_conv<1>(acc, g, row0, col0, wr, wc, lane);
@@ -347,6 +359,8 @@ int conv3w_plan(int64_t W, int64_t H, int64_t IC, int64_t N, int64_t OC, int ksi
     if (bn_out) *bn_out = bn;
     return S;
 }
+
+bool conv3w_gn_rec_supported(int64_t OHOW, int64_t OC, int64_t N) { return OHOW % GN_REC_CHUNK == 0 && OC % 32 == 0 && N > 0; }
 
 template <int TW, int BN>
 static void c3_launch(hipStream_t s, const G16Args& g, unsigned tiles, unsigned ny) {
@@ -395,6 +409,14 @@ void launch_conv3w(hipStream_t s, float* dst, const void* x16_nhwc, const void* 
     g.ep.chan_add = e.chan_add;
     g.ep.chan_ld  = (int)e.chan_ld;
     g.ncol_tiles  = (int)(OC / bn);
+    if (e.gn_rec) {
+        // the planner dropped a GroupNorm statistics pass for these records (plan_conv_chain::rec_register): a launch that cannot write them stops
+        if ((S > 1 && splitk_ws) || !conv3w_gn_rec_supported(g.OHOW, OC, N)) {
+            fprintf(stderr, "ggml-mi355x: conv3w asked for a GroupNorm side band on a launch it does not serve (split %d, %lld positions per image)\n", S, (long long)g.OHOW);
+            abort();
+        }
+        g.ep.gn_rec = e.gn_rec;
+    }
     if (S > 1 && splitk_ws) {
         g.split_k  = S;
         g.nt_slice = (g.nt + S - 1) / S;

@@ -14,7 +14,65 @@ struct G16Epi {  // dst = acc * scale + bias (+ residual); DiT variants: (acc*sc
     int gelu          = 0;        // f16-only output: tanh-GELU before rounding (Mlp fc1 -> fc2, block.hpp:249-258)
     const float* chan_add = nullptr;  // conv only: [N][OC] value added per (image, channel) — the ResBlock's time-embedding ADD (block.hpp:150-160)
     int chan_ld           = 0;        // floats between images of chan_add (0 = C)
+    GnRec* gn_rec         = nullptr;  // conv only, unsplit launches on whole 256-position tiles of one image: the GroupNorm side band this launch fills (epi_conv_gn)
 };
+
+// equal-count merge of two (mean, M2) records of n values each (hn = n / 2).  Symmetric in its operands: both lanes of an exchange get the same bits
+__device__ __forceinline__ void gn_merge(float& m, float& q, float m2, float q2, float hn) {
+    const float d = m2 - m;
+    q             = (q + q2) + (d * d) * hn;
+    m             = 0.5f * (m + m2);
+}
+template <int CTRL>
+__device__ __forceinline__ float gn_dpp(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true)); }
+// one transposing butterfly step: NP pairs of records (j, j + NP) become NP records — lanes with sel == 0 finish record j, the others record j + NP; the
+// partner lane (DPP control CTRL: it differs in the sel bit) sends the record this lane gives up
+template <int NP, int CTRL>
+__device__ __forceinline__ void gn_bfly(float (&m)[8], float (&q)[8], bool sel, float hn) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const float km = sel ? m[j + NP] : m[j], kq = sel ? q[j + NP] : q[j];
+        const float sm = sel ? m[j] : m[j + NP], sq = sel ? q[j] : q[j + NP];
+        m[j] = km;
+        q[j] = kq;
+        gn_merge(m[j], q[j], gn_dpp<CTRL>(sm), gn_dpp<CTRL>(sq), hn);
+    }
+}
+// (mean, M2) of the 32 RB values a wave holds per channel of one 32-channel block in the conv accumulator layout: v[rb] = the wave's RB (1 or 2) 32-position row
+// blocks, register r of lane l = channel (r & 3) + 8 (r >> 2) + 4 (l >> 5) at position l & 31.  A pairwise tree of equal-count merges in a fixed order: the two
+// row blocks, then lanes l / l + 16 (v_permlane16_swap), then l ^ 15, l ^ 7, l ^ 3, l ^ 1 inside a row of 16 lanes (DPP row_mirror, row_half_mirror, quad_perm) —
+// the first four lane steps also halve the number of records a lane carries (16 -> 1).  Every lane ends with the record of channel gn_lane_chan(lane); lanes
+// l and l ^ 1 hold the same bits.
+__device__ __forceinline__ int gn_lane_chan(int lane) {
+    const int j = (lane >> 1) & 7, r = (lane & 16) ? j : j + 8;
+    return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+}
+template <int RB>
+__device__ __forceinline__ void gn_wave_stats(const float (&v)[RB][16], int lane, float& mo, float& qo) {
+    static_assert(RB == 1 || RB == 2, "one or two row blocks per wave");
+    constexpr float n0 = (float)RB;  // values per lane and register
+    float m[8], q[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float ma = v[0][j + 8], qa = 0.f, mb = v[0][j], qb = 0.f;
+        if constexpr (RB == 2) {
+            gn_merge(ma, qa, v[1][j + 8], 0.f, 0.5f);
+            gn_merge(mb, qb, v[1][j], 0.f, 0.5f);
+        }
+        // vdst = register j + 8, src = register j: lanes 0..15 of a half finish register j + 8, lanes 16..31 register j (cf. epi_geglu16)
+        const auto sm = __builtin_amdgcn_permlane16_swap(__float_as_uint(ma), __float_as_uint(mb), false, false);
+        const auto sq = __builtin_amdgcn_permlane16_swap(__float_as_uint(qa), __float_as_uint(qb), false, false);
+        m[j] = __uint_as_float(sm[0]);
+        q[j] = __uint_as_float(sq[0]);
+        gn_merge(m[j], q[j], __uint_as_float(sm[1]), __uint_as_float(sq[1]), 0.5f * n0);
+    }
+    gn_bfly<4, 0x140>(m, q, (lane & 8) != 0, n0);        // row_mirror: l ^ 15
+    gn_bfly<2, 0x141>(m, q, (lane & 4) != 0, 2.f * n0);  // row_half_mirror: l ^ 7
+    gn_bfly<1, 0x1B>(m, q, (lane & 2) != 0, 4.f * n0);   // quad_perm [3,2,1,0]: l ^ 3
+    gn_merge(m[0], q[0], gn_dpp<0xB1>(m[0]), gn_dpp<0xB1>(q[0]), 8.f * n0);  // quad_perm [1,0,3,2]: l ^ 1
+    mo = m[0];
+    qo = q[0];
+}
 
 struct G16Args {
     const _Float16* A;
@@ -397,6 +455,67 @@ __device__ __forceinline__ void epi_conv(const float16_t (&acc)[RB][CB], const G
                 }
             }
         }
+    }
+}
+
+// epi_conv of a tile of 256 positions of ONE image (WR wave rows x RB row blocks: 4 x 2 or 8 x 1; full channel blocks) that also fills the GroupNorm side band
+// (GnRec, kernels.h): same values, same stores, walked channel block by channel block so that the 16 RB stored values of a lane are at hand for gn_wave_stats.
+// The wave rows' records meet in LDS (lds: WR x BN records that nothing else uses until the workgroup ends) and thread c < BN merges them pairwise — (0, 1),
+// (2, 3), ... then the pairs — into the tile's record of channel col0 + c.  No atomics, every order fixed.  RES: + residual
+template <bool RES, int BN, int WR, int RB, int CB>
+__device__ __forceinline__ void epi_conv_gn(const float16_t (&acc)[RB][CB], const G16Args& g, int64_t row0, int col0, int wr, int wc, int lane, GnRec* lds) {
+    static_assert(WR * RB == 8 && (RB == 1 || RB == 2), "a 256-position tile");
+    const int hi = lane >> 5, lc = lane & 31;
+    const uint32_t ohow = (uint32_t)g.OHOW;
+    const uint32_t img0 = (uint32_t)(row0 / g.OHOW), p0 = (uint32_t)(row0 - (int64_t)img0 * g.OHOW);
+    const uint32_t le   = (uint32_t)(wr * (RB * 32) + lc) + 4u * hi * ohow;  // per-lane elements relative to (img0, cblk, p0), row block 0
+    const uint32_t cld  = g.ep.chan_ld ? (uint32_t)g.ep.chan_ld : (uint32_t)g.C;
+    const int chl = gn_lane_chan(lane);
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+        const int cblk   = col0 + (wc * CB + cb) * 32;
+        const int64_t ub = ((int64_t)img0 * g.C + cblk) * g.OHOW + p0;  // uniform
+        const float* pb  = g.ep.bias ? g.ep.bias + cblk : nullptr;
+        const float* pc  = g.ep.chan_add ? g.ep.chan_add + (int64_t)img0 * cld + cblk : nullptr;
+        float v[RB][16];
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += 8) {
+            float bv[8], rv[RB][8];
+#pragma unroll
+            for (int r = r0; r < r0 + 8; ++r) {
+                const int ro = (r & 3) + 8 * (r >> 2);
+                bv[r - r0]   = pb ? ld_u(pb + ro, 16u * hi) : 0.f;
+                if (pc) bv[r - r0] += ld_u(pc + ro, 16u * hi);
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb) rv[rb][r - r0] = RES ? ld_u(g.ep.residual + ub + (int64_t)ro * g.OHOW + rb * 32, le * 4u) : 0.f;
+            }
+#pragma unroll
+            for (int r = r0; r < r0 + 8; ++r) {
+                const int ro = (r & 3) + 8 * (r >> 2);
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb) {
+                    v[rb][r] = acc[rb][cb][r] * g.ep.scale + bv[r - r0] + rv[rb][r - r0];
+                    st_u(g.dst + ub + (int64_t)ro * g.OHOW + rb * 32, le * 4u, v[rb][r]);
+                }
+            }
+        }
+        float m, q;
+        gn_wave_stats<RB>(v, lane, m, q);
+        if (!(lane & 1)) lds[wr * BN + (wc * CB + cb) * 32 + chl] = GnRec{m, q};
+    }
+    __syncthreads();
+    const int c = (wc * WR + wr) * 64 + lane;  // (not threadIdx.x: that register would stay live through the main loop)
+    if (c < BN) {
+        GnRec a[WR];
+#pragma unroll
+        for (int i = 0; i < WR; ++i) a[i] = lds[i * BN + c];
+        float hn = 16.f * RB;  // half the count of a wave row's record
+#pragma unroll
+        for (int st = 1; st < WR; st *= 2, hn *= 2.f)
+#pragma unroll
+            for (int i = 0; i < WR; i += 2 * st) gn_merge(a[i].mean, a[i].m2, a[i + st].mean, a[i + st].m2, hn);
+        const uint32_t chunks = ohow / (uint32_t)GN_REC_CHUNK, t = p0 / (uint32_t)GN_REC_CHUNK;
+        g.ep.gn_rec[((int64_t)img0 * chunks + t) * g.C + col0 + c] = a[0];
     }
 }
 

@@ -94,6 +94,8 @@ __global__ __launch_bounds__(WR * WC * 64, PIPE ? 2 : 2) void k_gemm16(G16Args g
     constexpr int SMEMB = QT ? QR0 + QNRAW * QRAWB : NST * (ABYTES + BBYTES);
     static_assert(SMEMB <= 160 * 1024, "LDS budget");
     __shared__ __attribute__((aligned(1024))) char smem[SMEMB];
+    constexpr bool G16_GN_REC_TILE = CONV && BM == 256 && BN != 128 && ((WR == 4 && RB == 2) || (WR == 8 && RB == 1));  // tiles whose epilogue can fill a GnRec side band (epi_conv_gn)
+    static_assert(!G16_GN_REC_TILE || WR * BN * (int)sizeof(GnRec) <= SMEMB, "the tile's records fit the staging ring");
 
     const int lane0 = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1003,6 +1005,17 @@ __global__ __launch_bounds__(WR * WC * 64, PIPE ? 2 : 2) void k_gemm16(G16Args g
             epi_dispatch_linear<BM>(acc, gs, row0, col0, wr, wc, lane);
         } else
         epi_dispatch_linear<BM>(acc, g, row0, col0, wr, wc, lane);
+    } else if (G16_GN_REC_TILE && g.ep.gn_rec) {
+        // GroupNorm side band (launch-uniform; g16_launch admits only unsplit launches of whole column tiles whose 256-row tile is GN_REC_CHUNK positions of one
+        // image): the same stores + one GnRec per channel of the tile.  The wave rows' records meet in the staging ring, dead behind this barrier.  Not compiled into
+        // the 256 x 128 tiles: two of their workgroups share a CU at <= 128 registers per lane, which this epilogue's 32 values + 16 records in flight would exceed
+        if constexpr (G16_GN_REC_TILE) {
+            __syncthreads();
+            if (g.ep.residual)
+                epi_conv_gn<true, BN, WR, RB, CB>(acc, g, row0, col0, wr, wc, lane, (GnRec*)smem);
+            else
+                epi_conv_gn<false, BN, WR, RB, CB>(acc, g, row0, col0, wr, wc, lane, (GnRec*)smem);
+        }
     } else {
         const bool fullc = col0 + BN <= g.C;
         if (fullc) {
@@ -1242,6 +1255,18 @@ int gemm16_worder_rows(const G16Args& g, unsigned gx, unsigned ny) {
     return wts >= 2.0 * act ? nrow : 0;
 }
 static bool g16_trace();
+// conv launches whose epilogue fills a GroupNorm side band (Epilogue::gn_rec, epi_conv_gn): unsplit, a 256-row tile with four wave rows of two row blocks
+// or eight wave rows of one (256 x 160 with four or eight waves, 256 x 320, 256 x 256 pipelined; not the 256 x 128 tiles), whole column tiles, whole GN_REC_CHUNK-position tiles per image
+static bool g16_gn_rec_tile_ok(int tile, int64_t C, int64_t ohow, int ny) {
+    const int bn = (tile == G16_T160 || tile == G16_T160N) ? 160 : (tile == G16_T320 ? 320 : (tile == G16_T256P ? 256 : 0));
+    return bn > 0 && ny == 1 && C % bn == 0 && ohow % GN_REC_CHUNK == 0;
+}
+// The planner registers a side band only after gemm16_conv_gn_rec_supported said yes for the launch's own shape, and then drops the GroupNorm's statistics
+// pass; a launch that cannot write the records stops instead of leaving them unwritten
+[[noreturn]] static void g16_gn_rec_contract_violation() {
+    fprintf(stderr, "ggml-mi355x: conv launch asked for a GroupNorm side band on a shape / tile it does not serve\n");
+    abort();
+}
 template <int BN_, bool CONV_>
 static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, double bytes) {  // bytes: algorithmic HBM bytes (operand images read once + output written once [+ residual])
     const unsigned ny = g.split_k > 1 ? (unsigned)g.split_k : 1u;
@@ -1286,6 +1311,9 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                 g16_launch<BN_, CONV_>(s, t, rows - (int64_t)rtm * 256, flops * (1.0 - fm), bytes * (1.0 - fm));
                 return;
             }
+        }
+        if constexpr (CONV_) {
+            if (g.ep.gn_rec && !g16_gn_rec_tile_ok(tile, g.C, g.OHOW, (int)ny)) g16_gn_rec_contract_violation();
         }
         if (tile != G16_T128) {
             const int64_t rt256 = (rows + 255) / 256;
@@ -1370,6 +1398,7 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
             return;
         }
     }
+    if (CONV_ && g.ep.gn_rec) g16_gn_rec_contract_violation();  // 128-row tiles do not fill a side band
     const dim3 grid((unsigned)(((rows + 127) / 128) * g.ncol_tiles * mul), ny);
     KScope ks_(s, CONV_ ? KF_CONV_T128 : KF_LINEAR, flops, bytes);
     // (measured and rejected: the hand-pipelined loop of the 256x320 tile instantiated for a 128x128 tile — 2 waves of 64x128, 4 stages, two
@@ -1990,6 +2019,13 @@ void launch_gemm16_linear_geglu(hipStream_t s, void* dst16, const void* a16, int
     g16_launch<128, false>(s, g, rows, 2.0 * rows * K * M, (double)rows * rup64(K, 64) * 2.0 + (double)rup64(K, 64) * rup64(M, 128) * 2.0 + (double)rows * (M / 2) * 2.0);
 }
 
+// an UNSPLIT launch_gemm16_conv of this shape (OHOW output positions per image, N images, K = ICp * ksize^2) fills a side band handed to it: the tile choice
+// g16_launch will make, tested the way it tests it
+bool gemm16_conv_gn_rec_supported(int64_t OHOW, int64_t N, int64_t OC, int64_t ICp, int ksize) {
+    if (OC <= 64 || g_g16_variant != 3) return false;
+    const int64_t nt = (int64_t)ksize * ksize * (ICp / 64) * (g16_bk32() ? 2 : 1);
+    return g16_gn_rec_tile_ok(g16_pick_tile(OHOW * N, OC, 0, true, 0, nt, 1), OC, OHOW, 1);
+}
 void launch_gemm16_conv(hipStream_t s, float* dst, const void* x16_nhwc, const void* wswz, int64_t W, int64_t H, int64_t IC, int64_t N, int64_t OC, int ksize,
                         int stride, int pad, bool upscale2x, const Epilogue& e, float* splitk_ws, int* splitk_cnt, int splitk_S) {
     G16Args g{};
@@ -2020,6 +2056,8 @@ void launch_gemm16_conv(hipStream_t s, float* dst, const void* x16_nhwc, const v
     g.ep.chan_ld  = (int)e.chan_ld;
     const bool inker = splitk_ws && splitk_cnt != nullptr && splitk_S > 1;
     const int S      = inker ? splitk_S : (splitk_ws ? gemm16_split_k(g.R, OC, (int64_t)g.ICp * ksize * ksize, true) : 1);
+    if (e.gn_rec && (S > 1 || OC <= 64)) g16_gn_rec_contract_violation();
+    g.ep.gn_rec = e.gn_rec;
     if (S > 1) {
         g.split_k  = S;
         g.nt_slice = (g.nt + S - 1) / S;
@@ -2514,6 +2552,54 @@ __global__ __launch_bounds__(64) void k_gn_stats_final(float* __restrict__ scale
         shift[(int64_t)n * C + c] = (b ? b[c] : 0.f) - mean * sc;
     }
 }
+// GroupNorm tables from the side band(s) a conv epilogue filled (GnRec, kernels.h) — no pass over the tensor.  One wave per (image, group): the group's
+// records are those of its channels c0 .. c1 - 1 in every chunk, channel c < C1 from r1 ([N][chunks][C1]), the others from r2 ([N][chunks][C - C1]) as gn_ld4
+// splits a concatenation (a group may straddle the two).  Merge in a fixed order, in double (a few hundred records: no cancellation question left):
+// mean = sum m * mean_t / sum m, then M2 = sum [M2_t + m (mean_t - mean)^2]; lane l takes records l, l + 64, ..., the lanes are added by a xor butterfly.
+__device__ __forceinline__ double gn_wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ __launch_bounds__(64) void k_gn_finalize(float* __restrict__ scale, float* __restrict__ shift, const GnRec* __restrict__ r1, const GnRec* __restrict__ r2, int chunks,
+                                                    int C, int C1, int groups, int cpg, float eps, const float* __restrict__ w, const float* __restrict__ b) {
+    const int gidx = blockIdx.x % groups, n = blockIdx.x / groups;
+    const int c0 = gidx * cpg, c1 = min(c0 + cpg, C);
+    if (c0 >= c1) return;
+    const int nc = c1 - c0, nrec = nc * chunks;
+    auto rec = [&](int i) -> GnRec {
+        const int t = i / nc, c = c0 + (i - t * nc);
+        return c < C1 ? r1[((int64_t)n * chunks + t) * C1 + c] : r2[((int64_t)n * chunks + t) * (C - C1) + (c - C1)];
+    };
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nrec; i += 64) s += (double)rec(i).mean;  // every record counts GN_REC_CHUNK values: the mean of the means
+    const double mean = gn_wave_sum_f64(s) / (double)nrec;
+    double q = 0.0;
+    for (int i = threadIdx.x; i < nrec; i += 64) {
+        const GnRec r  = rec(i);
+        const double d = (double)r.mean - mean;
+        q += (double)r.m2 + (double)GN_REC_CHUNK * d * d;
+    }
+    const double var = gn_wave_sum_f64(q) / ((double)nrec * (double)GN_REC_CHUNK);
+    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    for (int c = c0 + threadIdx.x; c < c1; c += 64) {
+        const float sc            = (w ? w[c] : 1.f) * rstd;
+        scale[(int64_t)n * C + c] = sc;
+        shift[(int64_t)n * C + c] = (b ? b[c] : 0.f) - (float)mean * sc;
+    }
+}
+void launch_gn_finalize(hipStream_t s, float* scale, float* shift, const GnRec* r1, const GnRec* r2, int64_t hw, int64_t C, int64_t C1, int64_t N, int groups, float eps,
+                        const float* w, const float* b) {
+    if (hw % GN_REC_CHUNK != 0 || !r1 || (r2 != nullptr) != (C1 < C) || C1 <= 0 || C1 > C) {
+        fprintf(stderr, "ggml-mi355x: GroupNorm finalize asked for a shape the side band does not describe\n");
+        abort();
+    }
+    const int chunks = (int)(hw / GN_REC_CHUNK), cpg = (int)((C + groups - 1) / groups);
+    KScope ks_(s, KF_GN_STATS, 0.0, (double)N * chunks * C * 8.0 + (double)N * C * 8.0);  // the records once, the two tables once
+    if (g16_trace()) fprintf(stderr, "GN finalize hw=%lld C=%lld N=%lld groups=%d C1=%lld\n", (long long)hw, (long long)C, (long long)N, groups, (long long)C1);
+    k_gn_finalize<<<(unsigned)(N * groups), 64, 0, s>>>(scale, shift, r1, r2, chunks, (int)C, (int)C1, groups, cpg, eps, w, b);
+}
+
 static int64_t g_gn_split_min = 1 << 16;  // option "gn_split_min": least floats per (image, group) slab for the shared-slab form (0 turns it off: 1 << 62)
 void gemm16_set_gn_split_min(int v) { g_gn_split_min = v <= 0 ? (1ll << 62) : (int64_t)v; }
 // workgroups per slab for that form (0: the one-workgroup-per-slab kernels); the caller provides N * groups * P * 2 floats of scratch
@@ -2534,6 +2620,7 @@ bool gn_two_source_supported(const float* x, const float* x2, int64_t hw, int64_
 void launch_gn_stats(hipStream_t s, float* scale, float* shift, const float* x, int64_t hw, int64_t C, int64_t N, int groups, float eps, const float* w,
                      const float* b, const float* x2, int64_t C1, float* part) {
     KScope ks_(s, KF_GN_STATS, 0.0, (double)hw * C * N * 4.0);  // algorithmic: ONE read of the activation
+    if (g16_trace()) fprintf(stderr, "GN stats hw=%lld C=%lld N=%lld groups=%d C1=%lld\n", (long long)hw, (long long)C, (long long)N, groups, (long long)(x2 ? C1 : C));
     const int cpg       = (int)((C + groups - 1) / groups);
     const int64_t cnt   = (int64_t)cpg * hw;
     const bool v4       = hw % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)x2)) & 15) == 0;  // (a short last group is fine: the kernels bound it by c1)

@@ -75,6 +75,16 @@ void launch_wswz_conv(hipStream_t s, void* dst, const void* src, int64_t KW, int
 // kblk: K ordered (kblk-channel block, tap, channel): 64 for the per-tap gather kernels of gemm16.hip, 32 for the LDS-window kernel of conv3w.hip;
 // 0: (tap, channel)
 
+// GroupNorm partial-statistics side band: what a conv epilogue knows about the f32 values it stores, kept per channel so that ANY grouping of the
+// channels (a GroupNorm on the tensor, on a channel concatenation of two tensors, groups that straddle the two sources) can be finished from it
+// by k_gn_finalize.  One record per (image n, chunk t, channel c): mean and M2 = sum (v - mean)^2 over the chunk's positions of that image and channel,
+// v = exactly the value stored (acc * scale + bias + chan_add + residual).  A chunk is GN_REC_CHUNK consecutive positions of one image — the row tile of the
+// conv kernels.  Layout: rec[(n * chunks + t) * C + c], chunks = OH * OW / GN_REC_CHUNK: N * chunks * C * 8 bytes (655 KB for 16 x 320 x 64 x 64).
+struct GnRec {
+    float mean, m2;
+};
+constexpr int GN_REC_CHUNK = 256;
+
 struct Epilogue {
     const float* bias     = nullptr;  // per output feature / channel
     const float* residual = nullptr;  // same layout as dst (added after bias)
@@ -90,6 +100,9 @@ struct Epilogue {
     const float* gn_b     = nullptr;
     int gn_groups         = 0;
     float gn_eps          = 0.f;
+    // conv only, UNSPLIT launches only: the side band of per-channel partial statistics this launch's epilogue fills (planner look-ahead: a GroupNorm, or a
+    // skip CONCAT feeding one, reads the output).  Only for launches conv3w_gn_rec_supported / gemm16_conv_gn_rec_supported accept; any other launch handed one aborts.
+    GnRec* gn_rec         = nullptr;
     // Linear only, split-K launches with the slab reduce pass only: the LayerNorm (-> MUL w -> ADD b) that reads this output next and feeds only
     // weight GEMMs (planner look-ahead, plan_linear) — the reduce pass keeps each finished row in registers and also writes that LayerNorm's
     // f16 operand image (k_splitk_reduce_ln): no second read of the tensor, no second launch
@@ -175,11 +188,15 @@ void gemm16_set_splitk_in_target(int v);
 // x16: f16 NHWC [N][H][W][ICp]; dst f32 NCHW [OW,OH,OC,N]
 void launch_gemm16_conv(hipStream_t s, float* dst, const void* x16_nhwc, const void* wswz, int64_t W, int64_t H, int64_t IC, int64_t N, int64_t OC,
                         int ksize, int stride, int pad, bool upscale2x, const Epilogue& ep, float* splitk_ws = nullptr, int* splitk_cnt = nullptr, int splitk_S = 0);
+// an UNSPLIT launch_gemm16_conv of this shape can fill a GnRec side band (Epilogue::gn_rec): a 256-row tile = GN_REC_CHUNK positions of one image
+bool gemm16_conv_gn_rec_supported(int64_t OHOW, int64_t N, int64_t OC, int64_t ICp, int ksize);
 // ---- conv3w.hip: 3x3 / stride-1 conv with the input window resident in LDS (weights in the kblk = 32 image)
 // K slices the window kernel would run this shape with (>= 1), or 0: the shape stays on launch_gemm16_conv
 int conv3w_plan(int64_t W, int64_t H, int64_t IC, int64_t N, int64_t OC, int ksize, int stride, bool upscale2x, int* bn_out = nullptr);
 void launch_conv3w(hipStream_t s, float* dst, const void* x16_nhwc, const void* wswz32, int64_t W, int64_t H, int64_t IC, int64_t N, int64_t OC, const Epilogue& ep,
                    float* splitk_ws, int S);
+// an UNSPLIT launch_conv3w of this output can fill a GnRec side band (Epilogue::gn_rec): every tile is GN_REC_CHUNK positions of one image
+bool conv3w_gn_rec_supported(int64_t OHOW, int64_t OC, int64_t N);
 void qgemm16_set_rb(int v);   // option "qgemm16_rb" (3): row blocks per k_qgemm16 tile (1 / 2 / 4 forced; 3 = 64-row tiles for small grids; 0 = by row count only)
 void conv3w_set_prio(int v);  // option "conv3w_prio" (3): static wave priority of the second half of a k_conv3w workgroup; 0 = without (A/B)
 void conv3w_set(int v);  // option "conv3w"
@@ -201,6 +218,10 @@ bool gn_two_source_supported(const float* x, const float* x2, int64_t hw, int64_
 void launch_gn_stats(hipStream_t s, float* scale, float* shift, const float* x, int64_t hw, int64_t C, int64_t N, int groups, float eps,
                      const float* w, const float* b, const float* x2 = nullptr, int64_t C1 = 0, float* part = nullptr);
 int gn_stats_split(int64_t hw, int64_t C, int64_t N, int groups);
+// GroupNorm scale / shift tables from the side band(s) a conv epilogue filled (Epilogue::gn_rec) instead of a pass over the tensor: r1 holds C1 channels per
+// image, r2 (nullptr: one source, C1 = C) the remaining C - C1 of a channel concatenation; both over hw positions in chunks of GN_REC_CHUNK
+void launch_gn_finalize(hipStream_t s, float* scale, float* shift, const GnRec* r1, const GnRec* r2, int64_t hw, int64_t C, int64_t C1, int64_t N, int groups, float eps,
+                        const float* w, const float* b);
 void gemm16_set_gn_split_min(int v);  // option "gn_split_min" (65536 floats): least slab size for it; 0 = never  // workgroups per slab the split form would use (0: not used for this shape)
 void launch_nchw_to_nhwc_f16(hipStream_t s, void* dst, const float* x, int64_t hw, int64_t C, int64_t N, const float* scale, const float* shift,
                              int act, const float* x2 = nullptr, int64_t C1 = 0, void* dst_raw = nullptr, float post_mul = 1.f, float* dst_f32 = nullptr);  // act: 0 none, 1 SiLU, 2 ReLU (after the affine); post_mul: after affine / activation (Conv2d scale); dst_f32: the activated values also as f32 NCHW (may be x itself: the in-place unary), single source only
