@@ -105,6 +105,7 @@ struct ggml_backend_mi355x_stats {
     int64_t flash_mslot_launches;   /* ... that took the one-block max-slot kernel (d = 40, f16 K / V) */
     int64_t flash_generic_launches; /* ... that took a !FAST instantiation (generic staging: f32 or strided K / V, d % 8 != 0) */
     int64_t fused_gn_epilogue;   /* GroupNorms (direct, or over a skip CONCAT) whose statistics pass was replaced by k_gn_finalize over the per-channel records the producing conv epilogues wrote (option fuse_gn_epilogue) */
+    int64_t fused_tile_merge;    /* overlap merges of a VAE tile batch (MUL by the row ramps -> MUL by the column ramps -> per tile ADD in place / CPY into a view of the canvas) run as ONE gather launch of k_tile_merge (option fuse_tile_merge) */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and
@@ -168,7 +169,9 @@ GGML_MI355X_API int ggml_backend_mi355x_get_kernel_timings(struct ggml_backend_m
  * "fuse_flash_slices" (1: the proj Linears of an MMDiT / FLUX double block read their token slices out of the flash kernel's f16 image), "gemm16_t192p" (1: the pipelined 256 x 192 Linear tile where it quantises better on 256 CUs), "hoist_mod" (1), "plan_cache_cap" (512), "gn_split_min" (65536);
  * "fuse_ln_reduce" (1: the slab reduce of a split-K Linear also writes the f16 operand image of the LayerNorm that reads its result);
  * "fuse_gn_epilogue" (1: an unsplit LDS-window conv read by a GroupNorm, or by a skip CONCAT a GroupNorm reads, writes per-channel (mean, M2) records of the values it
- * stores; the GroupNorm's statistics pass over the tensor becomes one small finalize launch over the records; 0 = the plan without it).
+ * stores; the GroupNorm's statistics pass over the tensor becomes one small finalize launch over the records; 0 = the plan without it);
+ * "fuse_tile_merge" (1: the overlap merge of a VAE tile batch — two MULs by the ramp vectors and one ADD in place / CPY per tile into views of the canvas — as one
+ * launch of k_tile_merge: every canvas cell of the batch's bounding box is read and written once, results bit-identical to the plain nodes; timed in family 11).
  * An unknown key changes nothing and is named on stderr.  Wrong-result timing ablations exist only in builds with -DMI355X_EXPERIMENTS ("gemm16_abl"). */
 GGML_MI355X_API void ggml_backend_mi355x_set_option(const char* key, int value);
 /* What the calling thread's current device delivers, measured in about a second (csrc/kernels/calib.hip): an MFMA loop from registers (f16, 32x32x16: the

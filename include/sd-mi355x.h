@@ -221,6 +221,36 @@ SD_API bool sd_unet_forward_skip_layers(sdm_ctx_t* ctx, const float* x, int w, i
                                         int64_t n_tokens, int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const int* skip_layers, int n_skip, float* out);
 /* VAE decode_first_stage (stable-diffusion.cpp:3062-3078): latents [w,h,zc,n] (diffusion scale) -> rgb f32 [8w,8h,3,n] in [0,1] */
 SD_API bool sd_vae_decode(sdm_ctx_t* ctx, const float* latents, int w, int h, int c, int n, float* out_rgb);
+/* the same WITHOUT the host step of VAE::decode (vae.hpp:216-218: (x + 1) / 2 and the clamp): what the decoder graph wrote, [8w,8h,3,n] — with tiling on, the merged canvas.
+ * sd_vae_decode is this call followed by that step (the reference also applies it once, to the merged result, never per tile) */
+SD_API bool sd_vae_decode_raw(sdm_ctx_t* ctx, const float* latents, int w, int h, int c, int n, float* out);
+/* VAE tiling: sd_tiling_params_t (include/stable-diffusion.h, `--vae-tiling`; sd_img_gen_params_t::vae_tiling_params), same fields, same order, same defaults
+ * ({false, 0, 0, 0.5f, 0, 0}), + tile_batch (OURS): tiles decoded / encoded per graph compute, stacked along the batch dimension (GroupNorm and attention are per
+ * sample, so a tile's arithmetic does not depend on its neighbours in the batch); 0 = the engine's default (DESIGN.md 1, row "VAE tiling").  Tile sizes follow
+ * VAE::get_tile_sizes (src/model/vae/vae.hpp:89-116), tile counts / achieved overlap sd_tiling_calc_tiles (src/core/ggml_extend.hpp:691-739, non-circular branch),
+ * tile order / positions / the shifted last tile process_tiles_2d (:823-951), the overlap blend sd_tensor_merge_2d (:771-821).  Not implemented: circular and
+ * temporal tiling, extra_tiling_args. */
+typedef struct {
+    bool enabled;
+    int tile_size_x, tile_size_y; /* latent cells; < 4 = the default 32 */
+    float target_overlap;         /* clamped to [0, 0.5] */
+    float rel_size_x, rel_size_y; /* (0, 1]: fraction of the latent size; > 1: tile count; wins over tile_size_* */
+    int tile_batch;
+} sdm_tiling_params_t;
+SD_API void sdm_tiling_params_init(sdm_tiling_params_t* p);
+/* context state like sd_use_tae (the reference keeps vae_tiling_params on its context too): honoured by sd_vae_decode(_raw), sd_vae_encode and, through them,
+ * sdm_generate_image.  NULL or enabled == false: the untiled path, exactly as before.  Tiles are cropped on the host, run through the ordinary VAE graph
+ * tile_batch at a time (one graph topology for every full batch) and blended ON THE DEVICE into a canvas that is read back once (the reference merges on the
+ * host per tile); with tiling on, the encoder's Gaussian sample and latent scaling run on the merged moments (VAE::encode, vae.hpp:118-168) */
+SD_API bool sd_set_vae_tiling(sdm_ctx_t* ctx, const sdm_tiling_params_t* params);
+/* the tile plan alone (host arithmetic, for known-answer tests): small_w x small_h is the LATENT size (decode: of the input; encode: of the output),
+ * encode_factor VAE::get_tile_sizes' encoding_factor (1 decode, 2 the image VAE's encode).  tile_size[2] / overlap[2]: latent cells per axis (x, y);
+ * tiles: (x, y, dx, dy) per tile in processing order (y outer, x inner), all in latent cells — dx / dy are the first columns / rows of a shifted last tile
+ * that the merge skips.  Returns the tile count (also when it exceeds tile_capacity: nothing beyond the capacity is written), -1 on bad arguments. */
+SD_API int sd_tiling_plan(int small_w, int small_h, const sdm_tiling_params_t* params, float encode_factor, int* tile_size, int* overlap, int* tiles, int tile_capacity);
+/* the tiling driver with the IDENTITY in place of the VAE (tile size / overlap in cells of the input, encode_factor 1): crops, tile batches, the device merge and
+ * the read-back alone — [w,h,c,n] -> [w,h,c,n].  The ramps of overlapping tiles sum to 1, so the result equals the input up to rounding (partition-of-unity test) */
+SD_API bool sd_tiling_blend(sdm_ctx_t* ctx, const float* in, int w, int h, int c, int n, float* out);
 /* VAE encode — encode_first_stage (stable-diffusion.cpp:3042-3060): rgb f32 planar [w,h,3,n] in [0,1] -> diffusion latents [w/8,h/8,zc,n], SAMPLED from the encoder's diagonal
  * Gaussian with Philox(seed) like the reference (auto_encoder_kl.hpp:750-759) and scaled to the diffusion model's range; moments_out (optional) receives the graph's output
  * [w/8,h/8,2*zc,n] (mean | log-variance).  The encoder ("first_stage_model.encoder. ...", "first_stage_model.quant_conv. ...") is made on first use. */

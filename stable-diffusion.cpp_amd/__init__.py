@@ -109,6 +109,12 @@ class SdImage(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("channel", C.c_uint32), ("data", C.POINTER(C.c_uint8))]
 
 
+class SdTilingParams(C.Structure):
+    """sdm_tiling_params_t (include/sd-mi355x.h)"""
+    _fields_ = [("enabled", C.c_bool), ("tile_size_x", C.c_int), ("tile_size_y", C.c_int), ("target_overlap", C.c_float),
+                ("rel_size_x", C.c_float), ("rel_size_y", C.c_float), ("tile_batch", C.c_int)]
+
+
 class SdStats(C.Structure):
     _fields_ = [("last_sample_ms", C.c_double), ("last_decode_ms", C.c_double), ("unet_calls", C.c_int64),
                 ("graph_nodes", C.c_int64), ("compute_buffer_bytes", C.c_size_t), ("weight_bytes", C.c_size_t),
@@ -328,7 +334,7 @@ def load_mi355x_backend() -> None:
 _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned kernels_launched fused_conv fused_conv_bounced fused_linear "
                         "fused_norm fused_geglu fused_attention generic_matmul swizzled_weight_bytes graph_replays fused_linear_geglu "
                         "split_k_gemms head_major_gemms fused_modulate fused_gate fused_gelu fused_rope fused_concat_heads qgemv_linears fused_chan_add fused_proj_tokens gemm_attention fused_q16 split_k_inlaunch qgemm16_linears fgemv_linears fused_presilu fused_sibling_linears hoisted_kv_linears window_convs hoisted_emb_linears fused_rows16 fused_joint_qkv jit_images fused_cat_rows16 fused_gn_stats fused_ln_reduce redirect_fallbacks fused_concat_gn fused_conv_scale view_graphs plans_evicted hoisted_mod_linears view_external_nodes qinloop_linears flash_out_alias flash_slice_images "
-                        "flash_short_launches flash_qb2_launches flash_mslot_launches flash_generic_launches fused_gn_epilogue").split()
+                        "flash_short_launches flash_qb2_launches flash_mslot_launches flash_generic_launches fused_gn_epilogue fused_tile_merge").split()
 
 
 class BackendStats(C.Structure):
@@ -640,14 +646,45 @@ class Engine:
             raise EngineError("sd_unet_forward_skip_layers failed: " + L.sd_last_error().decode())
         return out
 
-    def vae_decode(self, latents: np.ndarray) -> np.ndarray:
-        """latents [N,C,h,w] (diffusion scale) -> rgb [N,3,8h,8w] in [0,1]."""
+    def vae_decode(self, latents: np.ndarray, raw: bool = False) -> np.ndarray:
+        """latents [N,C,h,w] (diffusion scale) -> rgb [N,3,8h,8w] in [0,1]; raw: sd_vae_decode_raw, the decoder output before (x + 1) / 2 and the clamp
+        (with tiling on, the merged canvas)."""
         z = _f32(latents)
         n, c, h, w = z.shape
         out = np.empty((n, 3, h * 8, w * 8), dtype=np.float32)
-        if not lib().sd_vae_decode(self._ctx, _fptr(z), w, h, c, n, _fptr(out)):
-            raise EngineError("sd_vae_decode failed: " + lib().sd_last_error().decode())
+        L = lib()
+        L.sd_vae_decode_raw.argtypes = L.sd_vae_decode.argtypes
+        L.sd_vae_decode_raw.restype = C.c_bool
+        if not (L.sd_vae_decode_raw if raw else L.sd_vae_decode)(self._ctx, _fptr(z), w, h, c, n, _fptr(out)):
+            raise EngineError("sd_vae_decode failed: " + L.sd_last_error().decode())
         return out
+
+    def tiling_blend(self, x: np.ndarray) -> np.ndarray:
+        """sd_tiling_blend: the tiling driver (crop, tile batches, device merge) around the identity — x [N,C,H,W] -> the blended canvas of the same shape."""
+        a = _f32(x)
+        n, c, h, w = a.shape
+        out = np.empty_like(a)
+        L = lib()
+        L.sd_tiling_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.sd_tiling_blend.restype = C.c_bool
+        if not L.sd_tiling_blend(self._ctx, _fptr(a), w, h, c, n, _fptr(out)):
+            raise EngineError("sd_tiling_blend failed: " + L.sd_last_error().decode())
+        return out
+
+    def set_vae_tiling(self, enabled: bool = True, tile_size_x: int = 0, tile_size_y: int = 0, target_overlap: float = 0.5, rel_size_x: float = 0.0,
+                       rel_size_y: float = 0.0, tile_batch: int = 0) -> None:
+        """sd_set_vae_tiling — the reference's `--vae-tiling` (sd_tiling_params_t) + tile_batch, the tiles per graph compute (0 = the engine's default).
+        Honoured by vae_decode, vae_encode and generate_image; enabled=False restores the untiled path."""
+        L = lib()
+        L.sd_set_vae_tiling.argtypes = [C.c_void_p, C.POINTER(SdTilingParams)]
+        L.sd_set_vae_tiling.restype = C.c_bool
+        if enabled is None:
+            ok = L.sd_set_vae_tiling(self._ctx, None)
+        else:
+            p = SdTilingParams(bool(enabled), tile_size_x, tile_size_y, target_overlap, rel_size_x, rel_size_y, tile_batch)
+            ok = L.sd_set_vae_tiling(self._ctx, C.byref(p))
+        if not ok:
+            raise EngineError("sd_set_vae_tiling failed: " + L.sd_last_error().decode())
 
     def vae_encode(self, rgb: np.ndarray, seed: int = 42, return_moments: bool = False):
         """sd_vae_encode: rgb [N,3,H,W] in [0,1] -> diffusion latents [N,zc,H/8,W/8] sampled with Philox(seed) (+ the moments [N,2*zc,H/8,W/8] the graph produced)."""
@@ -899,6 +936,24 @@ def rccl_comm_create(device: int, nranks: int, rank: int, unique_id: bytes):
 
 def rccl_comm_destroy(comm) -> None:
     lib().sd_rccl_comm_destroy(comm)
+
+
+def tiling_plan(small_w: int, small_h: int, tile_size_x: int = 0, tile_size_y: int = 0, target_overlap: float = 0.5, rel_size_x: float = 0.0,
+                rel_size_y: float = 0.0, encode_factor: float = 1.0) -> dict:
+    """sd_tiling_plan: the VAE tile plan over a small_w x small_h latent — {"tile_size": (x, y), "overlap": (x, y), "tiles": [(x, y, dx, dy), ...]} in latent
+    cells, tiles in processing order (y outer, x inner); dx / dy = leading cells of a shifted last tile that the merge skips."""
+    L = lib()
+    L.sd_tiling_plan.argtypes = [C.c_int, C.c_int, C.POINTER(SdTilingParams), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.sd_tiling_plan.restype = C.c_int
+    p = SdTilingParams(True, tile_size_x, tile_size_y, target_overlap, rel_size_x, rel_size_y, 0)
+    ts = np.zeros(2, dtype=np.int32)
+    ov = np.zeros(2, dtype=np.int32)
+    n = L.sd_tiling_plan(small_w, small_h, C.byref(p), encode_factor, _fptr(ts), _fptr(ov), None, 0)
+    if n < 0:
+        raise EngineError("sd_tiling_plan: bad arguments")
+    tiles = np.zeros((n, 4), dtype=np.int32)
+    L.sd_tiling_plan(small_w, small_h, C.byref(p), encode_factor, _fptr(ts), _fptr(ov), _fptr(tiles), n)
+    return {"tile_size": (int(ts[0]), int(ts[1])), "overlap": (int(ov[0]), int(ov[1])), "tiles": [tuple(int(v) for v in row) for row in tiles]}
 
 
 def cfg_combine(cond: np.ndarray, uncond: np.ndarray, scale: float) -> np.ndarray:

@@ -168,7 +168,7 @@ std::atomic<int64_t> g_stat_counters[N_STATS];
 #define STAT(field) g_stat_counters[offsetof(ggml_backend_mi355x_stats, field) / sizeof(int64_t)]
 
 struct Options {
-    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1}, fuse_gn_epilogue{1};
+    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1}, fuse_gn_epilogue{1}, fuse_tile_merge{1};
 } g_opt;
 
 using Step = std::function<void(hipStream_t)>;  // one launch (or a few) of a plan
@@ -3552,6 +3552,102 @@ void plan_flux_qkv(Builder& B) {
 // (Measured, rejected and removed: the just-in-time weight-image rebuild of Linear k+1 forked onto a side stream while the GEMM of Linear k computes.  Bit-identical and
 // SLOWER, profiles/r07h_ab_jit_overlap.txt: FLUX.1-dev 89.97 -> 92.58 ms per step (+2.9 %) — the 256 x 256 GEMM tile owns its CU, so the rebuild's workgroups only get the
 // CUs the GEMM's last round has left and arrive as a burst of 75 MB of writes exactly when the next GEMM wants its first tiles.)
+// Overlap merge of one VAE tile batch (the host's tiled decode / encode, csrc/host/engine.cpp vae_tiled; the reference merges on the host, sd_tensor_merge_2d,
+// src/core/ggml_extend.hpp:771-821):
+//   m1 = MUL(tiles [TW,TH,C,N*k], wy [1,TH,1,k]);  m2 = MUL(m1, wx [TW,1,1,k]);
+//   per tile t, in order: ADD in place (or CPY) of VIEW(m2: tile t behind its skip, all N images) into VIEW(canvas at the tile's position behind the skip)
+// -> ONE launch of k_tile_merge (gather form: the tiles of a batch overlap each other, so a launch per tile or a workgroup per tile would race or cost k passes
+// over the canvas).  m1 / m2 are never written, so the match refuses whenever anything else could read them: another consumer, an OUTPUT flag, a reader outside a
+// sub-graph view (GInfo's phantom consumer), a non-view node between the chain's nodes; and whenever a tile operand shares memory with the canvas.
+bool plan_tile_merge(Builder& B, int i, std::vector<int>& chain) {
+    if (!g_opt.fusion || !g_opt.fuse_tile_merge) return false;
+    GInfo& gi             = B.gi;
+    const ggml_tensor* m1 = gi.node(i);
+    const ggml_tensor *S = m1->src[0], *wy = m1->src[1];
+    if (!S || !wy || !is_f32(m1) || !is_f32(S) || !is_f32(wy) || !contig(S) || !contig(wy) || !contig(m1) || (m1->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
+    const int64_t TW = S->ne[0], TH = S->ne[1], C = S->ne[2], NK = S->ne[3], k = wy->ne[3];
+    if (wy->ne[0] != 1 || wy->ne[1] != TH || wy->ne[2] != 1 || k < 1 || k > TILE_MERGE_MAX || NK % k != 0) return false;
+    const int64_t N = NK / k;
+    const int j1    = gi.sole(i);
+    if (j1 < 0) return false;
+    const ggml_tensor* m2 = gi.node(j1);
+    if (xop(m2) != GGML_OP_MUL || m2->src[0] != m1 || (m2->flags & GGML_TENSOR_FLAG_OUTPUT) || !contig(m2)) return false;
+    const ggml_tensor* wx = m2->src[1];
+    if (!wx || !is_f32(wx) || !contig(wx) || wx->ne[0] != TW || wx->ne[1] != 1 || wx->ne[2] != 1 || wx->ne[3] != k) return false;
+    if ((int64_t)gi.consumers[j1].size() != k) return false;
+    if (TW > INT32_MAX || TH > INT32_MAX || C * N > INT32_MAX) return false;
+    TileMergeArgs a;
+    memset(&a, 0, sizeof(a));
+    const ggml_tensor* R = nullptr;  // the canvas
+    int store = -1, last = j1;
+    std::vector<char> seen((size_t)k, 0);
+    std::vector<std::pair<int, TileMergeTile>> found;  // (op node, descriptor): sorted into graph order below
+    for (int jv : gi.consumers[j1]) {
+        const ggml_tensor* v = gi.node(jv);
+        if (xop(v) != GGML_OP_VIEW || v->view_src != m2 || (v->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
+        const int jop = gi.sole(jv);
+        if (jop < 0) return false;
+        const ggml_tensor* op = gi.node(jop);  // (a reader outside a sub-graph view is the phantom node: neither ADD nor CPY)
+        const bool is_add = xop(op) == GGML_OP_ADD, is_cpy = xop(op) == GGML_OP_CPY;
+        if (!is_add && !is_cpy) return false;
+        if (store >= 0 && store != (is_cpy ? 1 : 0)) return false;
+        store                 = is_cpy ? 1 : 0;
+        const ggml_tensor* cv = is_add ? op->src[0] : op->src[1];
+        if ((is_add ? op->src[1] : op->src[0]) != v || !cv || !is_f32(cv) || !is_f32(op) || !cv->view_src) return false;
+        if (R && cv->view_src != R) return false;
+        R = cv->view_src;
+        // the op writes the canvas view itself (ggml_add_inplace / ggml_cpy return a view of their destination)
+        if (op->data != cv->data || op->view_src != R) return false;
+        for (int d = 0; d < 4; ++d)
+            if (op->ne[d] != cv->ne[d] || op->nb[d] != cv->nb[d] || v->ne[d] != cv->ne[d]) return false;
+        // the tile view: tile t behind (dx, dy), all N images
+        if (v->nb[0] != 4 || v->nb[1] != m2->nb[1] || v->nb[2] != m2->nb[2] || v->nb[3] != m2->nb[3] * (size_t)k || v->ne[2] != C || v->ne[3] != N) return false;
+        const size_t vo = v->view_offs;
+        const int64_t t = (int64_t)(vo / m2->nb[3]), dy = (int64_t)((vo % m2->nb[3]) / m2->nb[1]), dx = (int64_t)((vo % m2->nb[1]) / 4);
+        if (vo % 4 != 0 || t >= k || seen[(size_t)t] || (vo % m2->nb[3]) >= m2->nb[2] || v->ne[0] != TW - dx || v->ne[1] != TH - dy || v->ne[0] < 1 || v->ne[1] < 1) return false;
+        seen[(size_t)t] = 1;
+        // the canvas view: a rectangle of every plane of R
+        if (!contig(R) || !is_f32(R) || R->ne[2] != C || R->ne[3] != N || cv->nb[0] != 4 || cv->nb[1] != R->nb[1] || cv->nb[2] != R->nb[2] || cv->nb[3] != R->nb[3]) return false;
+        if (R->ne[0] > INT32_MAX || R->ne[1] > INT32_MAX) return false;
+        const size_t co = cv->view_offs;
+        const int64_t y = (int64_t)(co / R->nb[1]), x = (int64_t)((co % R->nb[1]) / 4);
+        if (co % 4 != 0 || co >= R->nb[2] || x + v->ne[0] > R->ne[0] || y + v->ne[1] > R->ne[1] || (const char*)cv->data != (const char*)R->data + co) return false;
+        TileMergeTile d;
+        d.x = (int)x, d.y = (int)y, d.w = (int)v->ne[0], d.h = (int)v->ne[1];
+        d.src = (int64_t)(vo / 4);
+        d.wx  = t * TW + dx;
+        d.wy  = t * TH + dy;
+        found.push_back({jop, d});
+        chain.push_back(jop);
+        last = std::max(last, jop);
+    }
+    if (!R || (int64_t)found.size() != k) return false;
+    chain.push_back(i);
+    chain.push_back(j1);
+    if (!gi.only_noops_between(i, last, chain)) return false;
+    // a tile operand and the canvas share memory: the plain nodes define what that means, not this kernel
+    const size_t rb = ggml_abi_nbytes(R);
+    if (overlaps(R->data, rb, S->data, ggml_abi_nbytes(S)) || overlaps(R->data, rb, wx->data, ggml_abi_nbytes(wx)) || overlaps(R->data, rb, wy->data, ggml_abi_nbytes(wy))) return false;
+    std::sort(found.begin(), found.end(), [](const std::pair<int, TileMergeTile>& p, const std::pair<int, TileMergeTile>& q) { return p.first < q.first; });
+    int x0 = INT32_MAX, y0 = INT32_MAX, x1 = 0, y1 = 0;
+    for (int64_t t = 0; t < k; ++t) {
+        a.t[t] = found[(size_t)t].second;
+        x0 = std::min(x0, a.t[t].x), y0 = std::min(y0, a.t[t].y);
+        x1 = std::max(x1, a.t[t].x + a.t[t].w), y1 = std::max(y1, a.t[t].y + a.t[t].h);
+    }
+    a.k = (int)k, a.bx = x0, a.by = y0, a.bw = x1 - x0, a.bh = y1 - y0;
+    a.planes = (int)(C * N), a.C = (int)C;
+    a.c_row = (int64_t)R->nb[1] / 4, a.c_plane = (int64_t)R->nb[2] / 4, a.c_img = (int64_t)R->nb[3] / 4;
+    a.s_row = TW, a.s_plane = TW * TH, a.s_img = TW * TH * C * k;
+    a.store = store;
+    float* canvas      = (float*)R->data;
+    const float* tiles = (const float*)S->data;
+    const float *wxp = (const float*)wx->data, *wyp = (const float*)wy->data;
+    B.emit_at(last, i, [=](hipStream_t st) { launch_tile_merge(st, canvas, tiles, wxp, wyp, a); });
+    STAT(fused_tile_merge)++;
+    return true;
+}
+
 bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, bool no_redirect = false) {
     Builder B(P, plan, g);
     B.no_redirect = no_redirect;
@@ -3598,6 +3694,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                     ok = plan_manual_attention(B, i, s, chain);
                 }
                 break;
+            case GGML_OP_MUL: ok = plan_tile_merge(B, i, chain); break;
             case GGML_OP_GROUP_NORM: ok = plan_group_norm(B, i, s, chain); break;
             case GGML_OP_NORM:
             case GGML_OP_RMS_NORM: ok = plan_layer_norm(B, i, s, chain); break;
@@ -4124,6 +4221,7 @@ const OptionRow g_option_table[] = {
     OPT(fuse_cat_rows16),
     OPT(fuse_gn_stats),
     OPT(fuse_gn_epilogue),  // unsplit window convs fill a per-channel GroupNorm side band in their epilogue; the statistics pass becomes k_gn_finalize
+    OPT(fuse_tile_merge),  // MUL -> MUL -> { ADD in place | CPY } x k of a VAE tile batch's overlap merge as one gather launch (k_tile_merge)
     OPT(fuse_joint_qkv),
     OPT(fuse_ln_reduce),
     OPT(jit_qimages),

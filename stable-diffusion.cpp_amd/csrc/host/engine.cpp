@@ -543,6 +543,24 @@ struct sdm_ctx_t {
     Runner tae_runner;
     TaeDecoder tae;
     bool tae_ready = false, tae_for_images = false;
+    // VAE tiling (sd_set_vae_tiling): the parameters, and per direction (0 decode, 1 encode) the device-resident state of the last tiled call
+    sdm_tiling_params_t tiling{false, 0, 0, 0.5f, 0.f, 0.f, 0};
+    struct TileState {
+        ggml_context* sctx        = nullptr;
+        ggml_backend_buffer_t buf = nullptr;
+        ggml_gallocr_t merge_galloc = nullptr;
+        ggml_tensor* canvas = nullptr;                  // [W, H, C_out, N]: zeroed per call, blended into by the merge graphs, read back once
+        ggml_tensor* store[2] = {nullptr, nullptr};     // the tile graph's result [TW, TH, C_out, N * k]: full batches / the short last batch
+        ggml_tensor *wx = nullptr, *wy = nullptr;       // ramp vectors of every tile, [TW, 1, 1, T] and [1, TH, 1, T] (they depend on the plan only)
+        std::string key;
+        uint64_t serial = 0;  // part of the tile graph's signature: a cached graph never outlives the store tensor it copies into
+        ~TileState() {
+            if (merge_galloc) ggml_gallocr_free(merge_galloc);
+            if (buf) ggml_backend_buffer_free(buf);
+            if (sctx) ggml_free(sctx);
+        }
+    };
+    std::unique_ptr<TileState> tstate[3];  // decode, encode, sd_tiling_blend
     std::vector<Runner*> runners() {
         std::vector<Runner*> v{&unet_runner, &vae_runner};
         if (tae_ready) v.push_back(&tae_runner);
@@ -1291,13 +1309,257 @@ bool sd_unet_forward_skip_layers(sdm_ctx_t* ctx, const float* x, int w, int h, i
     return unet_forward_skip(ctx, x, w, h, c, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, out, &skip);
 }
 
+// ---- VAE tiling -----------------------------------------------------------------------------------
+// The reference's `--vae-tiling` (sd_tiling_params_t): tile sizes VAE::get_tile_sizes (src/model/vae/vae.hpp:89-116), tile counts and the achieved overlap
+// sd_tiling_calc_tiles (src/core/ggml_extend.hpp:691-739, non-circular branch), order / positions / the shifted last tile process_tiles_2d (:823-951), the
+// blend sd_tensor_merge_2d (:771-821).  Restated here; what differs is WHERE things run: the reference computes one graph per tile and merges on the host,
+// this driver stacks tile_batch tiles along the batch dimension of one graph and blends on the device into a canvas that is read back once.
+static const int TILE_BATCH_DEFAULT = 16;  // the smallest batch within 3 % of the best time at a 256^2 latent (profiles/vae_tiling_probe.txt; DESIGN.md 1, row "VAE tiling")
+static const int TILE_BATCH_MAX     = 32;  // the fused merge kernel's descriptor table (kernels.h: TILE_MERGE_MAX)
+
+struct TileAxis {
+    int tile = 0, overlap = 0;             // latent cells
+    std::vector<std::pair<int, int>> pos;  // (start, skipped leading cells) per tile
+};
+// one axis: `requested` cells per tile over `small` cells with `target` overlap
+static void tiling_axis(int small, int requested, float target, TileAxis& ax) {
+    const int want    = (int)(requested * target);
+    const int stride0 = requested - want;
+    int count         = (small - want) / stride0;
+    const int over    = ((count + 1) * stride0 + want) % small;
+    if (over != stride0 && over <= count * (requested / 2 - want)) ++count;  // room for one more tile without passing an overlap of 0.5
+    float factor = (float)(requested * count - small) / (float)(requested * (count - 1));
+    if (count <= 2) {
+        if (small <= requested) {
+            count  = 1;
+            factor = 0.f;
+        } else {
+            count  = 2;
+            factor = (2 * requested - small) / (float)requested;
+        }
+    }
+    ax.overlap     = (int)(requested * factor);
+    ax.tile        = std::min(requested, small);
+    const int step = std::max(1, requested - ax.overlap);
+    ax.pos.clear();
+    bool last = false;
+    for (int x = 0; x < small && !last; x += step) {
+        int at = x, skip = 0;
+        if (x + ax.tile >= small) {  // the last tile ends at the border; what it repeats of its neighbour is skipped by the merge
+            at   = small - ax.tile;
+            skip = x - at;
+            last = true;
+        }
+        ax.pos.push_back({at, skip});
+    }
+}
+static int tiling_tile_size(int requested, float rel, int64_t latent, float overlap, float encode_factor) {
+    int size = 32;
+    if (rel > 0.f) {
+        if (rel > 1.0) rel = 1 / (rel - rel * overlap + overlap);  // a tile COUNT across the axis
+        size = (int)std::round(latent * rel);
+    } else if (requested >= 4) {
+        size = requested;
+    }
+    size = (int)(size * encode_factor);
+    return std::max(std::min(size, (int)latent), 4);
+}
+struct TilePlan {
+    TileAxis ax, ay;
+    int count() const { return (int)(ax.pos.size() * ay.pos.size()); }
+};
+static bool tiling_plan(int small_w, int small_h, const sdm_tiling_params_t& tp, float encode_factor, TilePlan& pl) {
+    if (small_w < 1 || small_h < 1 || !(encode_factor > 0.f)) return false;
+    const float target = std::max(std::min(tp.target_overlap, 0.5f), 0.0f);
+    tiling_axis(small_w, tiling_tile_size(tp.tile_size_x, tp.rel_size_x, small_w, target, encode_factor), target, pl.ax);
+    tiling_axis(small_h, tiling_tile_size(tp.tile_size_y, tp.rel_size_y, small_h, target, encode_factor), target, pl.ay);
+    return true;
+}
+static inline float tile_ramp(float t) { return t * t * t * (t * (6.0f * t - 15.0f) + 10.0f); }
+// s(min(rise, fall, 1)) for every cell of one tile along one axis, in OUTPUT cells: start / skip / overlap / tile already scaled, `full` = the canvas extent
+static void tile_ramp_vector(float* w, int tile, int start, int skip, int overlap, int full) {
+    for (int i = 0; i < tile; ++i) {
+        if (i < skip) {
+            w[i] = 0.f;  // never read: the merge starts behind the skip
+            continue;
+        }
+        const float rise = (overlap > 0 && start > 0) ? (i - skip) / float(overlap) : 1.f;
+        const float fall = (overlap > 0 && start < full - tile) ? (tile - i) / float(overlap) : 1.f;
+        w[i]             = tile_ramp(std::min(std::min(rise, fall), 1.f));
+    }
+}
+
+// dir 0, decode: in = VAE latents [iw, ih, ic, n] -> out [8 iw, 8 ih, 3, n] (the raw decoder output); dir 1, encode: in = pixels in [-1, 1] [iw, ih, 3, n] ->
+// moments [iw/8, ih/8, 2 zc, n]; dir 2 (sd_tiling_blend): the identity in place of the model, [iw, ih, ic, n] -> the same shape
+static bool vae_tiled(sdm_ctx_t* ctx, int dir, const float* in, int iw, int ih, int ic, int n, float* out) {
+    const bool decode = dir == 0;
+    const int scale = dir == 2 ? 1 : 8;
+    const int sw = decode ? iw : iw / scale, sh = decode ? ih : ih / scale;
+    const int oc = decode ? 3 : dir == 2 ? ic : 2 * (int)ctx->vae.cfg.z_channels;
+    const sdm_tiling_params_t& tp = ctx->tiling;
+    TilePlan pl;
+    if (!tiling_plan(sw, sh, tp, dir == 1 ? 2.0f : 1.0f, pl)) {
+        set_error("VAE tiling: empty input");
+        return false;
+    }
+    const int T  = pl.count(), ntx = (int)pl.ax.pos.size();
+    const int k  = std::max(1, std::min(std::min(tp.tile_batch > 0 ? tp.tile_batch : TILE_BATCH_DEFAULT, TILE_BATCH_MAX), T));
+    const int kl = T % k;  // tiles of the short last batch
+    // in-tile / out-tile extents and the merge geometry in OUTPUT cells (pixels for decode, latent cells for encode)
+    const int itw = pl.ax.tile * (decode ? 1 : scale), ith = pl.ay.tile * (decode ? 1 : scale);
+    const int om  = decode ? scale : 1;
+    const int otw = pl.ax.tile * om, oth = pl.ay.tile * om, ow = sw * om, oh = sh * om, ovx = pl.ax.overlap * om, ovy = pl.ay.overlap * om;
+    const bool blend = ovx > 0 || ovy > 0;  // sd_tensor_merge_2d accumulates when either overlap is positive and stores otherwise
+
+    char key[256];
+    snprintf(key, sizeof(key), "%d %d %d %d %d %d | %d %d %d %d | %d %d", dir, iw, ih, ic, n, k, pl.ax.tile, pl.ay.tile, pl.ax.overlap, pl.ay.overlap, ntx, T);
+    std::unique_ptr<sdm_ctx_t::TileState>& sp = ctx->tstate[dir];
+    if (!sp || sp->key != key) {
+        sp.reset(new sdm_ctx_t::TileState());
+        auto& st = *sp;
+        ggml_init_params ip{0, nullptr, true};
+        st.sctx   = ggml_init(ip);
+        st.canvas = ggml_new_tensor_4d(st.sctx, GGML_TYPE_F32, ow, oh, oc, n);
+        ggml_set_name(st.canvas, "vae_tiling.canvas");
+        if (T >= k) st.store[0] = ggml_new_tensor_4d(st.sctx, GGML_TYPE_F32, otw, oth, oc, (int64_t)n * k);
+        if (kl > 0) st.store[1] = ggml_new_tensor_4d(st.sctx, GGML_TYPE_F32, otw, oth, oc, (int64_t)n * kl);
+        st.wx = ggml_new_tensor_4d(st.sctx, GGML_TYPE_F32, otw, 1, 1, T);
+        st.wy = ggml_new_tensor_4d(st.sctx, GGML_TYPE_F32, 1, oth, 1, T);
+        st.buf = ggml_backend_alloc_ctx_tensors(st.sctx, ctx->backend);
+        if (!st.buf) {
+            sp.reset();
+            set_error("VAE tiling: canvas allocation failed");
+            return false;
+        }
+        // the ramps depend on the plan alone: computed on the host in f32 and uploaded once per state
+        std::vector<float> wx((size_t)otw * T), wy((size_t)oth * T);
+        for (int t = 0; t < T; ++t) {
+            const auto& px = pl.ax.pos[t % ntx];
+            const auto& py = pl.ay.pos[t / ntx];
+            tile_ramp_vector(&wx[(size_t)t * otw], otw, px.first * om, px.second * om, ovx, ow);
+            tile_ramp_vector(&wy[(size_t)t * oth], oth, py.first * om, py.second * om, ovy, oh);
+        }
+        ggml_backend_tensor_set(st.wx, wx.data(), 0, wx.size() * sizeof(float));
+        ggml_backend_tensor_set(st.wy, wy.data(), 0, wy.size() * sizeof(float));
+        st.merge_galloc = ggml_gallocr_new(ggml_backend_get_default_buffer_type(ctx->backend));
+        st.key          = key;
+        static std::atomic<uint64_t> serial{0};
+        st.serial = ++serial;
+    }
+    auto& st = *sp;
+    // process_tiles_2d starts from zeros; the canvas may hold anything (the previous image, NaN): cleared through the buffer interface, never by arithmetic
+    ggml_backend_tensor_memset(st.canvas, 0, 0, ggml_nbytes(st.canvas));
+
+    Runner& r = dir == 1 ? ctx->vae_enc_runner : ctx->vae_runner;
+    const size_t in_plane = (size_t)iw * ih, tile_plane = (size_t)itw * ith;
+    std::vector<std::vector<float>> crops;  // kept until the read-back: uploads and graphs are enqueued, not waited for
+    crops.reserve((size_t)(T + k - 1) / k);
+    for (int t0 = 0; t0 < T; t0 += k) {
+        const int kb       = std::min(k, T - t0);
+        ggml_tensor* store = st.store[kb == k ? 0 : 1];
+        // crop: [itw, ith, ic, n * kb], image-major (index n_i * kb + t): the ramp vectors [., ., 1, kb] then broadcast over the images like any ggml operand
+        crops.emplace_back(tile_plane * ic * n * kb);
+        float* cb = crops.back().data();
+        for (int t = 0; t < kb; ++t) {
+            const int x0 = pl.ax.pos[(t0 + t) % ntx].first * (decode ? 1 : scale), y0 = pl.ay.pos[(t0 + t) / ntx].first * (decode ? 1 : scale);
+            for (int b = 0; b < n; ++b)
+                for (int c = 0; c < ic; ++c) {
+                    const float* src = in + ((size_t)b * ic + c) * in_plane + (size_t)y0 * iw + x0;
+                    float* dst       = cb + (((size_t)b * kb + t) * ic + c) * tile_plane;
+                    for (int y = 0; y < ith; ++y) memcpy(dst + (size_t)y * itw, src + (size_t)y * iw, (size_t)itw * sizeof(float));
+                }
+        }
+        auto build = [&](GraphCtx& g, std::vector<HostInput>& inp) {
+            g.flash_attn    = ctx->params.diffusion_flash_attn;
+            g.conv_direct   = ctx->params.diffusion_conv_direct;
+            ggml_tensor* tz = ggml_new_tensor_4d(g.ctx, GGML_TYPE_F32, itw, ith, ic, (int64_t)n * kb);
+            ggml_set_input(tz);
+            inp.push_back({tz, cb, ggml_nbytes(tz)});
+            ggml_tensor* y = decode ? ctx->vae.forward(g, tz) : dir == 1 ? ctx->vae_enc.forward(g, tz) : tz;
+            return ggml_cpy(g.ctx, y, store);  // tile positions stay out of this graph: every full batch replays one plan
+        };
+        char sig[128];
+        snprintf(sig, sizeof(sig), "vae-tile%d %d %d %d %d*%d s%g #%llu", dir, itw, ith, ic, n, kb, (double)ctx->vae_conv2d_scale, (unsigned long long)st.serial);
+        if (!r.compute(build, nullptr, 0, sig, {cb})) return false;
+
+        // merge graph of this batch: MUL(tiles, wy) -> MUL(., wx) -> per tile, in processing order, ADD in place into the canvas behind the tile's skip
+        ggml_init_params ip{0, nullptr, true};
+        ggml_context* mc = ggml_init(ip);
+        ggml_cgraph* gf  = ggml_new_graph_custom(mc, 64 + 4 * (size_t)kb, false);
+        // (with both overlaps 0 every ramp value is s(1) = 1: the products are the tile's own bits, and the copies below store them like the reference does)
+        ggml_tensor* wy = ggml_view_4d(mc, st.wy, 1, oth, 1, kb, st.wy->nb[1], st.wy->nb[2], st.wy->nb[3], (size_t)t0 * st.wy->nb[3]);
+        ggml_tensor* wx = ggml_view_4d(mc, st.wx, otw, 1, 1, kb, st.wx->nb[1], st.wx->nb[2], st.wx->nb[3], (size_t)t0 * st.wx->nb[3]);
+        ggml_tensor* m  = ggml_mul(mc, ggml_mul(mc, store, wy), wx);
+        for (int t = 0; t < kb; ++t) {
+            const auto& px = pl.ax.pos[(t0 + t) % ntx];
+            const auto& py = pl.ay.pos[(t0 + t) / ntx];
+            const int dx = px.second * om, dy = py.second * om, x = px.first * om, y = py.first * om;
+            ggml_tensor* tv = ggml_view_4d(mc, m, otw - dx, oth - dy, oc, n, m->nb[1], m->nb[2], m->nb[3] * kb, (size_t)t * m->nb[3] + (size_t)dy * m->nb[1] + (size_t)dx * m->nb[0]);
+            ggml_tensor* cv = ggml_view_4d(mc, st.canvas, otw - dx, oth - dy, oc, n, st.canvas->nb[1], st.canvas->nb[2], st.canvas->nb[3],
+                                           (size_t)(y + dy) * st.canvas->nb[1] + (size_t)(x + dx) * st.canvas->nb[0]);
+            ggml_build_forward_expand(gf, blend ? ggml_add_inplace(mc, cv, tv) : ggml_cpy(mc, tv, cv));
+        }
+        bool ok = ggml_gallocr_alloc_graph(st.merge_galloc, gf);
+        if (!ok) set_error("VAE tiling: merge buffer allocation failed");
+        if (ok && g_graph_capture) g_last_graph = describe_graph(gf);
+        // (an installed eval callback sees the merge graphs like every other graph of the context: slices that cut the MUL / MUL / ADD chain run as plain nodes)
+        if (ok && (g_eval_cb ? (enum ggml_status)sdm_backend_graph_compute_with_eval_callback(ctx->backend, gf, g_eval_cb, g_eval_cb_data)
+                             : ggml_backend_graph_compute_async(ctx->backend, gf)) != GGML_STATUS_SUCCESS) {
+            set_error("VAE tiling: merge graph compute failed");
+            ok = false;
+        }
+        ggml_free(mc);
+        if (!ok) return false;
+    }
+    ggml_backend_tensor_get(st.canvas, out, 0, ggml_nbytes(st.canvas));  // synchronises the stream
+    if (r.galloc) ctx->stats.compute_buffer_bytes = ggml_gallocr_get_buffer_size(r.galloc, 0);
+    return true;
+}
+
+void sdm_tiling_params_init(sdm_tiling_params_t* p) { *p = sdm_tiling_params_t{false, 0, 0, 0.5f, 0.f, 0.f, 0}; }
+bool sd_set_vae_tiling(sdm_ctx_t* ctx, const sdm_tiling_params_t* params) {
+    if (params && params->enabled && (params->tile_batch < 0 || !std::isfinite(params->target_overlap) || !std::isfinite(params->rel_size_x) || !std::isfinite(params->rel_size_y))) {
+        set_error("sd_set_vae_tiling: tile_batch must be >= 0 and the overlap / relative sizes finite");
+        return false;
+    }
+    if (params)
+        ctx->tiling = *params;
+    else
+        sdm_tiling_params_init(&ctx->tiling);
+    if (!ctx->tiling.enabled)
+        for (auto& st : ctx->tstate) st.reset();
+    return true;
+}
+bool sd_tiling_blend(sdm_ctx_t* ctx, const float* in, int w, int h, int c, int n, float* out) {
+    if (!ctx->tiling.enabled || w < 1 || h < 1 || c < 1 || n < 1) {
+        set_error("sd_tiling_blend: tiling is off (sd_set_vae_tiling) or the input is empty");
+        return false;
+    }
+    return vae_tiled(ctx, 2, in, w, h, c, n, out);
+}
+int sd_tiling_plan(int small_w, int small_h, const sdm_tiling_params_t* params, float encode_factor, int* tile_size, int* overlap, int* tiles, int tile_capacity) {
+    TilePlan pl;
+    if (!params || !tiling_plan(small_w, small_h, *params, encode_factor, pl)) return -1;
+    if (tile_size) tile_size[0] = pl.ax.tile, tile_size[1] = pl.ay.tile;
+    if (overlap) overlap[0] = pl.ax.overlap, overlap[1] = pl.ay.overlap;
+    const int T = pl.count(), ntx = (int)pl.ax.pos.size();
+    for (int t = 0; tiles && t < T && t < tile_capacity; ++t) {
+        tiles[4 * t + 0] = pl.ax.pos[t % ntx].first;
+        tiles[4 * t + 1] = pl.ay.pos[t / ntx].first;
+        tiles[4 * t + 2] = pl.ax.pos[t % ntx].second;
+        tiles[4 * t + 3] = pl.ay.pos[t / ntx].second;
+    }
+    return T;
+}
+
 // ---- VAE decode ---------------------------------------------------------------------------------
-bool sd_vae_decode(sdm_ctx_t* ctx, const float* latents, int w, int h, int c, int n, float* out_rgb) {
+bool sd_vae_decode_raw(sdm_ctx_t* ctx, const float* latents, int w, int h, int c, int n, float* out_rgb) {
     Runner& r       = ctx->vae_runner;
     const float sf  = ctx->vae.cfg.scale_factor, sh = ctx->vae.cfg.shift_factor;
     const size_t ne = (size_t)w * h * c * n;
     std::vector<float> z(ne);
     for (size_t i = 0; i < ne; ++i) z[i] = latents[i] / sf + sh;  // diffusion_to_vae_latents, auto_encoder_kl.hpp:818-826
+    if (ctx->tiling.enabled) return vae_tiled(ctx, 0, z.data(), w, h, c, n, out_rgb);  // VAE::decode, vae.hpp:182-205
     auto build = [&](GraphCtx& g, std::vector<HostInput>& in) {
         g.flash_attn    = ctx->params.diffusion_flash_attn;
         g.conv_direct   = ctx->params.diffusion_conv_direct;
@@ -1307,10 +1569,14 @@ bool sd_vae_decode(sdm_ctx_t* ctx, const float* latents, int w, int h, int c, in
         return ctx->vae.forward(g, tz);
     };
     const size_t on = (size_t)w * 8 * h * 8 * 3 * n;
-    const double t0 = now_ms();
     char sig[64];
     snprintf(sig, sizeof(sig), "vae %d %d %d %d s%g", w, h, c, n, (double)ctx->vae_conv2d_scale);
-    if (!r.compute(build, out_rgb, on * sizeof(float), sig, {z.data()})) return false;
+    return r.compute(build, out_rgb, on * sizeof(float), sig, {z.data()});
+}
+bool sd_vae_decode(sdm_ctx_t* ctx, const float* latents, int w, int h, int c, int n, float* out_rgb) {
+    const size_t on = (size_t)w * 8 * h * 8 * 3 * n;
+    const double t0 = now_ms();
+    if (!sd_vae_decode_raw(ctx, latents, w, h, c, n, out_rgb)) return false;
     parallel_chunks(on, [&](size_t b, size_t e) {  // scale_tensor_to_0_1, vae.hpp:24-30
         for (size_t i = b; i < e; ++i) {
             const float v = (out_rgb[i] + 1.0f) * 0.5f;
@@ -1366,7 +1632,10 @@ bool sd_vae_encode(sdm_ctx_t* ctx, const float* rgb, int w, int h, int n, uint64
     std::vector<float> moments(2 * per * n);
     char sig[64];
     snprintf(sig, sizeof(sig), "vae-enc %d %d %d s%g", w, h, n, (double)ctx->vae_conv2d_scale);
-    if (!r.compute(build, moments.data(), moments.size() * sizeof(float), sig, {x.data()})) return false;
+    if (ctx->tiling.enabled) {  // VAE::encode, vae.hpp:130-154: the split follows x * 2 - 1; the sample and the latent scaling below see the merged moments
+        if (!vae_tiled(ctx, 1, x.data(), w, h, 3, n, moments.data())) return false;
+    } else if (!r.compute(build, moments.data(), moments.size() * sizeof(float), sig, {x.data()}))
+        return false;
     if (moments_out) memcpy(moments_out, moments.data(), moments.size() * sizeof(float));
     PhiloxRNG rng(seed);
     const std::vector<float> noise = rng.randn((uint32_t)(per * n));  // randn_like(mean): one draw over the whole [lw, lh, zc, n] tensor

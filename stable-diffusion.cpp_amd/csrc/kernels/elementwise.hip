@@ -159,6 +159,83 @@ void launch_binary(hipStream_t s, BinOp op, void* dst, const int64_t dnb[4], con
     }
 }
 
+// ---------------------------------------------------------------------------------------- VAE tile merge
+// V = 4: every rectangle, the bounding box and every stride / offset are multiples of 4 cells and the pointers 16-byte aligned (decode: positions and skips are
+// multiples of 8 pixels), so a float4 group lies inside or outside a tile as a whole; V = 1: arbitrary offsets (encode merges at latent resolution).
+template <int V>
+__global__ void k_tile_merge(float* __restrict__ canvas, const float* __restrict__ tiles, const float* __restrict__ wx, const float* __restrict__ wy,
+                             const TileMergeArgs a) {
+    // hipcc contracts a + b * c into one fused operation by default, and this toolchain's __fmul_rn / __fadd_rn are plain operators compiled under that default:
+    // the pragma is what keeps the three roundings of old + ((new * s_y) * s_x) apart, so that the launch gives the bits of the MUL / MUL / ADD nodes it replaces
+#pragma clang fp contract(off)
+    const int bwv      = a.bw / V;
+    const int64_t ntot = (int64_t)bwv * a.bh * a.planes;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < ntot; i += (int64_t)gridDim.x * blockDim.x) {
+        const int x       = a.bx + (int)(i % bwv) * V;
+        const int y       = a.by + (int)((i / bwv) % a.bh);
+        const int plane   = (int)(i / ((int64_t)bwv * a.bh));
+        const int c       = plane % a.C, img = plane / a.C;
+        float* cp         = canvas + (int64_t)img * a.c_img + (int64_t)c * a.c_plane + (int64_t)y * a.c_row + x;
+        const int64_t sp  = (int64_t)img * a.s_img + (int64_t)c * a.s_plane;
+        float acc[V];
+        bool covered = false, loaded = false;
+        for (int t = 0; t < a.k; ++t) {
+            const TileMergeTile& d = a.t[t];
+            const int tx = x - d.x, ty = y - d.y;
+            if (tx < 0 || ty < 0 || tx >= d.w || ty >= d.h) continue;
+            if (!a.store && !loaded) {
+                if constexpr (V == 4) {
+                    const float4 o = *(const float4*)cp;
+                    acc[0] = o.x, acc[1] = o.y, acc[2] = o.z, acc[3] = o.w;
+                } else {
+                    acc[0] = *cp;
+                }
+                loaded = true;
+            }
+            covered            = true;
+            const float* src   = tiles + d.src + sp + (int64_t)ty * a.s_row + tx;
+            const float fy     = wy[d.wy + ty];
+            float v[V], fx[V];
+            if constexpr (V == 4) {
+                const float4 q = *(const float4*)src, r = *(const float4*)(wx + d.wx + tx);
+                v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+                fx[0] = r.x, fx[1] = r.y, fx[2] = r.z, fx[3] = r.w;
+            } else {
+                v[0]  = *src;
+                fx[0] = wx[d.wx + tx];
+            }
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const float m = (v[e] * fy) * fx[e];  // plain operators: they take this function's contraction state (the header's __fmul_rn / __fadd_rn carry their own)
+                acc[e]        = a.store ? m : acc[e] + m;
+            }
+        }
+        if (!covered) continue;
+        if constexpr (V == 4)
+            *(float4*)cp = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        else
+            *cp = acc[0];
+    }
+}
+
+void launch_tile_merge(hipStream_t s, float* canvas, const float* tiles, const float* wx, const float* wy, const TileMergeArgs& a) {
+    double cells = 0;
+    bool v4      = ((((uintptr_t)canvas | (uintptr_t)tiles | (uintptr_t)wx) & 15) == 0) && a.bx % 4 == 0 && a.bw % 4 == 0 && a.c_row % 4 == 0 && a.c_plane % 4 == 0 &&
+              a.c_img % 4 == 0 && a.s_row % 4 == 0 && a.s_plane % 4 == 0 && a.s_img % 4 == 0;
+    for (int t = 0; t < a.k; ++t) {
+        const TileMergeTile& d = a.t[t];
+        cells += (double)d.w * d.h;
+        v4 = v4 && d.x % 4 == 0 && d.w % 4 == 0 && d.src % 4 == 0 && d.wx % 4 == 0;
+    }
+    KScope ks_(s, KF_BINARY, 0.0, cells * a.planes * 4.0 + (double)a.bw * a.bh * a.planes * 8.0);  // read every tile cell once, read + write the box of the canvas
+    const int64_t n = (int64_t)(a.bw / (v4 ? 4 : 1)) * a.bh * a.planes;
+    if (n <= 0) return;
+    if (v4)
+        k_tile_merge<4><<<grid_for(n, 256), 256, 0, s>>>(canvas, tiles, wx, wy, a);
+    else
+        k_tile_merge<1><<<grid_for(n, 256), 256, 0, s>>>(canvas, tiles, wx, wy, a);
+}
+
 // ---------------------------------------------------------------------------------------- unary
 template <int OP>
 __global__ void k_unary(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {

@@ -21,6 +21,26 @@ enum UnOp { UN_SILU = 0, UN_GELU = 1, UN_GELU_QUICK = 2, UN_SIGMOID = 3, UN_TANH
 // ---- elementwise.hip --------------------------------------------------------------------------------
 // dst = a (op) broadcast(b); a/dst f32 with arbitrary strides, b f32 broadcast by modulo on every dim
 void launch_binary(hipStream_t s, BinOp op, void* dst, const int64_t dnb[4], const View4& a, const View4& b);
+// Overlap merge of one VAE tile batch (planner: plan_tile_merge; the reference's sd_tensor_merge_2d, src/core/ggml_extend.hpp:771-821, for up to TILE_MERGE_MAX tiles
+// in ONE launch): canvas[y][x] (+)= (tile[ty][tx] * wy[ty]) * wx[tx] for every tile of the batch that covers the cell, in the batch's order, each operation rounded
+// separately — the bits of MUL -> MUL -> ADD-in-place per tile.  Gather form: a thread owns canvas cells of the batch's bounding box, walks the descriptor table and
+// touches the canvas once.  All offsets / strides in f32 ELEMENTS.
+constexpr int TILE_MERGE_MAX = 32;
+struct TileMergeTile {
+    int x, y, w, h;   // covered canvas rectangle (behind the tile's skip)
+    int64_t src;      // tiles: element of (x, y) in plane 0 of image 0 of this tile
+    int64_t wx, wy;   // ramps: element of column x / of row y
+};
+struct TileMergeArgs {
+    TileMergeTile t[TILE_MERGE_MAX];
+    int k;
+    int bx, by, bw, bh;               // bounding box of the rectangles
+    int planes, C;                    // C * N planes, channels per image
+    int64_t c_row, c_plane, c_img;    // canvas strides
+    int64_t s_row, s_plane, s_img;    // tile strides (s_img: between the images of ONE tile)
+    int store;                        // 1: canvas = value (both overlaps 0: the last covering tile wins, like successive copies); 0: canvas += value
+};
+void launch_tile_merge(hipStream_t s, float* canvas, const float* tiles, const float* wx, const float* wy, const TileMergeArgs& a);
 void launch_unary(hipStream_t s, UnOp op, float* dst, const float* src, int64_t n);
 void launch_scale(hipStream_t s, float* dst, const float* src, int64_t n, float scale, float bias);
 // generic strided copy with conversion between f32/f16/bf16 (logical element order preserved)
