@@ -188,6 +188,16 @@ GGML_MI355X_API int ggml_backend_mi355x_calibrate(struct ggml_backend_mi355x_cal
 /* the hipStream_t every graph of this backend instance is enqueued on (graph_compute_async, set/get_tensor_async): a caller that touches a
  * tensor's device memory between two graphs (the CFG-pair all-reduce, sd_set_pair_exchange) orders its work on this stream */
 GGML_MI355X_API void* ggml_backend_mi355x_get_stream(ggml_backend_t backend);
+/* The step caches' device passes (EasyCache / UCache on the device-resident sampler; kernels/step_cache.hip), enqueued on that stream between two graphs.  All
+ * pointers are DEVICE addresses of f32 data; `stats` is 4 floats.  Both sums are deterministic (fixed grid, per-workgroup partials added in a fixed order by a second
+ * one-workgroup launch, no floating-point atomics; at most 128 additions deep).  false: bad arguments or a size beyond that depth bound — nothing was enqueued.
+ *   probe : stats[0] = sum over n of |x * c_in - prev_in|, the product rounded to f32 once (the step graph's MUL)
+ *   record: in / prev_in / prev_out [per, nb], out / diff [per, k, nb] with k = 1 or 2 conditions adjacent per image, condition 0 first:
+ *           diff_j = out_j - in, prev_in = in, prev_out = out_0, stats[1] = sum |out_0 - prev_out before this call| (0 and prev_out not read unless has_prev_out),
+ *           stats[2] = sum |out_0| */
+GGML_MI355X_API bool ggml_backend_mi355x_step_cache_probe(ggml_backend_t backend, const float* x, float c_in, const float* prev_in, int64_t n, float* stats);
+GGML_MI355X_API bool ggml_backend_mi355x_step_cache_record(ggml_backend_t backend, const float* in, const float* out, float* prev_in, float* prev_out, float* diff, int64_t per,
+                                                           int k, int64_t nb, bool has_prev_out, float* stats);
 /* path of the HIP runtime library this plug-in is bound to, and hipSetDevice through it (for companions that must share its streams: RCCL) */
 GGML_MI355X_API const char* ggml_backend_mi355x_hip_library(void);
 GGML_MI355X_API int ggml_backend_mi355x_set_device(int hip_device);

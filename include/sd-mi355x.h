@@ -268,6 +268,54 @@ SD_API bool sd_sample_latents(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, flo
 SD_API bool sdm_generate_image(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, sdm_image_t** images_out, int* num_images_out);
 SD_API void sdm_free_images(sdm_image_t* images, int num_images);
 
+/* ---- step caches: the reference's `--cache-mode easycache` (DiT families) and `--cache-mode ucache` (UNet families) -------------------------------------------
+ * sd_cache_params_t of include/stable-diffusion.h restricted to the two condition-level caches (src/runtime/easycache.hpp, ucache.hpp, sample-cache.cpp): a denoise
+ * step whose model output can be predicted from the previous computed step (output = input + (previous output - previous input)) is not run.  The state machines
+ * are restated in csrc/host/step_cache.hpp.  DBCache / TaylorSeer / CacheDIT / Spectrum reach into the model's blocks and are not implemented.  Mode values as in
+ * the reference's sd_cache_mode_t. */
+enum sdm_cache_mode_t { SDM_CACHE_DISABLED = 0, SDM_CACHE_EASYCACHE = 1, SDM_CACHE_UCACHE = 2 };
+typedef struct {
+    enum sdm_cache_mode_t mode;
+    float reuse_threshold;       /* INFINITY = the mode's default (EasyCache 0.2, UCache 1.0); negative values count as 0 */
+    float start_percent;         /* the cache may act on steps inside (start_percent, end_percent) of the trajectory; an invalid range disables it */
+    float end_percent;
+    float error_decay_rate;      /* UCache, clamped to [0, 1] */
+    bool use_relative_threshold; /* UCache */
+    bool reset_error_on_compute; /* UCache */
+} sdm_cache_params_t;
+SD_API void sdm_cache_params_init(sdm_cache_params_t* p); /* sd_cache_params_init: DISABLED, INFINITY, 0.15, 0.95, 1.0, true, true */
+/* Context state like sd_set_vae_tiling; NULL or SDM_CACHE_DISABLED turns it off (the sampler paths are then exactly the uncached ones).  Honoured by
+ * sd_sample_latents / sdm_generate_image with every sample method, on the host loop and on the device-resident sampler.  A mode that does not fit the model family
+ * or an invalid percent range is NOT an error: the trajectory runs uncached like the reference's, and sd_step_cache_status says why.  One decision per device
+ * group: with device_batch > 1 the three means run over the whole group (the reference samples one image at a time).  false (sd_last_error): a NaN parameter.
+ * Refused at sampling time (sd_last_error): an armed cache together with skip-layer guidance, or with a CFG-pair exchange (sd_set_pair_exchange*). */
+SD_API bool sd_set_step_cache(sdm_ctx_t* ctx, const sdm_cache_params_t* params);
+/* one record per denoise call (model evaluation request of the sampler) of the last trajectory — the last device group of the last sd_sample_latents */
+typedef struct {
+    int step;            /* what the sampler handed the denoise call: i + 1, negated for the first stage of the two-stage methods (never cached) */
+    float sigma;
+    bool active;         /* inside the cache's sigma window */
+    bool skipped;        /* the model was not run: outputs were rebuilt from the stored differences */
+    float input_change;  /* mean |input - previous computed input| (0 when not measured) */
+    float output_change; /* mean |output - previous computed output| of the anchor condition (computed steps; 0 when there was no previous output) */
+    float output_norm;   /* mean |output| of the anchor condition (computed steps) */
+    float rate;          /* the estimated output change of this step the decision added (0 when no decision was due) */
+    float accumulated;   /* EasyCache: cumulative change rate, UCache: accumulated error — after adding `rate`, before any reset */
+    float threshold;     /* the effective threshold `accumulated` was compared with */
+} sdm_cache_step_t;
+SD_API int sd_step_cache_trace(sdm_ctx_t* ctx, sdm_cache_step_t* out, int capacity); /* returns the record count (also with capacity 0); at most `capacity` are written */
+SD_API const char* sd_step_cache_status(sdm_ctx_t* ctx);                             /* "easycache" / "ucache" when the last trajectory was armed, else why not */
+/* whether the device-resident sampler's two cache passes run as the backend's HIP kernels (true) or as the host restatement of a backend without those exports (false);
+ * an MI355X backend that lacks the exports is an error at sampling time, never a quiet fall-back */
+SD_API bool sd_step_cache_device_passes(sdm_ctx_t* ctx);
+SD_API float sd_t_to_sigma(sdm_ctx_t* ctx, float t);                                 /* the context's denoiser (what the caches' percent_to_sigma goes through) */
+/* The two device passes of the device-resident sampler's cache on caller memory (tests): uploads, runs probe and record through the path the sampler uses (the
+ * backend's exports "ggml_backend_mi355x_step_cache_probe" / "_record", or the host restatement on a backend without them), reads back.  in / prev_in / prev_out:
+ * [n, nb]; out / diff_out: [n, k, nb] with k = 1 or 2.  stats[0] = sum |in * c_in - prev_in|, stats[1] = sum |out_0 - prev_out| (prev_out NULL: never written, 0),
+ * stats[2] = sum |out_0|; diff_out_j = out_j - in, prev_in_out = in, prev_out_out = out_0. */
+SD_API bool sd_step_cache_kernels(sdm_ctx_t* ctx, const float* in, const float* out, const float* prev_in, const float* prev_out, int64_t n, int k, int nb, float c_in,
+                                  float* stats, float* diff_out, float* prev_in_out, float* prev_out_out);
+
 /* ---- host-side sampler pieces exposed for known-answer tests ---- */
 SD_API void sd_philox_randn(uint64_t seed, uint32_t offset, uint32_t n, float* out); /* rng_philox.hpp:101-122 */
 SD_API void sd_philox_uint32(uint64_t seed, uint32_t offset, uint32_t n, uint32_t* out /* 4*n words */); /* the integer stage alone: philox4_32, rng_philox.hpp:63-77 */
@@ -355,6 +403,7 @@ typedef struct {
      * uploads + graph_compute (which contains the device time on the synchronous path, only the enqueue cost on the device-resident path) */
     double host_build_ms, host_alloc_ms, host_submit_ms;
     int64_t graph_cache_hits; /* denoiser calls that replayed the cached graph (same shapes as the previous call) instead of rebuilding it */
+    int64_t steps_skipped;    /* denoise steps the step cache (sd_set_step_cache) did not run in the last sd_sample_latents / sdm_generate_image, over all device groups; after a call that failed it counts the groups that had finished only */
 } sd_stats_t;
 SD_API void sd_get_stats(sdm_ctx_t* ctx, sd_stats_t* out);
 /* ---- text encoders + conditioner --------------------------------------------------------

@@ -37,6 +37,8 @@ TCD, RES_MULTISTEP, RES_2S, ER_SDE, EULER_CFG_PP, EULER_A_CFG_PP, EULER_GE, DPMP
 SAMPLE_METHOD_DEFAULT = 21   # Euler for the DiT families, Euler-A otherwise (sd_get_default_sample_method)
 SCHED_DISCRETE, SCHED_KARRAS, SCHED_EXPONENTIAL, SCHED_AYS, SCHED_GITS, SCHED_SGM_UNIFORM, SCHED_SIMPLE, SCHED_SMOOTHSTEP, SCHED_KL_OPTIMAL, SCHED_LCM = range(10)
 SCHED_BONG_TANGENT, SCHED_FLUX, SCHED_BETA, SCHEDULER_DEFAULT = 10, 14, 15, 16   # DEFAULT: LCM for the LCM method, SIMPLE for DDIM trailing, FLUX for FLUX, DISCRETE otherwise (sd_get_default_scheduler)
+# sdm_cache_mode_t (include/sd-mi355x.h): the reference's sd_cache_mode_t values
+CACHE_DISABLED, CACHE_EASYCACHE, CACHE_UCACHE = 0, 1, 2
 
 
 class EngineError(RuntimeError):
@@ -119,7 +121,19 @@ class SdStats(C.Structure):
     _fields_ = [("last_sample_ms", C.c_double), ("last_decode_ms", C.c_double), ("unet_calls", C.c_int64),
                 ("graph_nodes", C.c_int64), ("compute_buffer_bytes", C.c_size_t), ("weight_bytes", C.c_size_t),
                 ("host_build_ms", C.c_double), ("host_alloc_ms", C.c_double), ("host_submit_ms", C.c_double),
-                ("graph_cache_hits", C.c_int64)]
+                ("graph_cache_hits", C.c_int64), ("steps_skipped", C.c_int64)]
+
+
+class SdCacheParams(C.Structure):
+    """sdm_cache_params_t (include/sd-mi355x.h)"""
+    _fields_ = [("mode", C.c_int), ("reuse_threshold", C.c_float), ("start_percent", C.c_float), ("end_percent", C.c_float), ("error_decay_rate", C.c_float),
+                ("use_relative_threshold", C.c_bool), ("reset_error_on_compute", C.c_bool)]
+
+
+class SdCacheStep(C.Structure):
+    """sdm_cache_step_t (include/sd-mi355x.h)"""
+    _fields_ = [("step", C.c_int), ("sigma", C.c_float), ("active", C.c_bool), ("skipped", C.c_bool), ("input_change", C.c_float), ("output_change", C.c_float),
+                ("output_norm", C.c_float), ("rate", C.c_float), ("accumulated", C.c_float), ("threshold", C.c_float)]
 
 
 _lib = None
@@ -685,6 +699,73 @@ class Engine:
             ok = L.sd_set_vae_tiling(self._ctx, C.byref(p))
         if not ok:
             raise EngineError("sd_set_vae_tiling failed: " + L.sd_last_error().decode())
+
+    # ---- step caches (EasyCache / UCache) ----
+    def set_step_cache(self, mode: int = CACHE_DISABLED, reuse_threshold: float = float("inf"), start_percent: float = 0.15, end_percent: float = 0.95,
+                       error_decay_rate: float = 1.0, use_relative_threshold: bool = True, reset_error_on_compute: bool = True) -> None:
+        """sd_set_step_cache — the reference's `--cache-mode easycache` (DiT families) / `ucache` (UNet families): sample_latents / generate_image skip denoise steps
+        whose output the previous computed step predicts.  mode None or CACHE_DISABLED turns it off.  A mode that does not fit the family or an invalid percent
+        range runs uncached (step_cache_status says why)."""
+        L = lib()
+        L.sd_set_step_cache.argtypes = [C.c_void_p, C.POINTER(SdCacheParams)]
+        L.sd_set_step_cache.restype = C.c_bool
+        if mode is None:
+            ok = L.sd_set_step_cache(self._ctx, None)
+        else:
+            p = SdCacheParams(int(mode), reuse_threshold, start_percent, end_percent, error_decay_rate, bool(use_relative_threshold), bool(reset_error_on_compute))
+            ok = L.sd_set_step_cache(self._ctx, C.byref(p))
+        if not ok:
+            raise EngineError("sd_set_step_cache failed: " + L.sd_last_error().decode())
+
+    def step_cache_trace(self) -> list:
+        """sd_step_cache_trace: one dict per denoise call of the last trajectory (the last device group of the last sample_latents / generate_image)."""
+        L = lib()
+        L.sd_step_cache_trace.argtypes = [C.c_void_p, C.POINTER(SdCacheStep), C.c_int]
+        L.sd_step_cache_trace.restype = C.c_int
+        n = L.sd_step_cache_trace(self._ctx, None, 0)
+        buf = (SdCacheStep * max(n, 1))()
+        n = min(n, L.sd_step_cache_trace(self._ctx, buf, n))
+        return [{f[0]: getattr(buf[i], f[0]) for f in SdCacheStep._fields_} for i in range(n)]
+
+    def step_cache_status(self) -> str:
+        """sd_step_cache_status: "easycache" / "ucache" when the last trajectory was armed, otherwise the reason it ran uncached."""
+        L = lib()
+        L.sd_step_cache_status.argtypes = [C.c_void_p]
+        L.sd_step_cache_status.restype = C.c_char_p
+        return L.sd_step_cache_status(self._ctx).decode()
+
+    def step_cache_device_passes(self) -> bool:
+        """sd_step_cache_device_passes: True when the device sampler's probe / record passes are the backend's HIP kernels, False on a backend without them (host restatement)."""
+        L = lib()
+        L.sd_step_cache_device_passes.argtypes = [C.c_void_p]
+        L.sd_step_cache_device_passes.restype = C.c_bool
+        return bool(L.sd_step_cache_device_passes(self._ctx))
+
+    def t_to_sigma(self, t: float) -> float:
+        """sd_t_to_sigma: the context's denoiser, as the caches' percent_to_sigma uses it (after a trajectory: with that trajectory's flow shift)."""
+        L = lib()
+        L.sd_t_to_sigma.argtypes = [C.c_void_p, C.c_float]
+        L.sd_t_to_sigma.restype = C.c_float
+        return float(L.sd_t_to_sigma(self._ctx, float(t)))
+
+    def step_cache_kernels(self, inp: np.ndarray, out: np.ndarray, prev_in: np.ndarray, prev_out: np.ndarray | None, c_in: float = 1.0):
+        """sd_step_cache_kernels: the device sampler's probe and record passes on caller arrays.  inp / prev_in / prev_out [nb, n], out [nb, k, n] (k = 1 or 2) ->
+        (stats[3], diff [nb, k, n], prev_in' [nb, n], prev_out' [nb, n]) with stats = (sum |inp * c_in - prev_in|, sum |out_0 - prev_out| or 0 without prev_out,
+        sum |out_0|), diff_j = out_j - inp, prev_in' = inp, prev_out' = out_0."""
+        a, o, pi = _f32(inp), _f32(out), _f32(prev_in)
+        po = None if prev_out is None else _f32(prev_out)
+        nb, n = a.shape
+        k = o.shape[1]
+        assert o.shape == (nb, k, n) and pi.shape == a.shape and (po is None or po.shape == a.shape)
+        stats = np.zeros(3, dtype=np.float32)
+        diff, pin2, pout2 = np.empty_like(o), np.empty_like(a), np.empty_like(a)
+        L = lib()
+        L.sd_step_cache_kernels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+        L.sd_step_cache_kernels.restype = C.c_bool
+        if not L.sd_step_cache_kernels(self._ctx, _fptr(a), _fptr(o), _fptr(pi), _fptr(po), n, k, nb, float(c_in), _fptr(stats), _fptr(diff), _fptr(pin2), _fptr(pout2)):
+            raise EngineError("sd_step_cache_kernels failed: " + L.sd_last_error().decode())
+        return stats, diff, pin2, pout2
 
     def vae_encode(self, rgb: np.ndarray, seed: int = 42, return_moments: bool = False):
         """sd_vae_encode: rgb [N,3,H,W] in [0,1] -> diffusion latents [N,zc,H/8,W/8] sampled with Philox(seed) (+ the moments [N,2*zc,H/8,W/8] the graph produced)."""

@@ -153,6 +153,7 @@ struct BackendCtx {
     hipStream_t stream;
     Planner* planner;
     UploadStaging up;
+    float* step_cache_partial = nullptr;  // per-workgroup partial sums of the step-cache passes (kernels/step_cache.hip), made on first use
 };
 static const char* be_get_name(ggml_backend_t b) { return ((BackendCtx*)b->context)->dev->name.c_str(); }
 static void be_free(ggml_backend_t b) {
@@ -160,6 +161,7 @@ static void be_free(ggml_backend_t b) {
     HIP_OK(hipSetDevice(c->dev->id));
     HIP_OK(hipStreamSynchronize(c->stream));
     planner_destroy(c->planner);
+    if (c->step_cache_partial) (void)hipFree(c->step_cache_partial);
     if (c->up.base) {
         (void)hipEventDestroy(c->up.done[0]);
         (void)hipEventDestroy(c->up.done[1]);
@@ -282,6 +284,8 @@ static void* reg_get_proc(ggml_backend_reg_t, const char* name) {
     if (strcmp(name, "ggml_backend_mi355x_get_kernel_timings") == 0) return (void*)ggml_backend_mi355x_get_kernel_timings;
     if (strcmp(name, "ggml_backend_mi355x_kernel_timing_enable_mask") == 0) return (void*)ggml_backend_mi355x_kernel_timing_enable_mask;
     if (strcmp(name, "ggml_backend_mi355x_get_stream") == 0) return (void*)ggml_backend_mi355x_get_stream;
+    if (strcmp(name, "ggml_backend_mi355x_step_cache_probe") == 0) return (void*)ggml_backend_mi355x_step_cache_probe;
+    if (strcmp(name, "ggml_backend_mi355x_step_cache_record") == 0) return (void*)ggml_backend_mi355x_step_cache_record;
     if (strcmp(name, "ggml_backend_mi355x_hip_library") == 0) return (void*)ggml_backend_mi355x_hip_library;
     if (strcmp(name, "ggml_backend_mi355x_set_device") == 0) return (void*)ggml_backend_mi355x_set_device;
     if (strcmp(name, "ggml_backend_mi355x_get_device") == 0) return (void*)ggml_backend_mi355x_get_device;
@@ -469,6 +473,29 @@ GGML_MI355X_API void ggml_backend_mi355x_kernel_timing_enable(int enable) { mi35
 GGML_MI355X_API void ggml_backend_mi355x_kernel_timing_enable_mask(uint32_t family_mask) { mi355x::ktime_enable(family_mask); }
 GGML_MI355X_API void* ggml_backend_mi355x_get_stream(ggml_backend_t backend) {
     return backend ? (void*)((mi355x::BackendCtx*)backend->context)->stream : nullptr;
+}
+// The step caches' device passes (include/ggml-mi355x.h): enqueued on the backend's stream between two graphs, like the CFG-pair exchange
+static float* step_cache_scratch(mi355x::BackendCtx* c) {
+    if (!c->step_cache_partial && hipMalloc((void**)&c->step_cache_partial, mi355x::step_cache_partial_bytes()) != hipSuccess) {
+        (void)hipGetLastError();
+        c->step_cache_partial = nullptr;
+    }
+    return c->step_cache_partial;
+}
+GGML_MI355X_API bool ggml_backend_mi355x_step_cache_probe(ggml_backend_t backend, const float* x, float c_in, const float* prev_in, int64_t n, float* stats) {
+    if (!backend || !x || !prev_in || !stats) return false;
+    mi355x::BackendCtx* c = (mi355x::BackendCtx*)backend->context;
+    if (hipSetDevice(c->dev->id) != hipSuccess) return false;
+    float* partial = step_cache_scratch(c);
+    return partial && mi355x::launch_step_cache_probe(c->stream, x, c_in, prev_in, n, partial, stats);
+}
+GGML_MI355X_API bool ggml_backend_mi355x_step_cache_record(ggml_backend_t backend, const float* in, const float* out, float* prev_in, float* prev_out, float* diff, int64_t per,
+                                                           int k, int64_t nb, bool has_prev_out, float* stats) {
+    if (!backend || !in || !out || !prev_in || !prev_out || !diff || !stats) return false;
+    mi355x::BackendCtx* c = (mi355x::BackendCtx*)backend->context;
+    if (hipSetDevice(c->dev->id) != hipSuccess) return false;
+    float* partial = step_cache_scratch(c);
+    return partial && mi355x::launch_step_cache_record(c->stream, in, out, prev_in, prev_out, diff, per, k, nb, has_prev_out, partial, stats + 1);
 }
 // The HIP runtime THIS plug-in is bound to (a process may hold a second copy, e.g. the one a torch wheel bundles): a companion library that
 // must share streams with the backend — RCCL for the native CFG-pair exchange — is loaded from the same directory.

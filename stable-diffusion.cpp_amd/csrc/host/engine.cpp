@@ -31,6 +31,7 @@
 #include "models.hpp"
 #include "conditioner.hpp"
 #include "sampler.hpp"
+#include "step_cache.hpp"
 #include "model_io.hpp"
 #include "torch_ckpt_io.hpp"
 #include "name_conversion.hpp"
@@ -521,7 +522,22 @@ struct sdm_ctx_t {
         ggml_backend_buffer_t buf = nullptr;
         ggml_tensor *x = nullptr, *noise = nullptr, *eps = nullptr;
         int64_t W = 0, H = 0, C = 0, N = 0;
+        // step cache (sd_set_step_cache), made only when a cache is armed: the recorded input / outputs of the last computed step, what the anchor saw the
+        // step before, the stored differences and the three sums (+ 1 spare) the host reads back once per active step
+        struct Cache {
+            ggml_context* cctx        = nullptr;
+            ggml_backend_buffer_t buf = nullptr;
+            ggml_tensor *in = nullptr, *out = nullptr, *prev_in = nullptr, *prev_out = nullptr, *diff = nullptr, *stats = nullptr;
+            int k = 0;
+            uint64_t serial = 0;  // part of the recording / skip-step graphs' signatures: a cached graph never outlives the tensors it names
+            ~Cache() {
+                if (buf) ggml_backend_buffer_free(buf);
+                if (cctx) ggml_free(cctx);
+            }
+        };
+        std::unique_ptr<Cache> cache;
         ~SamplerState() {
+            cache.reset();
             if (buf) ggml_backend_buffer_free(buf);
             if (sctx) ggml_free(sctx);
         }
@@ -532,6 +548,20 @@ struct sdm_ctx_t {
     void* pair_user             = nullptr;
     int pair_branch             = 0;
     Runner pair_runner;  // the sampler-update graph behind the exchange keeps its own cached graph + compute buffer
+    // step caches (sd_set_step_cache; csrc/host/step_cache.hpp): the request, the runtime of the current / last trajectory, and the runner of the device-resident
+    // sampler's skip-step graph (its own cached graph: alternating with the step graph must not rebuild either)
+    sdm_cache_params_t cache_params{SDM_CACHE_DISABLED, INFINITY, 0.15f, 0.95f, 1.0f, true, true};
+    StepCacheRuntime step_cache;
+    Runner skip_runner;
+    float t_to_sigma(float t) const { return is_flux ? flux_denoiser.t_to_sigma(t) : (is_dit ? flow_denoiser.t_to_sigma(t) : denoiser.t_to_sigma(t)); }
+    // whether the request would arm a cache on this family (init_sample_cache_runtime's tests that do not need the ladder)
+    bool step_cache_would_arm() const {
+        if (!StepCacheRuntime::has_valid_cache_percent_range(cache_params)) return false;
+        return (cache_params.mode == SDM_CACHE_EASYCACHE && is_dit) || (cache_params.mode == SDM_CACHE_UCACHE && !is_dit);
+    }
+    void step_cache_begin_trajectory(const std::vector<float>& sigmas) {
+        step_cache.init(&cache_params, is_dit, !is_dit, [this](float t) { return t_to_sigma(t); }, sigmas);
+    }
     std::vector<float> pe_cache;  // FLUX rotary table of the last (h, w, n_tokens)
     int pe_h = 0, pe_w = 0;
     int64_t pe_tokens = 0;
@@ -692,6 +722,8 @@ sdm_ctx_t* sdm_new_ctx(const sdm_ctx_params_t* params) {
         ctx->unet.init(ctx->unet_runner.ps, "model.diffusion_model.", ucfg);  // prefix: stable-diffusion.cpp:1337
     ctx->pair_runner.backend       = backend;
     ctx->pair_runner.graph_size    = 256;
+    ctx->skip_runner.backend       = backend;
+    ctx->skip_runner.graph_size    = 256;
     ctx->vae_runner.backend        = backend;
     ctx->vae_runner.ps.linear_type = GGML_TYPE_F16;
     ctx->vae_runner.graph_size     = 20480;
@@ -1774,6 +1806,11 @@ struct HostDenoise {
     int n_sigmas = 0;  // sigmas.size() of the trajectory (GuidanceInput::schedule_size)
     std::vector<std::vector<float>> apg_momentum;  // adaptive projected guidance: one momentum buffer per image
     std::vector<float> x2, o2, t2, c2, y2;  // staging of the fused (cond, uncond) pair
+    // step cache (csrc/host/step_cache.hpp): every model forward is wrapped like the reference's run_condition (stable-diffusion.cpp:2779-2795), cond = 0 and
+    // uncond = 1; the input is `noised` and the output the model output over the whole device group (nb = 1: the reference's tensors; nb > 1: the means run over
+    // the group and there is one decision for all its images)
+    StepCacheRuntime* sc = nullptr;
+    HostStepCacheStore sc_store;
     HostDenoise(sdm_ctx_t* ctx_, const sdm_img_gen_params_t* p_, int W_, int H_, int C_, int nb_)
         : ctx(ctx_), p(p_), W(W_), H(H_), C(C_), nb(nb_), per((size_t)W_ * H_ * C_), use_cfg(p_->sample_params.txt_cfg != 1.0f && p_->uncond.c_crossattn != nullptr),
           noised(per * nb_), cond_out(per * nb_), uncond_out(per * nb_), ts(nb_) {}
@@ -1788,9 +1825,14 @@ struct HostDenoise {
         step_scalings(ctx, sp, sigma, c_skip, c_out, c_in, t);
         for (int b = 0; b < nb; ++b) ts[b] = t;
         for (size_t k = 0; k < n; ++k) noised[k] = x[k] * c_in;  // stable-diffusion.cpp:2662
+        const bool cached = sc && sc->armed();
+        if (cached) sc->begin_call(step, sigma);  // SampleStepCacheDispatcher step_cache(cache_runtime, step, sigma), stable-diffusion.cpp:2688
         auto run = [&](const sd_condition_t& cd, float* dst) {
-            return sd_unet_forward(ctx, noised.data(), W, H, C, nb, ts.data(), cd.c_crossattn, cd.ctx_dim, cd.n_tokens, 1,
-                                   cd.c_vector, cd.vector_dim, 1, dst);
+            const int cond_id = &cd == &p->uncond ? 1 : 0;
+            if (cached && sc_store.before_condition(*sc, cond_id, noised.data(), dst, n)) return true;
+            if (!sd_unet_forward(ctx, noised.data(), W, H, C, nb, ts.data(), cd.c_crossattn, cd.ctx_dim, cd.n_tokens, 1, cd.c_vector, cd.vector_dim, 1, dst)) return false;
+            if (cached) sc_store.after_condition(*sc, cond_id, noised.data(), dst, n);
+            return true;
         };
         // the primary guidance of the (cond, uncond) pair: classifier-free (guidance.cpp:171) or, with any apg_* parameter set, adaptive projected guidance per image
         // (guidance.cpp:209-294; the momentum buffer lives as long as the trajectory, like the reference's guider object)
@@ -1822,16 +1864,29 @@ struct HostDenoise {
                 }
             }
             std::fill(t2.begin(), t2.end(), t);
-            for (int b = 0; b < nb; ++b) {
-                memcpy(&x2[(2 * b) * per], &noised[b * per], per * sizeof(float));
-                memcpy(&x2[(2 * b + 1) * per], &noised[b * per], per * sizeof(float));
-            }
-            if (!sd_unet_forward(ctx, x2.data(), W, H, C, 2 * nb, t2.data(), c2.data(), p->cond.ctx_dim, p->cond.n_tokens, 2,
-                                 has_y ? y2.data() : nullptr, p->cond.vector_dim, 2, o2.data()))
-                return false;
-            for (int b = 0; b < nb; ++b) {
-                memcpy(&cond_out[b * per], &o2[(2 * b) * per], per * sizeof(float));
-                memcpy(&uncond_out[b * per], &o2[(2 * b + 1) * per], per * sizeof(float));
+            // the anchor's before_condition runs in front of the ONE graph: on a skip both outputs come from their stored differences, otherwise the pair is
+            // computed and after_condition sees cond, then uncond
+            if (cached && sc_store.before_condition(*sc, 0, noised.data(), cond_out.data(), n)) {
+                if (!sc_store.before_condition(*sc, 1, noised.data(), uncond_out.data(), n)) {
+                    set_error("step cache: no stored difference for the unconditional branch of a skipped step");
+                    return false;
+                }
+            } else {
+                for (int b = 0; b < nb; ++b) {
+                    memcpy(&x2[(2 * b) * per], &noised[b * per], per * sizeof(float));
+                    memcpy(&x2[(2 * b + 1) * per], &noised[b * per], per * sizeof(float));
+                }
+                if (!sd_unet_forward(ctx, x2.data(), W, H, C, 2 * nb, t2.data(), c2.data(), p->cond.ctx_dim, p->cond.n_tokens, 2,
+                                     has_y ? y2.data() : nullptr, p->cond.vector_dim, 2, o2.data()))
+                    return false;
+                for (int b = 0; b < nb; ++b) {
+                    memcpy(&cond_out[b * per], &o2[(2 * b) * per], per * sizeof(float));
+                    memcpy(&uncond_out[b * per], &o2[(2 * b + 1) * per], per * sizeof(float));
+                }
+                if (cached) {
+                    sc_store.after_condition(*sc, 0, noised.data(), cond_out.data(), n);  // (uncond's before_condition in between changes nothing: it is never the anchor)
+                    sc_store.after_condition(*sc, 1, noised.data(), uncond_out.data(), n);
+                }
             }
             guide(denoised);
         } else if (!run(p->cond, cond_out.data())) {
@@ -1940,6 +1995,8 @@ static bool sample_group(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, 
     }, 2);
     HostDenoise denoise(ctx, p, W, H, C, nb);
     denoise.n_sigmas = (int)sigmas.size();
+    ctx->step_cache_begin_trajectory(sigmas);  // init_sample_cache_runtime per sample() call, stable-diffusion.cpp:2578
+    denoise.sc = &ctx->step_cache;
     std::vector<float> denoised(per * nb);
     std::vector<std::vector<float>> step_noise(nb);
 
@@ -1997,6 +2054,71 @@ static bool sample_group(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, 
     return true;
 }
 
+// The step caches' two device passes (include/ggml-mi355x.h) as the device-resident sampler and sd_step_cache_kernels reach them: plug-in exports found through the
+// registry's get_proc_address like ggml_backend_mi355x_get_stream, enqueued on the backend's stream between two graphs.  A backend without them (the CPU oracle of
+// the tests) gets the same quantities from the host: the tensors are read back, the sums formed like the host loop's (one float, sequential) and written back.
+struct StepCacheDevice {
+    typedef bool (*probe_fn)(ggml_backend_t, const float*, float, const float*, int64_t, float*);
+    typedef bool (*record_fn)(ggml_backend_t, const float*, const float*, float*, float*, float*, int64_t, int, int64_t, bool, float*);
+    ggml_backend_t backend = nullptr;
+    probe_fn probe_k       = nullptr;
+    record_fn record_k     = nullptr;
+    bool exports_missing   = false;
+    std::vector<float> a, b, c, d;
+    explicit StepCacheDevice(ggml_backend_t be) : backend(be) {
+        ggml_backend_dev_t dev = ggml_backend_get_device(be);
+        ggml_backend_reg_t reg = dev ? ggml_backend_dev_backend_reg(dev) : nullptr;
+        if (reg) {
+            probe_k  = (probe_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_step_cache_probe");
+            record_k = (record_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_step_cache_record");
+        }
+        if (!probe_k || !record_k) probe_k = nullptr, record_k = nullptr;
+        // the product backend without its passes is an error, never a quiet fall-back to full-tensor read-backs; any other backend takes the host restatement
+        exports_missing = !probe_k && reg && strcmp(ggml_backend_reg_name(reg), "MI355X") == 0;
+    }
+    bool on_device() const { return probe_k != nullptr; }
+    // stats[0] = sum |x * c_in - prev_in| over n floats
+    bool probe(ggml_tensor* x, float c_in, ggml_tensor* prev_in, int64_t n, ggml_tensor* stats) {
+        if (probe_k) return probe_k(backend, (const float*)x->data, c_in, (const float*)prev_in->data, n, (float*)stats->data);
+        a.resize((size_t)n), b.resize((size_t)n);
+        ggml_backend_tensor_get(x, a.data(), 0, (size_t)n * sizeof(float));
+        ggml_backend_tensor_get(prev_in, b.data(), 0, (size_t)n * sizeof(float));
+        float sum = 0.0f;
+        for (int64_t i = 0; i < n; ++i) {
+            const float m = a[(size_t)i] * c_in;
+            sum += std::fabs(m - b[(size_t)i]);
+        }
+        ggml_backend_tensor_set(stats, &sum, 0, sizeof(float));
+        return true;
+    }
+    // in / prev_in / prev_out [per, nb], out / diff [per, k, nb]: the stored differences, the anchor's previous input / output, stats[1] and stats[2]
+    bool record(ggml_tensor* in, ggml_tensor* out, ggml_tensor* prev_in, ggml_tensor* prev_out, ggml_tensor* diff, int64_t per, int k, int64_t nb, bool has_prev_out,
+                ggml_tensor* stats) {
+        if (record_k)
+            return record_k(backend, (const float*)in->data, (const float*)out->data, (float*)prev_in->data, (float*)prev_out->data, (float*)diff->data, per, k, nb, has_prev_out,
+                            (float*)stats->data);
+        const size_t n = (size_t)(per * nb);
+        a.resize(n), b.resize(n * k), c.resize(n), d.resize(n * k);
+        ggml_backend_tensor_get(in, a.data(), 0, n * sizeof(float));
+        ggml_backend_tensor_get(out, b.data(), 0, n * k * sizeof(float));
+        if (has_prev_out) ggml_backend_tensor_get(prev_out, c.data(), 0, n * sizeof(float));
+        float sums[2] = {0.0f, 0.0f};
+        for (int64_t im = 0; im < nb; ++im)
+            for (int64_t i = 0; i < per; ++i) {
+                const size_t e = (size_t)(im * per + i), o = (size_t)(im * k * per + i);
+                for (int j = 0; j < k; ++j) d[o + (size_t)j * per] = b[o + (size_t)j * per] - a[e];
+                if (has_prev_out) sums[0] += std::fabs(b[o] - c[e]);
+                sums[1] += std::fabs(b[o]);
+                c[e] = b[o];
+            }
+        ggml_backend_tensor_set(diff, d.data(), 0, n * k * sizeof(float));
+        ggml_backend_tensor_set(prev_in, a.data(), 0, n * sizeof(float));
+        ggml_backend_tensor_set(prev_out, c.data(), 0, n * sizeof(float));
+        ggml_backend_tensor_set(stats, sums, sizeof(float), sizeof(sums));
+        return true;
+    }
+};
+
 // ---- device-resident sampler -----------------------------------------------------------------------
 // The reference crosses the host boundary three times per model call (x*c_in up, eps down, CFG / Euler on the host:
 // stable-diffusion.cpp:2636-2664, 2855-2896; denoiser.hpp:1513-1546).  Here one graph per step carries the whole iteration —
@@ -2006,6 +2128,12 @@ static bool sample_group(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, 
 // scalars arrive as ONE 8-float input, so all steps share one cached plan.  Nothing is read back until the last step: uploads and
 // graphs are queued on the backend stream (set_tensor_async / graph_compute_async) and the host builds step k+1 while step k runs.
 // Ancestral noise stays the host Philox stream (bit-reproducible, rng_philox.hpp:101-122), uploaded per step (64 KB per SD1.5 image).
+//
+// Step cache (sd_set_step_cache): the decision depends on data, so an ACTIVE step cannot be queued blindly.  Per active step: the probe pass sums |x * c_in - prev_in|
+// from the live latents, ONE 16-byte read-back of cache.stats synchronises and delivers that sum together with the two the previous computed step's record pass left
+// there, the host state machine (step_cache.hpp) decides; a computed step runs the RECORDING variant of the step graph (noised and eps pass through cache.in /
+// cache.out on their way) followed by the record pass, a skipped step the SKIP-STEP graph (eps_j = noised + diff_j, then the same combine and update).  Inactive
+// steps, and every trajectory without an armed cache, use the plain step graph under its unchanged signature.  Active steps give up the build-ahead overlap.
 static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, int nb, float* out, bool* handled) {
     *handled = false;
     const int W = p->width / 8, H = p->height / 8, C = ctx->in_channels();
@@ -2096,6 +2224,53 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
         get_stream_fn gs       = reg ? (get_stream_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_get_stream") : nullptr;
         pair_stream            = gs ? gs(ctx->backend) : nullptr;  // host backends (the CPU oracle in the tests): no stream, calls are synchronous
     }
+    ctx->step_cache_begin_trajectory(sigmas);
+    StepCacheRuntime& rt = ctx->step_cache;
+    const int ck = both ? 2 : 1;  // conditions per image in the step graph's eps
+    StepCacheDevice cache_dev(ctx->backend);
+    if (rt.armed()) {  // (never together with a split CFG pair: sd_sample_latents refuses that)
+        if (cache_dev.exports_missing) {
+            set_error("step cache: the MI355X backend does not export its step-cache passes (ggml_backend_mi355x_step_cache_probe / _record)");
+            return false;
+        }
+        if (!st.cache || st.cache->k != ck) {
+            st.cache.reset(new sdm_ctx_t::SamplerState::Cache());
+            auto& cc = *st.cache;
+            ggml_init_params ip{0, nullptr, true};
+            cc.cctx     = ggml_init(ip);
+            cc.in       = ggml_new_tensor_4d(cc.cctx, GGML_TYPE_F32, W, H, C, nb);
+            cc.prev_in  = ggml_new_tensor_4d(cc.cctx, GGML_TYPE_F32, W, H, C, nb);
+            cc.prev_out = ggml_new_tensor_4d(cc.cctx, GGML_TYPE_F32, W, H, C, nb);
+            // the layout the step graph gives eps: cond and uncond of an image adjacent
+            cc.out   = both ? ggml_new_tensor_3d(cc.cctx, GGML_TYPE_F32, (int64_t)((size_t)W * H * C), 2, nb) : ggml_new_tensor_4d(cc.cctx, GGML_TYPE_F32, W, H, C, nb);
+            cc.diff  = both ? ggml_new_tensor_3d(cc.cctx, GGML_TYPE_F32, (int64_t)((size_t)W * H * C), 2, nb) : ggml_new_tensor_4d(cc.cctx, GGML_TYPE_F32, W, H, C, nb);
+            cc.stats = ggml_new_tensor_1d(cc.cctx, GGML_TYPE_F32, 4);
+            ggml_set_name(cc.in, "cache.in");
+            ggml_set_name(cc.out, "cache.out");
+            ggml_set_name(cc.prev_in, "cache.prev_in");
+            ggml_set_name(cc.prev_out, "cache.prev_out");
+            ggml_set_name(cc.diff, "cache.diff");
+            ggml_set_name(cc.stats, "cache.stats");
+            cc.buf = ggml_backend_alloc_ctx_tensors(cc.cctx, ctx->backend);
+            if (!cc.buf) {
+                st.cache.reset();
+                set_error("step cache state allocation failed");
+                return false;
+            }
+            cc.k = ck;
+            static std::atomic<uint64_t> g_cache_serial{0};
+            cc.serial = ++g_cache_serial;
+        }
+    }
+    sdm_ctx_t::SamplerState::Cache* cc = rt.armed() ? st.cache.get() : nullptr;
+    int pending = -1;  // trace record of the computed step whose record-pass sums have not been read back yet
+    auto book_pending = [&](const float* stats) {  // after_condition of that step: cond, then uncond (which only marks its difference as stored)
+        sdm_cache_step_t* rec = &rt.trace[(size_t)pending];
+        const float ne        = static_cast<float>(per * (size_t)nb);
+        rt.after_condition(0, stats[1] / ne, stats[2] / ne, rec);
+        if (ck == 2) rt.after_condition(1, 0.0f, 0.0f, rec);
+        pending = -1;
+    };
     ModelSideInputs si;
     if (!prepare_side_inputs(ctx, W, H, n_model, p->cond.n_tokens, has_y, si)) return false;
     std::vector<float> ts(n_model);
@@ -2104,6 +2279,9 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
     snprintf(step_sig, sizeof(step_sig), "step %d %d %d %d cfg%d ea%d %lld %lld y%lld %p pair%d", W, H, C, nb, (int)use_cfg, (int)euler_a + 2 * (int)flow, (long long)p->cond.ctx_dim,
              (long long)p->cond.n_tokens, (long long)(has_y ? p->cond.vector_dim : -1), (void*)st.x, (int)pair);
     const std::string update_sig = std::string("update ") + step_sig;
+    const std::string cache_tag  = cc ? " cache" + std::to_string(cc->serial) : std::string();
+    const std::string record_sig = std::string("record ") + step_sig + cache_tag;  // the recording variant and the skip-step graph: plans of their own
+    const std::string skip_sig   = std::string("skip ") + step_sig + cache_tag;
 
     for (int i = 0; i < steps; ++i) {
         const float sigma = sigmas[i], sigma_to = sigmas[i + 1];
@@ -2146,7 +2324,27 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             }, 2);
             ggml_backend_tensor_set_async(ctx->backend, st.noise, noise.data(), 0, noise.size() * sizeof(float));
         }
-        auto build = [&](GraphCtx& g, std::vector<HostInput>& in) {
+        // step cache: book the previous computed step, measure this step's input change, decide (see the note above the function)
+        bool skip_step = false, record_step = false;
+        if (cc) {
+            const bool active  = rt.in_window(sigma);
+            const bool measure = active && (pending >= 0 || rt.core().has_prev_input);  // once the pending record is booked the anchor has a previous input, output and difference
+            float stats[4]     = {0.f, 0.f, 0.f, 0.f};
+            if (measure && !cache_dev.probe(st.x, c_in, cc->prev_in, (int64_t)(per * (size_t)nb), cc->stats)) {
+                set_error("step cache: the probe pass could not be enqueued");
+                return false;
+            }
+            if (measure || pending >= 0) ggml_backend_tensor_get(cc->stats, stats, 0, sizeof(stats));  // THE synchronisation of an active step
+            if (pending >= 0) book_pending(stats);
+            rt.begin_call(i + 1, sigma);
+            if (rt.step_is_active()) {
+                if (rt.before_condition(0) == SC_MEASURE) skip_step = rt.decide(stats[0] / static_cast<float>(per * (size_t)nb));
+                record_step = !skip_step;
+            }
+        }
+        // variant 0: the step graph; 1: the same, recording (noised passes through cache.in, eps through cache.out); 2: the skip-step graph (no model call)
+        auto build_variant = [&](int variant) {
+          return [&, variant](GraphCtx& g, std::vector<HostInput>& in) {
             ggml_context* c  = g.ctx;
             ggml_tensor* tsc = ggml_new_tensor_1d(c, GGML_TYPE_F32, 8);
             ggml_set_input(tsc);
@@ -2154,18 +2352,35 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             auto S = [&](int k) { return ggml_view_1d(c, tsc, 1, (size_t)k * sizeof(float)); };
             ggml_tensor* xs     = st.x;
             ggml_tensor* noised = ggml_mul(c, xs, S(0));
-            ggml_tensor* xin    = noised;
-            if (both) {  // every image twice, (cond, uncond) adjacent: [per, 1, nb] -> [per, 2, nb]
-                ggml_tensor* flat = ggml_reshape_3d(c, noised, (int64_t)per, 1, nb);
-                ggml_tensor* rep  = ggml_repeat(c, flat, ggml_new_tensor_3d(c, GGML_TYPE_F32, (int64_t)per, 2, nb));
-                xin               = ggml_reshape_4d(c, rep, W, H, C, 2 * nb);
+            if (variant == 1) noised = ggml_cpy(c, noised, cc->in);
+            ggml_tensor *eps = nullptr, *e3 = nullptr;  // e3: the pair's outputs [per, 2, nb], contiguous
+            if (variant == 2) {  // apply_condition_cache_diff for every condition: eps_j = noised + diff_j
+                if (both) {
+                    ggml_tensor* flat = ggml_reshape_3d(c, noised, (int64_t)per, 1, nb);
+                    ggml_tensor* rep  = ggml_repeat(c, flat, ggml_new_tensor_3d(c, GGML_TYPE_F32, (int64_t)per, 2, nb));
+                    e3                = ggml_add(c, rep, cc->diff);
+                } else {
+                    eps = ggml_add(c, noised, cc->diff);
+                }
+            } else {
+                ggml_tensor* xin = noised;
+                if (both) {  // every image twice, (cond, uncond) adjacent: [per, 1, nb] -> [per, 2, nb]
+                    ggml_tensor* flat = ggml_reshape_3d(c, noised, (int64_t)per, 1, nb);
+                    ggml_tensor* rep  = ggml_repeat(c, flat, ggml_new_tensor_3d(c, GGML_TYPE_F32, (int64_t)per, 2, nb));
+                    xin               = ggml_reshape_4d(c, rep, W, H, C, 2 * nb);
+                }
+                eps = build_model_call(ctx, g, in, xin, n_model, ts.data(), c2.data(), p->cond.ctx_dim, p->cond.n_tokens, ctx_n,
+                                       has_y ? y2.data() : nullptr, p->cond.vector_dim, ctx_n, si);
+                if (pair) return ggml_cpy(c, ggml_mul(c, eps, S(1)), st.eps);  // weight * eps of this rank's branch; the update follows the exchange
+                if (both) {
+                    e3 = ggml_reshape_3d(c, ggml_cont(c, eps), (int64_t)per, 2, nb);
+                    if (variant == 1) e3 = ggml_cpy(c, e3, cc->out);
+                } else if (variant == 1) {
+                    eps = ggml_cpy(c, eps, cc->out);
+                }
             }
-            ggml_tensor* eps = build_model_call(ctx, g, in, xin, n_model, ts.data(), c2.data(), p->cond.ctx_dim, p->cond.n_tokens, ctx_n,
-                                                has_y ? y2.data() : nullptr, p->cond.vector_dim, ctx_n, si);
-            if (pair) return ggml_cpy(c, ggml_mul(c, eps, S(1)), st.eps);  // weight * eps of this rank's branch; the update follows the exchange
             ggml_tensor* guided = eps;
             if (both) {  // uncond + s*(cond - uncond), guidance.cpp:171
-                ggml_tensor* e3 = ggml_reshape_3d(c, ggml_cont(c, eps), (int64_t)per, 2, nb);
                 ggml_tensor* ec = ggml_view_3d(c, e3, (int64_t)per, 1, nb, e3->nb[1], e3->nb[2], 0);
                 ggml_tensor* eu = ggml_view_3d(c, e3, (int64_t)per, 1, nb, e3->nb[1], e3->nb[2], e3->nb[1]);
                 ggml_tensor* d  = ggml_mul(c, ggml_sub(c, ec, eu), S(1));
@@ -2182,6 +2397,7 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
                 xn             = ggml_add(c, xs, ggml_mul(c, d, S(5)));
             }
             return ggml_cpy(c, xn, xs);
+          };
         };
         std::vector<const void*> ptrs{sc, ts.data(), c2.data()};
         if (has_y) ptrs.push_back(y2.data());
@@ -2189,7 +2405,18 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             ptrs.push_back(si.guidance.data());
             ptrs.push_back(si.pe().data());
         }
-        if (!r.compute(build, nullptr, 0, step_sig, ptrs)) return false;
+        if (skip_step) {
+            if (!ctx->skip_runner.compute(build_variant(2), nullptr, 0, skip_sig, {sc})) return false;
+            continue;
+        }
+        if (!r.compute(build_variant(record_step ? 1 : 0), nullptr, 0, record_step ? record_sig : std::string(step_sig), ptrs)) return false;
+        if (record_step) {
+            if (!cache_dev.record(cc->in, cc->out, cc->prev_in, cc->prev_out, cc->diff, (int64_t)per, ck, nb, rt.core().has_prev_output, cc->stats)) {
+                set_error("step cache: the record pass could not be enqueued");
+                return false;
+            }
+            pending = (int)rt.trace.size() - 1;
+        }
         if (pair) {
             if (!ctx->pair_fn(st.eps->data, (int64_t)(per * nb), pair_stream, ctx->pair_user)) {
                 set_error("CFG-pair exchange failed");
@@ -2218,10 +2445,83 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
         }
     }
     ggml_backend_tensor_get(st.x, out, 0, per * nb * sizeof(float));  // synchronises the stream
+    if (pending >= 0) {  // the last computed step's sums, for the trace
+        float stats[4];
+        ggml_backend_tensor_get(cc->stats, stats, 0, sizeof(stats));
+        book_pending(stats);
+    }
     ctx->stats.unet_calls  = r.calls;
     ctx->stats.graph_nodes = r.last_nodes;
     if (r.galloc) ctx->stats.compute_buffer_bytes = ggml_gallocr_get_buffer_size(r.galloc, 0);
     return true;
+}
+
+// ---- step caches (csrc/host/step_cache.hpp) -----------------------------------------------------------------------------------
+void sdm_cache_params_init(sdm_cache_params_t* p) { *p = sdm_cache_params_t{SDM_CACHE_DISABLED, INFINITY, 0.15f, 0.95f, 1.0f, true, true}; }  // sd_cache_params_init
+bool sd_set_step_cache(sdm_ctx_t* ctx, const sdm_cache_params_t* params) {
+    if (params && params->mode != SDM_CACHE_DISABLED &&
+        (std::isnan(params->reuse_threshold) || std::isnan(params->start_percent) || std::isnan(params->end_percent) || std::isnan(params->error_decay_rate))) {
+        set_error("sd_set_step_cache: NaN parameter");
+        return false;
+    }
+    if (params)
+        ctx->cache_params = *params;
+    else
+        sdm_cache_params_init(&ctx->cache_params);
+    if (ctx->cache_params.mode == SDM_CACHE_DISABLED && ctx->sstate) ctx->sstate->cache.reset();
+    return true;
+}
+int sd_step_cache_trace(sdm_ctx_t* ctx, sdm_cache_step_t* out, int capacity) {
+    const std::vector<sdm_cache_step_t>& t = ctx->step_cache.trace;
+    for (int i = 0; out && i < capacity && i < (int)t.size(); ++i) out[i] = t[(size_t)i];
+    return (int)t.size();
+}
+const char* sd_step_cache_status(sdm_ctx_t* ctx) { return ctx->step_cache.status.c_str(); }
+float sd_t_to_sigma(sdm_ctx_t* ctx, float t) { return ctx->t_to_sigma(t); }
+bool sd_step_cache_device_passes(sdm_ctx_t* ctx) { return StepCacheDevice(ctx->backend).on_device(); }
+bool sd_step_cache_kernels(sdm_ctx_t* ctx, const float* in, const float* out, const float* prev_in, const float* prev_out, int64_t n, int k, int nb, float c_in, float* stats,
+                           float* diff_out, float* prev_in_out, float* prev_out_out) {
+    if (!in || !out || !prev_in || !stats || n < 1 || nb < 1 || k < 1 || k > 2) {
+        set_error("sd_step_cache_kernels: bad arguments");
+        return false;
+    }
+    ggml_init_params ip{0, nullptr, true};
+    ggml_context* c = ggml_init(ip);
+    ggml_tensor* t_in   = ggml_new_tensor_2d(c, GGML_TYPE_F32, n, nb);
+    ggml_tensor* t_pin  = ggml_new_tensor_2d(c, GGML_TYPE_F32, n, nb);
+    ggml_tensor* t_pout = ggml_new_tensor_2d(c, GGML_TYPE_F32, n, nb);
+    ggml_tensor* t_out  = ggml_new_tensor_3d(c, GGML_TYPE_F32, n, k, nb);
+    ggml_tensor* t_diff = ggml_new_tensor_3d(c, GGML_TYPE_F32, n, k, nb);
+    ggml_tensor* t_st   = ggml_new_tensor_1d(c, GGML_TYPE_F32, 4);
+    ggml_backend_buffer_t buf = ggml_backend_alloc_ctx_tensors(c, ctx->backend);
+    if (!buf) {
+        ggml_free(c);
+        set_error("sd_step_cache_kernels: allocation failed");
+        return false;
+    }
+    const size_t bytes = (size_t)n * nb * sizeof(float);
+    const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+    ggml_backend_tensor_set(t_in, in, 0, bytes);
+    ggml_backend_tensor_set(t_out, out, 0, bytes * k);
+    ggml_backend_tensor_set(t_pin, prev_in, 0, bytes);
+    if (prev_out) ggml_backend_tensor_set(t_pout, prev_out, 0, bytes);
+    ggml_backend_tensor_set(t_st, zero, 0, sizeof(zero));
+    StepCacheDevice dev(ctx->backend);
+    const bool ok = !dev.exports_missing && dev.probe(t_in, c_in, t_pin, n * nb, t_st) && dev.record(t_in, t_out, t_pin, t_pout, t_diff, n, k, nb, prev_out != nullptr, t_st);
+    if (ok) {
+        float st4[4];
+        ggml_backend_tensor_get(t_st, st4, 0, sizeof(st4));  // (synchronises the stream the passes were enqueued on)
+        memcpy(stats, st4, 3 * sizeof(float));
+        if (diff_out) ggml_backend_tensor_get(t_diff, diff_out, 0, bytes * k);
+        if (prev_in_out) ggml_backend_tensor_get(t_pin, prev_in_out, 0, bytes);
+        if (prev_out_out) ggml_backend_tensor_get(t_pout, prev_out_out, 0, bytes);
+    } else {
+        ggml_backend_synchronize(ctx->backend);
+        set_error("sd_step_cache_kernels: the passes could not be run (size beyond the summation-depth bound?)");
+    }
+    ggml_backend_buffer_free(buf);
+    ggml_free(c);
+    return ok;
 }
 
 bool sd_sample_latents(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, float* out_latents) {
@@ -2229,14 +2529,31 @@ bool sd_sample_latents(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, float* out
     const size_t per = (size_t)W * H * C;
     const int group  = p->device_batch > 0 ? p->device_batch : p->batch_count;
     const double t0  = now_ms();
+    ctx->stats.steps_skipped = 0;
+    if (ctx->step_cache_would_arm()) {
+        const sdm_sample_params_t& sp = p->sample_params;
+        // the reference re-enters its cache with the cond pointer a second time inside a skip-layer step; that is not restated: refused
+        if (ctx->is_dit && !ctx->is_flux && sp.slg_scale != 0.0f && sp.slg_layers && sp.slg_layer_count > 0) {
+            set_error("step cache: not available together with skip-layer guidance");
+            return false;
+        }
+        if (ctx->pair_fn != nullptr && p->device_sampler) {
+            set_error("step cache: not available with a CFG-pair exchange (the anchor condition lives on one rank only)");
+            return false;
+        }
+    }
     for (int b0 = 0; b0 < p->batch_count; b0 += group) {
         const int nb = std::min(group, p->batch_count - b0);
         if (p->device_sampler) {
             bool handled = false;
             if (!sample_group_device(ctx, p, b0, nb, out_latents + b0 * per, &handled)) return false;
-            if (handled) continue;  // otherwise (cond / uncond shapes differ): the host loop below
+            if (handled) {
+                ctx->stats.steps_skipped += ctx->step_cache.total_steps_skipped();
+                continue;
+            }  // otherwise (cond / uncond shapes differ): the host loop below
         }
         if (!sample_group(ctx, p, b0, nb, out_latents + b0 * per)) return false;
+        ctx->stats.steps_skipped += ctx->step_cache.total_steps_skipped();
     }
     ctx->stats.last_sample_ms = now_ms() - t0;
     return true;

@@ -64,6 +64,16 @@ void launch_timestep_embedding(hipStream_t s, float* dst, const float* t, int n,
 // GEGLU: dst[t][i] = x[t][i] * gelu(x[t][inner + i]); x row stride given in floats
 void launch_geglu(hipStream_t s, float* dst, const float* x, int64_t tokens, int64_t inner, int64_t x_stride);
 
+// ---- step_cache.hip: the step caches' device passes (deterministic sums: per-workgroup partials + a one-workgroup finish launch, no float atomics) ----
+// partial: step_cache_partial_bytes() of device scratch owned by the caller's stream.  Both return false (nothing enqueued) for sizes beyond their depth bound.
+size_t step_cache_partial_bytes();
+// stats[0] = sum |x * c_in - prev_in| over n floats, x * c_in rounded once like the step graph's MUL
+bool launch_step_cache_probe(hipStream_t s, const float* x, float c_in, const float* prev_in, int64_t n, float* partial, float* stats);
+// in / prev_in / prev_out [per, nb], out / diff [per, k, nb] (k = 1 or 2, condition 0 first): diff_j = out_j - in, prev_in = in, prev_out = out_0,
+// stats2[0] = sum |out_0 - prev_out(old)| (0 without has_prev_out: prev_out is not read), stats2[1] = sum |out_0|
+bool launch_step_cache_record(hipStream_t s, const float* in, const float* out, float* prev_in, float* prev_out, float* diff, int64_t per, int k, int64_t nb, bool has_prev_out,
+                              float* partial, float* stats2);
+
 // ---- norm.hip ---------------------------------------------------------------------------------------
 // GROUP_NORM over [W*H, C, N] contiguous f32; optional fused affine (w,b per channel) and SiLU
 void launch_group_norm(hipStream_t s, float* dst, const float* x, int64_t hw, int64_t C, int64_t N, int groups, float eps,
