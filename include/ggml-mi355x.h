@@ -198,6 +198,16 @@ GGML_MI355X_API void* ggml_backend_mi355x_get_stream(ggml_backend_t backend);
 GGML_MI355X_API bool ggml_backend_mi355x_step_cache_probe(ggml_backend_t backend, const float* x, float c_in, const float* prev_in, int64_t n, float* stats);
 GGML_MI355X_API bool ggml_backend_mi355x_step_cache_record(ggml_backend_t backend, const float* in, const float* out, float* prev_in, float* prev_out, float* diff, int64_t per,
                                                            int k, int64_t nb, bool has_prev_out, float* stats);
+/*   probe_rel (the CacheDIT modes): stats[0] as probe, stats[3] = sum over n of |prev_in| — one pass and the finish launch, the same guarantees */
+GGML_MI355X_API bool ggml_backend_mi355x_step_cache_probe_rel(ggml_backend_t backend, const float* x, float c_in, const float* prev_in, int64_t n, float* stats);
+/* Spectrum's forecast (kernels/step_cache.hip), one streaming kernel on that stream: with H_j = ring + order[j] * slot_stride (k slots of n floats, oldest first,
+ * 2 <= k <= 16) and every operation rounded to f32 on its own,
+ *   pc = 0; for j: pc = pc + weights[j] * H_j[f];  pt = H_{k-1}[f] + 0.5 * (H_{k-1}[f] - H_{k-2}[f]);  out[f] = (1 - w) * pt + w * pc
+ * order and weights are HOST arrays (passed as kernel arguments).  out must not overlap the ring.  false: bad arguments — nothing was enqueued. */
+GGML_MI355X_API bool ggml_backend_mi355x_spectrum_predict(ggml_backend_t backend, const float* ring, int64_t slot_stride, const int* order, int k, const float* weights, float w,
+                                                          int64_t n, float* out);
+/* a computed step's `denoised` into its ring slot: a device-to-device copy of n floats enqueued on that stream (no kernel) */
+GGML_MI355X_API bool ggml_backend_mi355x_spectrum_push(ggml_backend_t backend, const float* src, float* dst, int64_t n);
 /* path of the HIP runtime library this plug-in is bound to, and hipSetDevice through it (for companions that must share its streams: RCCL) */
 GGML_MI355X_API const char* ggml_backend_mi355x_hip_library(void);
 GGML_MI355X_API int ggml_backend_mi355x_set_device(int hip_device);

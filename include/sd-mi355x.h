@@ -268,12 +268,23 @@ SD_API bool sd_sample_latents(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, flo
 SD_API bool sdm_generate_image(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, sdm_image_t** images_out, int* num_images_out);
 SD_API void sdm_free_images(sdm_image_t* images, int num_images);
 
-/* ---- step caches: the reference's `--cache-mode easycache` (DiT families) and `--cache-mode ucache` (UNet families) -------------------------------------------
- * sd_cache_params_t of include/stable-diffusion.h restricted to the two condition-level caches (src/runtime/easycache.hpp, ucache.hpp, sample-cache.cpp): a denoise
- * step whose model output can be predicted from the previous computed step (output = input + (previous output - previous input)) is not run.  The state machines
- * are restated in csrc/host/step_cache.hpp.  DBCache / TaylorSeer / CacheDIT / Spectrum reach into the model's blocks and are not implemented.  Mode values as in
- * the reference's sd_cache_mode_t. */
-enum sdm_cache_mode_t { SDM_CACHE_DISABLED = 0, SDM_CACHE_EASYCACHE = 1, SDM_CACHE_UCACHE = 2 };
+/* ---- step caches: the reference's `--cache-mode easycache` (DiT families), `ucache` (UNet families), `dbcache` / `taylorseer` / `cache-dit` (DiT families) and
+ * `spectrum` (UNet and DiT families) ---------------------------------------------------------------------------------------------------------------------------------
+ * sd_cache_params_t of include/stable-diffusion.h.  The condition-level caches (src/runtime/easycache.hpp, ucache.hpp, CacheDitConditionState of cache_dit.hpp,
+ * sample-cache.cpp): a denoise step whose model output can be predicted from the previous computed step (output = input + (previous output - previous input)) is
+ * not run.  dbcache, taylorseer and cache-dit are ONE such cache in the reference (the block-level CacheDitState is used nowhere by its sampler): they differ from
+ * EasyCache in the metric only — the relative L1 change of the model input against a fixed threshold — and the three modes behave identically.  Spectrum
+ * (src/runtime/spectrum.hpp) replaces whole denoise calls, on a schedule that does not depend on data, by a forecast from the last K denoised tensors.  The
+ * state machines are restated in csrc/host/step_cache.hpp.  Mode values as in the reference's sd_cache_mode_t. */
+enum sdm_cache_mode_t {
+    SDM_CACHE_DISABLED   = 0,
+    SDM_CACHE_EASYCACHE  = 1,
+    SDM_CACHE_UCACHE     = 2,
+    SDM_CACHE_DBCACHE    = 3,
+    SDM_CACHE_TAYLORSEER = 4,
+    SDM_CACHE_CACHE_DIT  = 5,
+    SDM_CACHE_SPECTRUM   = 6
+};
 typedef struct {
     enum sdm_cache_mode_t mode;
     float reuse_threshold;       /* INFINITY = the mode's default (EasyCache 0.2, UCache 1.0); negative values count as 0 */
@@ -290,21 +301,43 @@ SD_API void sdm_cache_params_init(sdm_cache_params_t* p); /* sd_cache_params_ini
  * group: with device_batch > 1 the three means run over the whole group (the reference samples one image at a time).  false (sd_last_error): a NaN parameter.
  * Refused at sampling time (sd_last_error): an armed cache together with skip-layer guidance, or with a CFG-pair exchange (sd_set_pair_exchange*). */
 SD_API bool sd_set_step_cache(sdm_ctx_t* ctx, const sdm_cache_params_t* params);
+/* The options of the modes 3 .. 6 that change a trajectory in the reference (its warm-up, max-cached-steps, max-continuous-cached-steps, steps-computation-mask and
+ * taylorseer_* options change none: DESIGN.md section 0). */
+typedef struct {
+    int Fn_compute_blocks;         /* > 0: the threshold is scaled by clamp(1 + 0.02 * (Fn - 8), 0.5, 2) */
+    int Bn_compute_blocks;         /* > 0: ... and by clamp(1 - 0.03 * Bn, 0.5, 1) */
+    float residual_diff_threshold; /* a step is skipped while sum |prev_in - in| / (sum |prev_in| + 1e-6) stays under the scaled threshold */
+} sdm_cache_dit_params_t;
+typedef struct {
+    float w;            /* weight of the Chebyshev forecast; 1 - w goes to the first-order extrapolation */
+    int m;              /* polynomial degree, 0 .. 15; the history holds K = max(m + 1, 6) denoised tensors */
+    float lam;          /* ridge term */
+    int window_size;    /* every floor(window)-th call after warm-up is computed; the window starts here ... */
+    float flex_window;  /* ... and grows by this much with every computed call after warm-up */
+    int warmup_steps;   /* denoise calls that are always computed */
+    float stop_percent; /* calls from (int)(stop_percent * steps) on are always computed */
+} sdm_spectrum_params_t;
+SD_API void sdm_cache_dit_params_init(sdm_cache_dit_params_t* p); /* 8, 0, 0.08 */
+SD_API void sdm_spectrum_params_init(sdm_spectrum_params_t* p);   /* 0.40, 3, 1.0, 2, 0.50, 4, 0.9 */
+/* sd_set_step_cache plus the two extensions; a NULL extension means its defaults (so does sd_set_step_cache with one of the modes 3 .. 6).  false (sd_last_error): a
+ * NaN parameter, or m outside 0 .. 15.  The CacheDIT modes on a UNet family, an invalid percent range (checked for every mode, though the CacheDIT window is fixed
+ * at 15 % .. 95 % of the ladder and Spectrum has no window) and Spectrum with the two CFG++ sample methods run uncached, and sd_step_cache_status says why. */
+SD_API bool sd_set_step_cache_ex(sdm_ctx_t* ctx, const sdm_cache_params_t* params, const sdm_cache_dit_params_t* cache_dit, const sdm_spectrum_params_t* spectrum);
 /* one record per denoise call (model evaluation request of the sampler) of the last trajectory — the last device group of the last sd_sample_latents */
 typedef struct {
     int step;            /* what the sampler handed the denoise call: i + 1, negated for the first stage of the two-stage methods (never cached) */
     float sigma;
     bool active;         /* inside the cache's sigma window */
     bool skipped;        /* the model was not run: outputs were rebuilt from the stored differences */
-    float input_change;  /* mean |input - previous computed input| (0 when not measured) */
+    float input_change;  /* mean |input - previous computed input| (0 when not measured); CacheDIT modes: the relative residual diff, as `rate` */
     float output_change; /* mean |output - previous computed output| of the anchor condition (computed steps; 0 when there was no previous output) */
     float output_norm;   /* mean |output| of the anchor condition (computed steps) */
     float rate;          /* the estimated output change of this step the decision added (0 when no decision was due) */
-    float accumulated;   /* EasyCache: cumulative change rate, UCache: accumulated error — after adding `rate`, before any reset */
+    float accumulated;   /* EasyCache: cumulative change rate, UCache: accumulated error — after adding `rate`, before any reset; CacheDIT modes: the accumulated residual diff */
     float threshold;     /* the effective threshold `accumulated` was compared with */
-} sdm_cache_step_t;
+} sdm_cache_step_t; /* Spectrum: active = past warm-up and before the stop call, skipped = forecast instead of computed, the metric fields 0 */
 SD_API int sd_step_cache_trace(sdm_ctx_t* ctx, sdm_cache_step_t* out, int capacity); /* returns the record count (also with capacity 0); at most `capacity` are written */
-SD_API const char* sd_step_cache_status(sdm_ctx_t* ctx);                             /* "easycache" / "ucache" when the last trajectory was armed, else why not */
+SD_API const char* sd_step_cache_status(sdm_ctx_t* ctx);                             /* "easycache" / "ucache" / "dbcache" / "taylorseer" / "cache-dit" / "spectrum" when the last trajectory was armed, else why not */
 /* whether the device-resident sampler's two cache passes run as the backend's HIP kernels (true) or as the host restatement of a backend without those exports (false);
  * an MI355X backend that lacks the exports is an error at sampling time, never a quiet fall-back */
 SD_API bool sd_step_cache_device_passes(sdm_ctx_t* ctx);
@@ -315,6 +348,14 @@ SD_API float sd_t_to_sigma(sdm_ctx_t* ctx, float t);                            
  * stats[2] = sum |out_0|; diff_out_j = out_j - in, prev_in_out = in, prev_out_out = out_0. */
 SD_API bool sd_step_cache_kernels(sdm_ctx_t* ctx, const float* in, const float* out, const float* prev_in, const float* prev_out, int64_t n, int k, int nb, float c_in,
                                   float* stats, float* diff_out, float* prev_in_out, float* prev_out_out);
+/* the CacheDIT modes' probe the same way ("ggml_backend_mi355x_step_cache_probe_rel"): sums[0] = sum |in * c_in - prev_in|, sums[1] = sum |prev_in| over n floats */
+SD_API bool sd_step_cache_kernels_rel(sdm_ctx_t* ctx, const float* in, const float* prev_in, int64_t n, float c_in, float* sums);
+/* Spectrum for tests.  schedule: predicted[i] = 1 when denoise call i of a trajectory of n_calls single-stage steps is forecast.  weights: the k history weights
+ * for the taus of the k stored calls (oldest first) and the tau of the call to forecast.  kernels: the forecast itself on caller memory — hist [k][n] oldest first —
+ * through the path the device sampler uses ("ggml_backend_mi355x_spectrum_predict", or the host restatement on a backend without it). */
+SD_API bool sd_spectrum_schedule(const sdm_spectrum_params_t* params, int n_calls, uint8_t* predicted);
+SD_API bool sd_spectrum_weights(const sdm_spectrum_params_t* params, const float* taus, int k, float tau_at, float* weights);
+SD_API bool sd_spectrum_kernels(sdm_ctx_t* ctx, const float* hist, int k, int64_t n, const float* weights, float w, float* out);
 
 /* ---- host-side sampler pieces exposed for known-answer tests ---- */
 SD_API void sd_philox_randn(uint64_t seed, uint32_t offset, uint32_t n, float* out); /* rng_philox.hpp:101-122 */

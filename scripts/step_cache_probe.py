@@ -7,7 +7,11 @@
   default    the reference's default parameters (EasyCache 0.2 / UCache 1.0, window 0.15 .. 0.95): steps skipped, seconds per image, and the PSNR of the decoded
              images against the uncached ones
 
-usage: step_cache_probe.py [sd15] [sdxl] [sd35] [flux] [steps=20] [out=FILE]   (weights are the engine's synthetic ones: the skip counts say what THESE models do,
+With modes=new the same workloads run the reference's other four cache modes at its defaults instead — dbcache, taylorseer and cache-dit (one cache under three
+names, DiT families only: on a UNet family the line says that they are not armed) and spectrum — each against cache off in the same process: steps skipped,
+seconds per image, PSNR of the decoded image against the uncached one.
+
+usage: step_cache_probe.py [sd15] [sdxl] [sd35] [flux] [steps=20] [modes=new] [out=FILE]   (weights are the engine's synthetic ones: the skip counts say what THESE models do,
 not what a trained checkpoint does; the timing of a computed, a skipped and an armed step does not depend on the weights)"""
 import sys
 import time
@@ -68,6 +72,22 @@ def main():
 
         e.set_step_cache(None)
         lat_off, ms_off, _, _ = run()
+        if opts.get("modes") == "new":
+            img_off = e.vae_decode(lat_off[:1])
+            say(f"   off          {ms_off / 1e3 / batch:8.4f} s / image   ({ms_off / steps:.2f} ms per step)")
+            for label_, mode_ in (("dbcache", sd.CACHE_DBCACHE), ("taylorseer", sd.CACHE_TAYLORSEER), ("cache-dit", sd.CACHE_CACHE_DIT), ("spectrum", sd.CACHE_SPECTRUM)):
+                e.set_step_cache(mode_)
+                lat_on, ms_on, skipped, tr_on = run()
+                status = e.step_cache_status()
+                if status != label_:
+                    say(f"   {label_:<12} {status}")
+                    continue
+                say(f"   {label_:<12} {ms_on / 1e3 / batch:8.4f} s / image   ({skipped} of {steps} steps skipped, {sum(r['active'] for r in tr_on)} active; {ms_off / ms_on:.3f}x; "
+                    f"PSNR of the decoded image against the uncached one {psnr(e.vae_decode(lat_on[:1]), img_off):.1f} dB; latents {'finite' if np.isfinite(lat_on).all() else 'NOT FINITE'})")
+                say(f"   {'':<12} skipped steps: " + (" ".join(str(r["step"]) for r in tr_on if r["skipped"]) or "none"))
+            e.set_step_cache(None)
+            e.close()
+            continue
         e.set_step_cache(mode, reuse_threshold=0.0)
         lat_zero, ms_zero, _, tr_zero = run()
         e.set_step_cache(mode)

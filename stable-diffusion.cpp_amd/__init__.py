@@ -39,6 +39,7 @@ SCHED_DISCRETE, SCHED_KARRAS, SCHED_EXPONENTIAL, SCHED_AYS, SCHED_GITS, SCHED_SG
 SCHED_BONG_TANGENT, SCHED_FLUX, SCHED_BETA, SCHEDULER_DEFAULT = 10, 14, 15, 16   # DEFAULT: LCM for the LCM method, SIMPLE for DDIM trailing, FLUX for FLUX, DISCRETE otherwise (sd_get_default_scheduler)
 # sdm_cache_mode_t (include/sd-mi355x.h): the reference's sd_cache_mode_t values
 CACHE_DISABLED, CACHE_EASYCACHE, CACHE_UCACHE = 0, 1, 2
+CACHE_DBCACHE, CACHE_TAYLORSEER, CACHE_CACHE_DIT, CACHE_SPECTRUM = 3, 4, 5, 6
 
 
 class EngineError(RuntimeError):
@@ -128,6 +129,62 @@ class SdCacheParams(C.Structure):
     """sdm_cache_params_t (include/sd-mi355x.h)"""
     _fields_ = [("mode", C.c_int), ("reuse_threshold", C.c_float), ("start_percent", C.c_float), ("end_percent", C.c_float), ("error_decay_rate", C.c_float),
                 ("use_relative_threshold", C.c_bool), ("reset_error_on_compute", C.c_bool)]
+
+
+class SdCacheDitParams(C.Structure):
+    """sdm_cache_dit_params_t (include/sd-mi355x.h)"""
+    _fields_ = [("Fn_compute_blocks", C.c_int), ("Bn_compute_blocks", C.c_int), ("residual_diff_threshold", C.c_float)]
+
+
+class SdSpectrumParams(C.Structure):
+    """sdm_spectrum_params_t (include/sd-mi355x.h)"""
+    _fields_ = [("w", C.c_float), ("m", C.c_int), ("lam", C.c_float), ("window_size", C.c_int), ("flex_window", C.c_float), ("warmup_steps", C.c_int),
+                ("stop_percent", C.c_float)]
+
+
+def cache_dit_params(**over) -> SdCacheDitParams:
+    """sdm_cache_dit_params_init, then the given fields"""
+    p = SdCacheDitParams()
+    lib().sdm_cache_dit_params_init(C.byref(p))
+    for k, v in over.items():
+        setattr(p, {"Fn": "Fn_compute_blocks", "Bn": "Bn_compute_blocks", "threshold": "residual_diff_threshold"}.get(k, k), v)
+    return p
+
+
+def spectrum_params(**over) -> SdSpectrumParams:
+    """sdm_spectrum_params_init, then the given fields"""
+    p = SdSpectrumParams()
+    lib().sdm_spectrum_params_init(C.byref(p))
+    for k, v in over.items():
+        if k not in dict(SdSpectrumParams._fields_):
+            raise TypeError("sdm_spectrum_params_t has no field " + k)
+        setattr(p, k, v)
+    return p
+
+
+def spectrum_schedule(n_calls: int, **over) -> str:
+    """sd_spectrum_schedule: one letter per denoise call of a single-stage trajectory, C = computed, P = predicted"""
+    p = spectrum_params(**over)
+    buf = (C.c_uint8 * max(n_calls, 1))()
+    L = lib()
+    L.sd_spectrum_schedule.argtypes = [C.POINTER(SdSpectrumParams), C.c_int, C.c_void_p]
+    L.sd_spectrum_schedule.restype = C.c_bool
+    if not L.sd_spectrum_schedule(C.byref(p), n_calls, buf):
+        raise EngineError("sd_spectrum_schedule failed: " + L.sd_last_error().decode())
+    return "".join("P" if buf[i] else "C" for i in range(n_calls))
+
+
+def spectrum_weights(taus, tau_at: float, **over) -> np.ndarray:
+    """sd_spectrum_weights: the history weights for the stored calls' taus (oldest first) and the tau of the call to forecast"""
+    p = spectrum_params(**over)
+    t = np.ascontiguousarray(taus, dtype=np.float32)
+    out = np.empty(t.size, dtype=np.float32)
+    L = lib()
+    L.sd_spectrum_weights.argtypes = [C.POINTER(SdSpectrumParams), C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+    L.sd_spectrum_weights.restype = C.c_bool
+    if not L.sd_spectrum_weights(C.byref(p), _fptr(t), int(t.size), float(tau_at), _fptr(out)):
+        raise EngineError("sd_spectrum_weights failed: " + L.sd_last_error().decode())
+    return out
 
 
 class SdCacheStep(C.Structure):
@@ -702,18 +759,27 @@ class Engine:
 
     # ---- step caches (EasyCache / UCache) ----
     def set_step_cache(self, mode: int = CACHE_DISABLED, reuse_threshold: float = float("inf"), start_percent: float = 0.15, end_percent: float = 0.95,
-                       error_decay_rate: float = 1.0, use_relative_threshold: bool = True, reset_error_on_compute: bool = True) -> None:
+                       error_decay_rate: float = 1.0, use_relative_threshold: bool = True, reset_error_on_compute: bool = True, cache_dit: dict | None = None,
+                       spectrum: dict | None = None) -> None:
         """sd_set_step_cache — the reference's `--cache-mode easycache` (DiT families) / `ucache` (UNet families): sample_latents / generate_image skip denoise steps
         whose output the previous computed step predicts.  mode None or CACHE_DISABLED turns it off.  A mode that does not fit the family or an invalid percent
-        range runs uncached (step_cache_status says why)."""
+        range runs uncached (step_cache_status says why).  CACHE_DBCACHE / CACHE_TAYLORSEER / CACHE_CACHE_DIT (DiT families; one cache under three names) and
+        CACHE_SPECTRUM (every family) take their options as dicts: cache_dit = {Fn_compute_blocks, Bn_compute_blocks, residual_diff_threshold}, spectrum = {w, m,
+        lam, window_size, flex_window, warmup_steps, stop_percent}; fields left out keep the reference's defaults.  With either given the call goes through
+        sd_set_step_cache_ex."""
         L = lib()
         L.sd_set_step_cache.argtypes = [C.c_void_p, C.POINTER(SdCacheParams)]
         L.sd_set_step_cache.restype = C.c_bool
-        if mode is None:
-            ok = L.sd_set_step_cache(self._ctx, None)
+        L.sd_set_step_cache_ex.argtypes = [C.c_void_p, C.POINTER(SdCacheParams), C.POINTER(SdCacheDitParams), C.POINTER(SdSpectrumParams)]
+        L.sd_set_step_cache_ex.restype = C.c_bool
+        p = None if mode is None else SdCacheParams(int(mode), reuse_threshold, start_percent, end_percent, error_decay_rate, bool(use_relative_threshold),
+                                                    bool(reset_error_on_compute))
+        if cache_dit is None and spectrum is None:
+            ok = L.sd_set_step_cache(self._ctx, None if p is None else C.byref(p))
         else:
-            p = SdCacheParams(int(mode), reuse_threshold, start_percent, end_percent, error_decay_rate, bool(use_relative_threshold), bool(reset_error_on_compute))
-            ok = L.sd_set_step_cache(self._ctx, C.byref(p))
+            d = None if cache_dit is None else C.byref(cache_dit_params(**cache_dit))
+            sp = None if spectrum is None else C.byref(spectrum_params(**spectrum))
+            ok = L.sd_set_step_cache_ex(self._ctx, None if p is None else C.byref(p), d, sp)
         if not ok:
             raise EngineError("sd_set_step_cache failed: " + L.sd_last_error().decode())
 
@@ -740,6 +806,34 @@ class Engine:
         L.sd_step_cache_device_passes.argtypes = [C.c_void_p]
         L.sd_step_cache_device_passes.restype = C.c_bool
         return bool(L.sd_step_cache_device_passes(self._ctx))
+
+    def step_cache_kernels_rel(self, inp: np.ndarray, prev_in: np.ndarray, c_in: float = 1.0) -> np.ndarray:
+        """sd_step_cache_kernels_rel: the CacheDIT modes' probe on caller arrays -> (sum |inp * c_in - prev_in|, sum |prev_in|)"""
+        a = np.ascontiguousarray(inp, dtype=np.float32).ravel()
+        pi = np.ascontiguousarray(prev_in, dtype=np.float32).ravel()
+        assert a.size == pi.size
+        sums = np.zeros(2, dtype=np.float32)
+        L = lib()
+        L.sd_step_cache_kernels_rel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
+        L.sd_step_cache_kernels_rel.restype = C.c_bool
+        if not L.sd_step_cache_kernels_rel(self._ctx, _fptr(a), _fptr(pi), a.size, float(c_in), _fptr(sums)):
+            raise EngineError("sd_step_cache_kernels_rel failed: " + L.sd_last_error().decode())
+        return sums
+
+    def spectrum_kernels(self, hist: np.ndarray, weights: np.ndarray, w: float) -> np.ndarray:
+        """sd_spectrum_kernels: Spectrum's forecast on caller arrays, through the ring push and the forecast pass the device sampler uses.  hist [k, n] oldest
+        first, weights [k] -> out [n]"""
+        h = np.ascontiguousarray(hist, dtype=np.float32)
+        wt = np.ascontiguousarray(weights, dtype=np.float32)
+        k, n = h.shape
+        assert wt.size == k
+        out = np.empty(n, dtype=np.float32)
+        L = lib()
+        L.sd_spectrum_kernels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_float, C.c_void_p]
+        L.sd_spectrum_kernels.restype = C.c_bool
+        if not L.sd_spectrum_kernels(self._ctx, _fptr(h), k, n, _fptr(wt), float(w), _fptr(out)):
+            raise EngineError("sd_spectrum_kernels failed: " + L.sd_last_error().decode())
+        return out
 
     def t_to_sigma(self, t: float) -> float:
         """sd_t_to_sigma: the context's denoiser, as the caches' percent_to_sigma uses it (after a trajectory: with that trajectory's flow shift)."""

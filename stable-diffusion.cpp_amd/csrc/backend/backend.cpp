@@ -286,6 +286,9 @@ static void* reg_get_proc(ggml_backend_reg_t, const char* name) {
     if (strcmp(name, "ggml_backend_mi355x_get_stream") == 0) return (void*)ggml_backend_mi355x_get_stream;
     if (strcmp(name, "ggml_backend_mi355x_step_cache_probe") == 0) return (void*)ggml_backend_mi355x_step_cache_probe;
     if (strcmp(name, "ggml_backend_mi355x_step_cache_record") == 0) return (void*)ggml_backend_mi355x_step_cache_record;
+    if (strcmp(name, "ggml_backend_mi355x_step_cache_probe_rel") == 0) return (void*)ggml_backend_mi355x_step_cache_probe_rel;
+    if (strcmp(name, "ggml_backend_mi355x_spectrum_predict") == 0) return (void*)ggml_backend_mi355x_spectrum_predict;
+    if (strcmp(name, "ggml_backend_mi355x_spectrum_push") == 0) return (void*)ggml_backend_mi355x_spectrum_push;
     if (strcmp(name, "ggml_backend_mi355x_hip_library") == 0) return (void*)ggml_backend_mi355x_hip_library;
     if (strcmp(name, "ggml_backend_mi355x_set_device") == 0) return (void*)ggml_backend_mi355x_set_device;
     if (strcmp(name, "ggml_backend_mi355x_get_device") == 0) return (void*)ggml_backend_mi355x_get_device;
@@ -496,6 +499,26 @@ GGML_MI355X_API bool ggml_backend_mi355x_step_cache_record(ggml_backend_t backen
     if (hipSetDevice(c->dev->id) != hipSuccess) return false;
     float* partial = step_cache_scratch(c);
     return partial && mi355x::launch_step_cache_record(c->stream, in, out, prev_in, prev_out, diff, per, k, nb, has_prev_out, partial, stats + 1);
+}
+GGML_MI355X_API bool ggml_backend_mi355x_step_cache_probe_rel(ggml_backend_t backend, const float* x, float c_in, const float* prev_in, int64_t n, float* stats) {
+    if (!backend || !x || !prev_in || !stats) return false;
+    mi355x::BackendCtx* c = (mi355x::BackendCtx*)backend->context;
+    if (hipSetDevice(c->dev->id) != hipSuccess) return false;
+    float* partial = step_cache_scratch(c);
+    return partial && mi355x::launch_step_cache_probe_rel(c->stream, x, c_in, prev_in, n, partial, stats);
+}
+GGML_MI355X_API bool ggml_backend_mi355x_spectrum_predict(ggml_backend_t backend, const float* ring, int64_t slot_stride, const int* order, int k, const float* weights, float w,
+                                                          int64_t n, float* out) {
+    if (!backend || !ring || !order || !weights || !out) return false;
+    mi355x::BackendCtx* c = (mi355x::BackendCtx*)backend->context;
+    if (hipSetDevice(c->dev->id) != hipSuccess) return false;
+    return mi355x::launch_spectrum_predict(c->stream, ring, slot_stride, order, k, weights, w, n, out);
+}
+GGML_MI355X_API bool ggml_backend_mi355x_spectrum_push(ggml_backend_t backend, const float* src, float* dst, int64_t n) {
+    if (!backend || !src || !dst || n < 1) return false;
+    mi355x::BackendCtx* c = (mi355x::BackendCtx*)backend->context;
+    if (hipSetDevice(c->dev->id) != hipSuccess) return false;
+    return hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
 }
 // The HIP runtime THIS plug-in is bound to (a process may hold a second copy, e.g. the one a torch wheel bundles): a companion library that
 // must share streams with the backend — RCCL for the native CFG-pair exchange — is loaded from the same directory.

@@ -536,8 +536,24 @@ struct sdm_ctx_t {
             }
         };
         std::unique_ptr<Cache> cache;
+        // Spectrum (sd_set_step_cache mode 6), made only when it is armed: the ring of the last K denoised tensors (slot stride padded to a multiple of 4 floats so
+        // every slot starts 16-byte aligned) and the tensor a computed step records its `denoised` in and a forecast is written to
+        struct Spectrum {
+            ggml_context* cctx        = nullptr;
+            ggml_backend_buffer_t buf = nullptr;
+            ggml_tensor *ring = nullptr, *denoised = nullptr;
+            int K = 0;
+            int64_t stride = 0;
+            uint64_t serial = 0;
+            ~Spectrum() {
+                if (buf) ggml_backend_buffer_free(buf);
+                if (cctx) ggml_free(cctx);
+            }
+        };
+        std::unique_ptr<Spectrum> spectrum;
         ~SamplerState() {
             cache.reset();
+            spectrum.reset();
             if (buf) ggml_backend_buffer_free(buf);
             if (sctx) ggml_free(sctx);
         }
@@ -551,16 +567,22 @@ struct sdm_ctx_t {
     // step caches (sd_set_step_cache; csrc/host/step_cache.hpp): the request, the runtime of the current / last trajectory, and the runner of the device-resident
     // sampler's skip-step graph (its own cached graph: alternating with the step graph must not rebuild either)
     sdm_cache_params_t cache_params{SDM_CACHE_DISABLED, INFINITY, 0.15f, 0.95f, 1.0f, true, true};
+    sdm_cache_dit_params_t cache_dit_params{8, 0, 0.08f};
+    sdm_spectrum_params_t spectrum_params{0.40f, 3, 1.0f, 2, 0.50f, 4, 0.9f};
     StepCacheRuntime step_cache;
     Runner skip_runner;
     float t_to_sigma(float t) const { return is_flux ? flux_denoiser.t_to_sigma(t) : (is_dit ? flow_denoiser.t_to_sigma(t) : denoiser.t_to_sigma(t)); }
     // whether the request would arm a cache on this family (init_sample_cache_runtime's tests that do not need the ladder)
-    bool step_cache_would_arm() const {
+    // method: the resolved sample method (Spectrum does not serve the two CFG++ methods)
+    bool step_cache_would_arm(int method) const {
         if (!StepCacheRuntime::has_valid_cache_percent_range(cache_params)) return false;
+        if (cache_params.mode == SDM_CACHE_SPECTRUM) return !sample_method_needs_uncond(method);
+        if (StepCacheRuntime::is_cachedit_mode(cache_params.mode)) return is_dit;
         return (cache_params.mode == SDM_CACHE_EASYCACHE && is_dit) || (cache_params.mode == SDM_CACHE_UCACHE && !is_dit);
     }
-    void step_cache_begin_trajectory(const std::vector<float>& sigmas) {
-        step_cache.init(&cache_params, is_dit, !is_dit, [this](float t) { return t_to_sigma(t); }, sigmas);
+    void step_cache_begin_trajectory(const std::vector<float>& sigmas, int method) {
+        step_cache.init(&cache_params, is_dit, !is_dit, [this](float t) { return t_to_sigma(t); }, sigmas, &cache_dit_params, &spectrum_params,
+                        sample_method_needs_uncond(method));
     }
     std::vector<float> pe_cache;  // FLUX rotary table of the last (h, w, n_tokens)
     int pe_h = 0, pe_w = 0;
@@ -1811,6 +1833,7 @@ struct HostDenoise {
     // the group and there is one decision for all its images)
     StepCacheRuntime* sc = nullptr;
     HostStepCacheStore sc_store;
+    std::vector<float> spectrum_ring;  // Spectrum's H_buf: K slots of the group's denoised tensor (SpectrumState keeps which slot is which)
     HostDenoise(sdm_ctx_t* ctx_, const sdm_img_gen_params_t* p_, int W_, int H_, int C_, int nb_)
         : ctx(ctx_), p(p_), W(W_), H(H_), C(C_), nb(nb_), per((size_t)W_ * H_ * C_), use_cfg(p_->sample_params.txt_cfg != 1.0f && p_->uncond.c_crossattn != nullptr),
           noised(per * nb_), cond_out(per * nb_), uncond_out(per * nb_), ts(nb_) {}
@@ -1825,6 +1848,16 @@ struct HostDenoise {
         step_scalings(ctx, sp, sigma, c_skip, c_out, c_in, t);
         for (int b = 0; b < nb; ++b) ts[b] = t;
         for (size_t k = 0; k < n; ++k) noised[k] = x[k] * c_in;  // stable-diffusion.cpp:2662
+        // Spectrum (stable-diffusion.cpp:2667-2679): a predicted call writes the forecast and returns — no forward, no guidance; only the inpainting blend follows
+        const bool spectrum = sc && sc->spectrum_enabled;
+        if (spectrum && sc->spectrum_begin_call(step, sigma)) {
+            float weights[SpectrumState::MAX_K];
+            int order[SpectrumState::MAX_K];
+            const int k = sc->spectrum.predict(weights, order);
+            spectrum_predict_host(spectrum_ring.data(), n, order, k, weights, sc->spectrum.config.w, n, denoised);
+            blend_mask(denoised);
+            return true;
+        }
         const bool cached = sc && sc->armed();
         if (cached) sc->begin_call(step, sigma);  // SampleStepCacheDispatcher step_cache(cache_runtime, step, sigma), stable-diffusion.cpp:2688
         auto run = [&](const sd_condition_t& cd, float* dst) {
@@ -1921,6 +1954,14 @@ struct HostDenoise {
             const float* base = use_cfg ? uncond_out.data() : cond_out.data();
             for (size_t k = 0; k < n; ++k) denoised_uncond[k] = base[k] * c_out + x[k] * c_skip;
         }
+        if (spectrum) {  // SpectrumState::update in front of the mask blend (stable-diffusion.cpp:2885-2887)
+            spectrum_ring.resize((size_t)sc->spectrum.K * n);
+            memcpy(&spectrum_ring[(size_t)sc->spectrum.update() * n], denoised, n * sizeof(float));
+        }
+        blend_mask(denoised);
+        return true;
+    }
+    void blend_mask(float* denoised) const {
         if (p->denoise_mask && p->init_latent) {  // inpainting: denoised * mask + init_latent * (1 - mask), the mask broadcast over channels and images (stable-diffusion.cpp:2888-2890)
             const size_t plane = (size_t)W * H;
             for (int b = 0; b < nb; ++b)
@@ -1933,7 +1974,6 @@ struct HostDenoise {
                     }
                 }
         }
-        return true;
     }
 };
 // img2img (stable-diffusion.cpp:4924-4980): with an init latent and strength < 1 the trajectory starts t_enc = steps * strength steps before the end of the ladder
@@ -1995,7 +2035,7 @@ static bool sample_group(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, 
     }, 2);
     HostDenoise denoise(ctx, p, W, H, C, nb);
     denoise.n_sigmas = (int)sigmas.size();
-    ctx->step_cache_begin_trajectory(sigmas);  // init_sample_cache_runtime per sample() call, stable-diffusion.cpp:2578
+    ctx->step_cache_begin_trajectory(sigmas, method);  // init_sample_cache_runtime per sample() call, stable-diffusion.cpp:2578
     denoise.sc = &ctx->step_cache;
     std::vector<float> denoised(per * nb);
     std::vector<std::vector<float>> step_noise(nb);
@@ -2061,9 +2101,16 @@ struct StepCacheDevice {
     typedef bool (*probe_fn)(ggml_backend_t, const float*, float, const float*, int64_t, float*);
     typedef bool (*record_fn)(ggml_backend_t, const float*, const float*, float*, float*, float*, int64_t, int, int64_t, bool, float*);
     ggml_backend_t backend = nullptr;
+    // the CacheDIT modes' probe, Spectrum's forecast and the push of a computed `denoised` into its ring slot (a device-to-device copy enqueued on the backend stream)
+    typedef bool (*predict_fn)(ggml_backend_t, const float*, int64_t, const int*, int, const float*, float, int64_t, float*);
+    typedef bool (*push_fn)(ggml_backend_t, const float*, float*, int64_t);
     probe_fn probe_k       = nullptr;
     record_fn record_k     = nullptr;
+    probe_fn probe_rel_k   = nullptr;
+    predict_fn predict_k   = nullptr;
+    push_fn push_k         = nullptr;
     bool exports_missing   = false;
+    bool mode_exports_missing = false;  // ... of the three above (an MI355X plug-in older than these modes)
     std::vector<float> a, b, c, d;
     explicit StepCacheDevice(ggml_backend_t be) : backend(be) {
         ggml_backend_dev_t dev = ggml_backend_get_device(be);
@@ -2072,7 +2119,14 @@ struct StepCacheDevice {
             probe_k  = (probe_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_step_cache_probe");
             record_k = (record_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_step_cache_record");
         }
+        if (reg) {
+            probe_rel_k = (probe_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_step_cache_probe_rel");
+            predict_k   = (predict_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_spectrum_predict");
+            push_k      = (push_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_spectrum_push");
+        }
         if (!probe_k || !record_k) probe_k = nullptr, record_k = nullptr;
+        if (!probe_k || !probe_rel_k || !predict_k || !push_k) probe_rel_k = nullptr, predict_k = nullptr, push_k = nullptr;
+        mode_exports_missing = !probe_rel_k && reg && strcmp(ggml_backend_reg_name(reg), "MI355X") == 0;
         // the product backend without its passes is an error, never a quiet fall-back to full-tensor read-backs; any other backend takes the host restatement
         exports_missing = !probe_k && reg && strcmp(ggml_backend_reg_name(reg), "MI355X") == 0;
     }
@@ -2089,6 +2143,38 @@ struct StepCacheDevice {
             sum += std::fabs(m - b[(size_t)i]);
         }
         ggml_backend_tensor_set(stats, &sum, 0, sizeof(float));
+        return true;
+    }
+    // stats[0] = sum |x * c_in - prev_in|, stats[3] = sum |prev_in| over n floats (calculate_residual_diff's two sums)
+    bool probe_rel(ggml_tensor* x, float c_in, ggml_tensor* prev_in, int64_t n, ggml_tensor* stats) {
+        if (probe_rel_k) return probe_rel_k(backend, (const float*)x->data, c_in, (const float*)prev_in->data, n, (float*)stats->data);
+        a.resize((size_t)n), b.resize((size_t)n);
+        ggml_backend_tensor_get(x, a.data(), 0, (size_t)n * sizeof(float));
+        ggml_backend_tensor_get(prev_in, b.data(), 0, (size_t)n * sizeof(float));
+        float sum = 0.0f, mag = 0.0f;
+        for (int64_t i = 0; i < n; ++i) {
+            const float m = a[(size_t)i] * c_in;
+            sum += std::fabs(b[(size_t)i] - m);
+            mag += std::fabs(b[(size_t)i]);
+        }
+        ggml_backend_tensor_set(stats, &sum, 0, sizeof(float));
+        ggml_backend_tensor_set(stats, &mag, 3 * sizeof(float), sizeof(float));
+        return true;
+    }
+    // Spectrum: ring [stride, K] f32, out n floats; order / weights: k host values, oldest first
+    bool spectrum_predict(ggml_tensor* ring, int64_t stride, int K, const int* order, int k, const float* weights, float w, int64_t n, ggml_tensor* out) {
+        if (predict_k) return predict_k(backend, (const float*)ring->data, stride, order, k, weights, w, n, (float*)out->data);
+        a.resize((size_t)(stride * K)), b.resize((size_t)n);
+        ggml_backend_tensor_get(ring, a.data(), 0, a.size() * sizeof(float));
+        spectrum_predict_host(a.data(), (size_t)stride, order, k, weights, w, (size_t)n, b.data());
+        ggml_backend_tensor_set(out, b.data(), 0, (size_t)n * sizeof(float));
+        return true;
+    }
+    bool spectrum_push(ggml_tensor* src, ggml_tensor* ring, int64_t stride, int slot, int64_t n) {
+        if (push_k) return push_k(backend, (const float*)src->data, (float*)ring->data + (int64_t)slot * stride, n);
+        a.resize((size_t)n);
+        ggml_backend_tensor_get(src, a.data(), 0, (size_t)n * sizeof(float));
+        ggml_backend_tensor_set(ring, a.data(), (size_t)slot * (size_t)stride * sizeof(float), (size_t)n * sizeof(float));
         return true;
     }
     // in / prev_in / prev_out [per, nb], out / diff [per, k, nb]: the stored differences, the anchor's previous input / output, stats[1] and stats[2]
@@ -2134,6 +2220,12 @@ struct StepCacheDevice {
 // there, the host state machine (step_cache.hpp) decides; a computed step runs the RECORDING variant of the step graph (noised and eps pass through cache.in /
 // cache.out on their way) followed by the record pass, a skipped step the SKIP-STEP graph (eps_j = noised + diff_j, then the same combine and update).  Inactive
 // steps, and every trajectory without an armed cache, use the plain step graph under its unchanged signature.  Active steps give up the build-ahead overlap.
+// The CacheDIT modes take the same flow with the probe_rel pass (two sums) in place of the probe; their record pass is the same one, its two sums unused.
+//
+// Spectrum: the schedule depends on counters only, so nothing is read back and the build-ahead overlap stays.  A computed call runs the SPECTRUM-RECORDING variant of
+// the step graph (denoised passes through spectrum.denoised on its way into the update) followed by a device-to-device copy into the call's ring slot, enqueued on
+// the backend stream; a predicted call enqueues the forecast pass (kernels/step_cache.hip) into spectrum.denoised — the host has the weights: they depend on taus
+// only — and then the PREDICTED-STEP graph, the tail of the step graph from `denoised` on.  Calls from the stop call on feed nothing any more: plain step graph.
 static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, int nb, float* out, bool* handled) {
     *handled = false;
     const int W = p->width / 8, H = p->height / 8, C = ctx->in_channels();
@@ -2224,10 +2316,38 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
         get_stream_fn gs       = reg ? (get_stream_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_get_stream") : nullptr;
         pair_stream            = gs ? gs(ctx->backend) : nullptr;  // host backends (the CPU oracle in the tests): no stream, calls are synchronous
     }
-    ctx->step_cache_begin_trajectory(sigmas);
+    ctx->step_cache_begin_trajectory(sigmas, method);
     StepCacheRuntime& rt = ctx->step_cache;
     const int ck = both ? 2 : 1;  // conditions per image in the step graph's eps
     StepCacheDevice cache_dev(ctx->backend);
+    if ((rt.is_cachedit() || rt.spectrum_enabled) && cache_dev.mode_exports_missing) {
+        set_error("step cache: the MI355X backend does not export the passes of this mode (ggml_backend_mi355x_step_cache_probe_rel / _spectrum_predict / _spectrum_push)");
+        return false;
+    }
+    if (rt.spectrum_enabled) {
+        const int K = rt.spectrum.K;
+        if (!st.spectrum || st.spectrum->K != K) {
+            st.spectrum.reset(new sdm_ctx_t::SamplerState::Spectrum());
+            auto& ss = *st.spectrum;
+            ggml_init_params ip{0, nullptr, true};
+            ss.cctx     = ggml_init(ip);
+            ss.stride   = ((int64_t)(per * (size_t)nb) + 3) / 4 * 4;
+            ss.ring     = ggml_new_tensor_2d(ss.cctx, GGML_TYPE_F32, ss.stride, K);
+            ss.denoised = ggml_new_tensor_4d(ss.cctx, GGML_TYPE_F32, W, H, C, nb);
+            ggml_set_name(ss.ring, "spectrum.ring");
+            ggml_set_name(ss.denoised, "spectrum.denoised");
+            ss.buf = ggml_backend_alloc_ctx_tensors(ss.cctx, ctx->backend);
+            if (!ss.buf) {
+                st.spectrum.reset();
+                set_error("step cache state allocation failed");
+                return false;
+            }
+            ss.K = K;
+            static std::atomic<uint64_t> g_spectrum_serial{0};
+            ss.serial = ++g_spectrum_serial;
+        }
+    }
+    sdm_ctx_t::SamplerState::Spectrum* ss = rt.spectrum_enabled ? st.spectrum.get() : nullptr;
     if (rt.armed()) {  // (never together with a split CFG pair: sd_sample_latents refuses that)
         if (cache_dev.exports_missing) {
             set_error("step cache: the MI355X backend does not export its step-cache passes (ggml_backend_mi355x_step_cache_probe / _record)");
@@ -2282,6 +2402,10 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
     const std::string cache_tag  = cc ? " cache" + std::to_string(cc->serial) : std::string();
     const std::string record_sig = std::string("record ") + step_sig + cache_tag;  // the recording variant and the skip-step graph: plans of their own
     const std::string skip_sig   = std::string("skip ") + step_sig + cache_tag;
+    const std::string spectrum_tag        = ss ? " spectrum" + std::to_string(ss->serial) : std::string();
+    const std::string spectrum_record_sig = std::string("spectrum-record ") + step_sig + spectrum_tag;
+    const std::string spectrum_step_sig   = std::string("spectrum-step ") + step_sig + spectrum_tag;
+    const bool rel = rt.is_cachedit();
 
     for (int i = 0; i < steps; ++i) {
         const float sigma = sigmas[i], sigma_to = sigmas[i + 1];
@@ -2330,19 +2454,27 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             const bool active  = rt.in_window(sigma);
             const bool measure = active && (pending >= 0 || rt.core().has_prev_input);  // once the pending record is booked the anchor has a previous input, output and difference
             float stats[4]     = {0.f, 0.f, 0.f, 0.f};
-            if (measure && !cache_dev.probe(st.x, c_in, cc->prev_in, (int64_t)(per * (size_t)nb), cc->stats)) {
+            if (measure && !(rel ? cache_dev.probe_rel(st.x, c_in, cc->prev_in, (int64_t)(per * (size_t)nb), cc->stats)
+                                 : cache_dev.probe(st.x, c_in, cc->prev_in, (int64_t)(per * (size_t)nb), cc->stats))) {
                 set_error("step cache: the probe pass could not be enqueued");
                 return false;
             }
-            if (measure || pending >= 0) ggml_backend_tensor_get(cc->stats, stats, 0, sizeof(stats));  // THE synchronisation of an active step
-            if (pending >= 0) book_pending(stats);
+            if (measure || (pending >= 0 && !rel)) ggml_backend_tensor_get(cc->stats, stats, 0, sizeof(stats));  // THE synchronisation of an active step
+            if (pending >= 0) book_pending(stats);  // (the CacheDIT modes book without numbers)
             rt.begin_call(i + 1, sigma);
             if (rt.step_is_active()) {
-                if (rt.before_condition(0) == SC_MEASURE) skip_step = rt.decide(stats[0] / static_cast<float>(per * (size_t)nb));
+                if (rt.before_condition(0) == SC_MEASURE) skip_step = rel ? rt.decide_rel(stats[0], stats[3]) : rt.decide(stats[0] / static_cast<float>(per * (size_t)nb));
                 record_step = !skip_step;
             }
         }
-        // variant 0: the step graph; 1: the same, recording (noised passes through cache.in, eps through cache.out); 2: the skip-step graph (no model call)
+        // Spectrum: this call's record, and whether it is forecast; a computed call that can still feed a forecast records its denoised
+        bool predict_step = false, spectrum_record = false;
+        if (ss) {
+            predict_step    = rt.spectrum_begin_call(i + 1, sigma);
+            spectrum_record = !predict_step && !(rt.spectrum.stop_step > 0 && rt.spectrum.cnt >= rt.spectrum.stop_step);
+        }
+        // variant 0: the step graph; 1: the same, recording (noised passes through cache.in, eps through cache.out); 2: the skip-step graph (no model call);
+        // 3: the step graph with denoised passing through spectrum.denoised; 4: the predicted-step graph (denoised IS spectrum.denoised, no model call)
         auto build_variant = [&](int variant) {
           return [&, variant](GraphCtx& g, std::vector<HostInput>& in) {
             ggml_context* c  = g.ctx;
@@ -2351,10 +2483,11 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             in.push_back({tsc, sc, sizeof(sc)});
             auto S = [&](int k) { return ggml_view_1d(c, tsc, 1, (size_t)k * sizeof(float)); };
             ggml_tensor* xs     = st.x;
-            ggml_tensor* noised = ggml_mul(c, xs, S(0));
+            ggml_tensor* noised = variant == 4 ? nullptr : ggml_mul(c, xs, S(0));
             if (variant == 1) noised = ggml_cpy(c, noised, cc->in);
             ggml_tensor *eps = nullptr, *e3 = nullptr;  // e3: the pair's outputs [per, 2, nb], contiguous
-            if (variant == 2) {  // apply_condition_cache_diff for every condition: eps_j = noised + diff_j
+            if (variant == 4) {  // no model input and no eps: denoised is already in spectrum.denoised
+            } else if (variant == 2) {  // apply_condition_cache_diff for every condition: eps_j = noised + diff_j
                 if (both) {
                     ggml_tensor* flat = ggml_reshape_3d(c, noised, (int64_t)per, 1, nb);
                     ggml_tensor* rep  = ggml_repeat(c, flat, ggml_new_tensor_3d(c, GGML_TYPE_F32, (int64_t)per, 2, nb));
@@ -2380,13 +2513,14 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
                 }
             }
             ggml_tensor* guided = eps;
-            if (both) {  // uncond + s*(cond - uncond), guidance.cpp:171
+            if (both && variant != 4) {  // uncond + s*(cond - uncond), guidance.cpp:171
                 ggml_tensor* ec = ggml_view_3d(c, e3, (int64_t)per, 1, nb, e3->nb[1], e3->nb[2], 0);
                 ggml_tensor* eu = ggml_view_3d(c, e3, (int64_t)per, 1, nb, e3->nb[1], e3->nb[2], e3->nb[1]);
                 ggml_tensor* d  = ggml_mul(c, ggml_sub(c, ec, eu), S(1));
                 guided          = ggml_reshape_4d(c, ggml_add(c, eu, d), W, H, C, nb);
             }
-            ggml_tensor* den = ggml_add(c, ggml_mul(c, guided, S(2)), ggml_mul(c, xs, S(3)));  // stable-diffusion.cpp:2876
+            ggml_tensor* den = variant == 4 ? ss->denoised : ggml_add(c, ggml_mul(c, guided, S(2)), ggml_mul(c, xs, S(3)));  // stable-diffusion.cpp:2876
+            if (variant == 3) den = ggml_cpy(c, den, ss->denoised);
             ggml_tensor* xn;
             if (euler_a) {  // denoiser.hpp:1513-1546
                 xn = ggml_add(c, ggml_mul(c, xs, S(4)), ggml_mul(c, den, S(5)));
@@ -2409,7 +2543,27 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             if (!ctx->skip_runner.compute(build_variant(2), nullptr, 0, skip_sig, {sc})) return false;
             continue;
         }
-        if (!r.compute(build_variant(record_step ? 1 : 0), nullptr, 0, record_step ? record_sig : std::string(step_sig), ptrs)) return false;
+        if (predict_step) {
+            float weights[SpectrumState::MAX_K];
+            int order[SpectrumState::MAX_K];
+            const int k = rt.spectrum.predict(weights, order);
+            if (!cache_dev.spectrum_predict(ss->ring, ss->stride, ss->K, order, k, weights, rt.spectrum.config.w, (int64_t)(per * (size_t)nb), ss->denoised)) {
+                set_error("step cache: the spectrum forecast pass could not be enqueued");
+                return false;
+            }
+            if (!ctx->skip_runner.compute(build_variant(4), nullptr, 0, spectrum_step_sig, {sc})) return false;
+            continue;
+        }
+        if (!r.compute(build_variant(record_step ? 1 : (spectrum_record ? 3 : 0)), nullptr, 0,
+                       record_step ? record_sig : (spectrum_record ? spectrum_record_sig : std::string(step_sig)), ptrs))
+            return false;
+        if (ss) {  // SpectrumState::update: the counters, and — while a forecast can still follow — the tensor
+            const int slot = rt.spectrum.update();
+            if (spectrum_record && !cache_dev.spectrum_push(ss->denoised, ss->ring, ss->stride, slot, (int64_t)(per * (size_t)nb))) {
+                set_error("step cache: the spectrum ring copy could not be enqueued");
+                return false;
+            }
+        }
         if (record_step) {
             if (!cache_dev.record(cc->in, cc->out, cc->prev_in, cc->prev_out, cc->diff, (int64_t)per, ck, nb, rt.core().has_prev_output, cc->stats)) {
                 set_error("step cache: the record pass could not be enqueued");
@@ -2469,7 +2623,128 @@ bool sd_set_step_cache(sdm_ctx_t* ctx, const sdm_cache_params_t* params) {
     else
         sdm_cache_params_init(&ctx->cache_params);
     if (ctx->cache_params.mode == SDM_CACHE_DISABLED && ctx->sstate) ctx->sstate->cache.reset();
+    if (ctx->cache_params.mode != SDM_CACHE_SPECTRUM && ctx->sstate) ctx->sstate->spectrum.reset();
+    sdm_cache_dit_params_init(&ctx->cache_dit_params);  // (sd_set_step_cache_ex overwrites them afterwards)
+    sdm_spectrum_params_init(&ctx->spectrum_params);
     return true;
+}
+void sdm_cache_dit_params_init(sdm_cache_dit_params_t* p) { *p = sdm_cache_dit_params_t{8, 0, 0.08f}; }                       // sd_cache_params_init, stable-diffusion.cpp:3514-3516
+void sdm_spectrum_params_init(sdm_spectrum_params_t* p) { *p = sdm_spectrum_params_t{0.40f, 3, 1.0f, 2, 0.50f, 4, 0.9f}; }  // :3524-3530
+bool sd_set_step_cache_ex(sdm_ctx_t* ctx, const sdm_cache_params_t* params, const sdm_cache_dit_params_t* cache_dit, const sdm_spectrum_params_t* spectrum) {
+    if (cache_dit && std::isnan(cache_dit->residual_diff_threshold)) {
+        set_error("sd_set_step_cache_ex: NaN parameter");
+        return false;
+    }
+    if (spectrum && (std::isnan(spectrum->w) || std::isnan(spectrum->lam) || std::isnan(spectrum->flex_window) || std::isnan(spectrum->stop_percent))) {
+        set_error("sd_set_step_cache_ex: NaN parameter");
+        return false;
+    }
+    if (spectrum && (spectrum->m < 0 || spectrum->m > SpectrumState::MAX_K - 1)) {
+        set_error("sd_set_step_cache_ex: spectrum m must be 0 .. 15 (the history holds max(m + 1, 6) <= 16 tensors)");
+        return false;
+    }
+    if (!sd_set_step_cache(ctx, params)) return false;
+    if (cache_dit) ctx->cache_dit_params = *cache_dit;
+    if (spectrum) ctx->spectrum_params = *spectrum;
+    return true;
+}
+bool sd_spectrum_schedule(const sdm_spectrum_params_t* params, int n_calls, uint8_t* predicted) {
+    if (!params || n_calls < 0 || (n_calls > 0 && !predicted) || params->m < 0 || params->m > SpectrumState::MAX_K - 1) {
+        set_error("sd_spectrum_schedule: bad arguments");
+        return false;
+    }
+    SpectrumState s;
+    s.init(SpectrumConfig{params->w, params->m, params->lam, params->window_size, params->flex_window, params->warmup_steps, params->stop_percent}, (size_t)n_calls);
+    float weights[SpectrumState::MAX_K];
+    int order[SpectrumState::MAX_K];
+    for (int i = 0; i < n_calls; ++i) {
+        predicted[i] = s.should_predict() ? 1 : 0;
+        if (predicted[i])
+            s.predict(weights, order);
+        else
+            s.update();
+    }
+    return true;
+}
+bool sd_spectrum_weights(const sdm_spectrum_params_t* params, const float* taus, int k, float tau_at, float* weights) {
+    if (!params || !taus || !weights || k < 1 || k > SpectrumState::MAX_K || params->m < 0 || params->m > SpectrumState::MAX_K - 1) {
+        set_error("sd_spectrum_weights: bad arguments");
+        return false;
+    }
+    SpectrumState::weights(SpectrumConfig{params->w, params->m, params->lam, params->window_size, params->flex_window, params->warmup_steps, params->stop_percent}, taus, k, tau_at,
+                           weights);
+    return true;
+}
+bool sd_spectrum_kernels(sdm_ctx_t* ctx, const float* hist, int k, int64_t n, const float* weights, float w, float* out) {
+    if (!hist || !weights || !out || k < 2 || k > SpectrumState::MAX_K || n < 1) {
+        set_error("sd_spectrum_kernels: bad arguments");
+        return false;
+    }
+    ggml_init_params ip{0, nullptr, true};
+    ggml_context* c       = ggml_init(ip);
+    const int64_t stride  = (n + 3) / 4 * 4;
+    ggml_tensor* t_ring   = ggml_new_tensor_2d(c, GGML_TYPE_F32, stride, k);
+    ggml_tensor* t_src    = ggml_new_tensor_1d(c, GGML_TYPE_F32, n);
+    ggml_tensor* t_out    = ggml_new_tensor_1d(c, GGML_TYPE_F32, n);
+    ggml_backend_buffer_t buf = ggml_backend_alloc_ctx_tensors(c, ctx->backend);
+    if (!buf) {
+        ggml_free(c);
+        set_error("sd_spectrum_kernels: allocation failed");
+        return false;
+    }
+    // the sampler's path: every tensor arrives in its ring slot through the push, rotated so that the ring wraps (slot of the j-th oldest = (j + 1) % k)
+    StepCacheDevice dev(ctx->backend);
+    bool ok = !dev.mode_exports_missing;
+    int order[SpectrumState::MAX_K];
+    for (int j = 0; ok && j < k; ++j) {
+        order[j] = (j + 1) % k;
+        ggml_backend_tensor_set(t_src, hist + (size_t)j * (size_t)n, 0, (size_t)n * sizeof(float));
+        ok = dev.spectrum_push(t_src, t_ring, stride, order[j], n);
+        ggml_backend_synchronize(ctx->backend);  // t_src is overwritten by the next upload
+    }
+    ok = ok && dev.spectrum_predict(t_ring, stride, k, order, k, weights, w, n, t_out);
+    ggml_backend_synchronize(ctx->backend);
+    if (ok)
+        ggml_backend_tensor_get(t_out, out, 0, (size_t)n * sizeof(float));
+    else
+        set_error("sd_spectrum_kernels: the passes could not be run");
+    ggml_backend_buffer_free(buf);
+    ggml_free(c);
+    return ok;
+}
+bool sd_step_cache_kernels_rel(sdm_ctx_t* ctx, const float* in, const float* prev_in, int64_t n, float c_in, float* sums) {
+    if (!in || !prev_in || !sums || n < 1) {
+        set_error("sd_step_cache_kernels_rel: bad arguments");
+        return false;
+    }
+    ggml_init_params ip{0, nullptr, true};
+    ggml_context* c    = ggml_init(ip);
+    ggml_tensor* t_in  = ggml_new_tensor_1d(c, GGML_TYPE_F32, n);
+    ggml_tensor* t_pin = ggml_new_tensor_1d(c, GGML_TYPE_F32, n);
+    ggml_tensor* t_st  = ggml_new_tensor_1d(c, GGML_TYPE_F32, 4);
+    ggml_backend_buffer_t buf = ggml_backend_alloc_ctx_tensors(c, ctx->backend);
+    if (!buf) {
+        ggml_free(c);
+        set_error("sd_step_cache_kernels_rel: allocation failed");
+        return false;
+    }
+    const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+    ggml_backend_tensor_set(t_in, in, 0, (size_t)n * sizeof(float));
+    ggml_backend_tensor_set(t_pin, prev_in, 0, (size_t)n * sizeof(float));
+    ggml_backend_tensor_set(t_st, zero, 0, sizeof(zero));
+    StepCacheDevice dev(ctx->backend);
+    const bool ok = !dev.mode_exports_missing && dev.probe_rel(t_in, c_in, t_pin, n, t_st);
+    if (ok) {
+        float st4[4];
+        ggml_backend_tensor_get(t_st, st4, 0, sizeof(st4));  // (synchronises the stream the pass was enqueued on)
+        sums[0] = st4[0], sums[1] = st4[3];
+    } else {
+        ggml_backend_synchronize(ctx->backend);
+        set_error("sd_step_cache_kernels_rel: the pass could not be run (size beyond the summation-depth bound?)");
+    }
+    ggml_backend_buffer_free(buf);
+    ggml_free(c);
+    return ok;
 }
 int sd_step_cache_trace(sdm_ctx_t* ctx, sdm_cache_step_t* out, int capacity) {
     const std::vector<sdm_cache_step_t>& t = ctx->step_cache.trace;
@@ -2530,7 +2805,7 @@ bool sd_sample_latents(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, float* out
     const int group  = p->device_batch > 0 ? p->device_batch : p->batch_count;
     const double t0  = now_ms();
     ctx->stats.steps_skipped = 0;
-    if (ctx->step_cache_would_arm()) {
+    if (ctx->step_cache_would_arm(resolve_sample_method(ctx, p->sample_params.sample_method))) {
         const sdm_sample_params_t& sp = p->sample_params;
         // the reference re-enters its cache with the cond pointer a second time inside a skip-layer step; that is not restated: refused
         if (ctx->is_dit && !ctx->is_flux && sp.slg_scale != 0.0f && sp.slg_layers && sp.slg_layer_count > 0) {

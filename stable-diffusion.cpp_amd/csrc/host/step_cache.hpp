@@ -1,6 +1,8 @@
-// step_cache.hpp — the reference's condition-level step caches, restated on the host: EasyCache (DiT families; src/runtime/easycache.hpp) and UCache (UNet
-// families; src/runtime/ucache.hpp), their set-up (src/runtime/sample-cache.cpp:5-103, 176-212) and the per-step dispatcher (sample-cache.cpp:214-291) the
-// denoise call wraps around every model forward (src/stable-diffusion.cpp:2688, 2779-2795, 2817).
+// step_cache.hpp — the reference's step caches, restated on the host: the condition-level caches EasyCache (DiT families; src/runtime/easycache.hpp), UCache (UNet
+// families; src/runtime/ucache.hpp) and CacheDIT (DiT families; CacheDitConditionState, src/runtime/cache_dit.hpp:638-894 — what `dbcache`, `taylorseer` and
+// `cache-dit` all run through), their set-up (src/runtime/sample-cache.cpp:5-146, 176-212) and the per-step dispatcher (sample-cache.cpp:214-291) the denoise call
+// wraps around every model forward (src/stable-diffusion.cpp:2688, 2779-2795, 2817); and Spectrum (src/runtime/spectrum.hpp), which sits beside that dispatcher and
+// replaces whole denoise calls (stable-diffusion.cpp:2583-2590, 2667-2679, 2885-2887).
 //
 // Both caches keep, per condition, diff = output - input of the last COMPUTED step (src/runtime/condition_cache_utils.hpp:10-36) and, for the anchor condition, the
 // previous input and output.  In front of the anchor's forward they measure mean |input - prev_input|, scale it by the last observed output-change / input-change
@@ -11,7 +13,8 @@
 // split where the reference touches data: before_condition() says what the caller has to do (compute / apply the diff / measure the input change and ask
 // decide()), after_condition() takes the two means the reference accumulates in its own loops.  Order of operations as in the reference, line for line.
 //
-// Out of scope: DBCache / TaylorSeer / CacheDIT (src/runtime/cache_dit.hpp) and Spectrum reach into the model's blocks.
+// CacheDIT keeps the same arrays and hooks; its decision is the relative L1 change of the anchor's input, sum |prev_in - in| / (sum |prev_in| + 1e-6), against a fixed
+// threshold.  The block-level CacheDitState of the same file is used nowhere by the reference's sampler and is not restated.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -264,11 +267,221 @@ struct UCacheState : ConditionCacheState {
     }
 };
 
-// SampleCacheRuntime + SampleStepCacheDispatcher (sample-cache.cpp) for the two modes, and the trace of include/sd-mi355x.h
+
+// DBCacheConfig (cache_dit.hpp) restricted to what CacheDitConditionState reads on a path that changes a trajectory.  NOT kept, because they have no effect there:
+// max_warmup_steps, the steps-computation mask, max_cached_steps and max_continuous_cached_steps (begin_step, cache_dit.hpp:737-760, sets step_active = true BEFORE
+// it tests them and then only returns), and TaylorSeerConfig (taylor_state is updated in after_condition, :879-881, and never read)
+struct CacheDitConfig {
+    bool enabled                  = false;
+    int Fn_compute_blocks         = 8;
+    int Bn_compute_blocks         = 0;
+    float residual_diff_threshold = 0.08f;
+};
+struct CacheDitCondState : ConditionCacheState {
+    CacheDitConfig config;
+    float accumulated_residual_diff = 0.0f;
+    void reset_runtime() {  // cache_dit.hpp:668-681
+        CacheDitCondState fresh;
+        fresh.config = config, fresh.initialized = initialized, fresh.start_sigma = start_sigma, fresh.end_sigma = end_sigma;
+        *this = fresh;
+    }
+    void init(const CacheDitConfig& cfg) {  // cache_dit.hpp:683-692
+        config      = cfg;
+        initialized = cfg.enabled;
+        reset_runtime();
+    }
+    // Rule (cache_dit.hpp:694-716): the window is FIXED at 15 % .. 95 % of the ladder, whatever start_percent / end_percent say — the sigmas of the steps at
+    // (size_t)(percent * n_steps), clamped to the last step, larger one first
+    void set_sigmas(const std::vector<float>& sigmas) {
+        if (!initialized || sigmas.size() < 2) return;
+        const size_t n_steps = sigmas.size() - 1;
+        const size_t a       = std::min(static_cast<size_t>(0.15f * n_steps), n_steps - 1);
+        const size_t b       = std::min(static_cast<size_t>(0.95f * n_steps), n_steps - 1);
+        start_sigma          = sigmas[a];
+        end_sigma            = sigmas[b];
+        if (start_sigma < end_sigma) std::swap(start_sigma, end_sigma);
+    }
+    void begin_step(int step_index, float sigma) {  // cache_dit.hpp:722-761
+        if (!initialized || step_index == current_step_index) return;
+        current_step_index = step_index;
+        skip_current_step  = false;
+        step_active        = in_window(sigma);
+    }
+    // Rule (cache_dit.hpp:847-857): more front blocks "computed" loosen the threshold by 2 % each around 8, back blocks tighten it by 3 % each
+    float effective_threshold() const {
+        float t = config.residual_diff_threshold;
+        if (config.Fn_compute_blocks > 0) t *= std::max(0.5f, std::min(2.0f, 1.0f + 0.02f * (config.Fn_compute_blocks - 8)));
+        if (config.Bn_compute_blocks > 0) t *= std::max(0.5f, std::min(1.0f, 1.0f - 0.03f * config.Bn_compute_blocks));
+        return t;
+    }
+    // The rest of before_condition (cache_dit.hpp:839-870), given the two sums of calculate_residual_diff (:293-306) measured by the caller
+    bool decide(float sum_diff, float sum_abs) {
+        trace_rate        = sum_diff / (sum_abs + 1e-6f);
+        trace_threshold   = effective_threshold();
+        trace_accumulated = accumulated_residual_diff;
+        if (!(trace_rate < trace_threshold)) return false;
+        skip_current_step = true;
+        ++total_steps_skipped;
+        accumulated_residual_diff += trace_rate;
+        trace_accumulated = accumulated_residual_diff;
+        return true;
+    }
+    // after_condition (cache_dit.hpp:873-882) + update_cache (:776-795): the caller stores the difference, prev_input and prev_output of every condition; only the
+    // anchor's previous input is ever read
+    void after_condition(int cond) {
+        if (!step_is_active()) return;
+        has_diff[cond] = true;
+        if (cond == anchor_condition) has_prev_input = has_prev_output = true;
+    }
+};
+
+// Spectrum (src/runtime/spectrum.hpp): per denoise call, should_predict() decides from counters alone; a predicted call is a ridge-regularised Chebyshev fit through
+// the last K denoised tensors, evaluated at this call's tau and blended with a first-order extrapolation; a computed call ends with update().  The tensors live
+// with the loop that owns the data (a ring of K slots); this state keeps the counters, the taus of the stored calls and which slot holds which.
+struct SpectrumConfig {  // spectrum.hpp:11-19
+    float w            = 0.40f;
+    int m              = 3;
+    float lam          = 1.0f;
+    int window_size    = 2;
+    float flex_window  = 0.50f;
+    int warmup_steps   = 4;
+    float stop_percent = 0.9f;
+};
+struct SpectrumState {
+    static constexpr int MAX_K = 16;
+    SpectrumConfig config;
+    int cnt                 = 0;
+    int num_cached          = 0;
+    float curr_ws           = 2.0f;
+    int K                   = 6;
+    int stop_step           = 0;
+    int total_steps_skipped = 0;
+    std::vector<float> T_buf;  // taus of the stored calls, oldest first (H_buf's tensors: the caller's ring)
+    int head = 0;              // ring slot the next update() writes
+    void init(const SpectrumConfig& cfg, size_t total_steps) {  // spectrum.hpp:33-43
+        config              = cfg;
+        cnt                 = 0;
+        num_cached          = 0;
+        curr_ws             = (float)cfg.window_size;
+        K                   = std::max(cfg.m + 1, 6);
+        stop_step           = (int)(cfg.stop_percent * (float)total_steps);
+        total_steps_skipped = 0;
+        T_buf.clear();
+        head = 0;
+    }
+    static float taus(int step_cnt) { return (step_cnt / 50.0f) * 2.0f - 1.0f; }
+    int stored() const { return (int)T_buf.size(); }
+    int slot(int j) const { return ((head - stored() + j) % K + K) % K; }  // ring slot of the j-th oldest stored tensor
+    bool past_warmup_before_stop() const { return cnt >= config.warmup_steps && !(stop_step > 0 && cnt >= stop_step); }
+    bool should_predict() const {  // spectrum.hpp:49-59
+        if (!past_warmup_before_stop() || stored() < 2) return false;
+        const int ws = std::max(1, (int)std::floor(curr_ws));
+        return (num_cached + 1) % ws != 0;
+    }
+    // update (spectrum.hpp:61-75) without the copy: returns the ring slot the caller writes `denoised` to
+    int update() {
+        const int at = head;
+        head         = (head + 1) % K;
+        T_buf.push_back(taus(cnt));
+        while ((int)T_buf.size() > K) T_buf.erase(T_buf.begin());
+        if (cnt >= config.warmup_steps) curr_ws += config.flex_window;
+        num_cached = 0;
+        cnt++;
+        return at;
+    }
+    // The weights of predict (spectrum.hpp:79-126): Chebyshev design matrix X by recurrence at the stored taus, x* at tau_at, (XtX + lam I) v = x* through Cholesky
+    // — with ONE retry after adding 1e-4 * trace / M1 to the diagonal when a pivot is not positive — and weights = X v.  f32, every operation rounded on its own.
+    static void weights(const SpectrumConfig& cfg, const float* T, int k, float tau_at, float* out) {
+        const int M1 = cfg.m + 1;
+        std::vector<float> X((size_t)k * M1), x_star(M1), XtX((size_t)M1 * M1, 0.0f), L((size_t)M1 * M1, 0.0f), v(M1, 0.0f), y(M1, 0.0f);
+        auto cheb = [M1](float t, float* row) {
+            row[0] = 1.0f;
+            if (M1 > 1) row[1] = t;
+            for (int j = 2; j < M1; j++) row[j] = 2.0f * t * row[j - 1] - row[j - 2];
+        };
+        for (int i = 0; i < k; i++) cheb(T[i], &X[(size_t)i * M1]);
+        cheb(tau_at, x_star.data());
+        for (int i = 0; i < M1; i++)
+            for (int j = 0; j < M1; j++) {
+                float sum = 0.0f;
+                for (int q = 0; q < k; q++) sum += X[(size_t)q * M1 + i] * X[(size_t)q * M1 + j];
+                XtX[(size_t)i * M1 + j] = sum + (i == j ? cfg.lam : 0.0f);
+            }
+        auto cholesky = [&]() {  // spectrum.hpp:150-168; false at the first non-positive pivot (L keeps what was written until then)
+            std::fill(L.begin(), L.end(), 0.0f);
+            for (int i = 0; i < M1; i++)
+                for (int j = 0; j <= i; j++) {
+                    float sum = 0.0f;
+                    for (int q = 0; q < j; q++) sum += L[(size_t)i * M1 + q] * L[(size_t)j * M1 + q];
+                    if (i == j) {
+                        const float diag = XtX[(size_t)i * M1 + i] - sum;
+                        if (diag <= 0.0f) return false;
+                        L[(size_t)i * M1 + j] = std::sqrt(diag);
+                    } else {
+                        L[(size_t)i * M1 + j] = (XtX[(size_t)i * M1 + j] - sum) / L[(size_t)j * M1 + j];
+                    }
+                }
+            return true;
+        };
+        if (!cholesky()) {
+            float trace = 0.0f;
+            for (int i = 0; i < M1; i++) trace += XtX[(size_t)i * M1 + i];
+            for (int i = 0; i < M1; i++) XtX[(size_t)i * M1 + i] += 1e-4f * trace / M1;
+            cholesky();
+        }
+        for (int i = 0; i < M1; i++) {  // cholesky_solve, spectrum.hpp:170-184
+            float sum = 0.0f;
+            for (int j = 0; j < i; j++) sum += L[(size_t)i * M1 + j] * y[j];
+            y[i] = (x_star[i] - sum) / L[(size_t)i * M1 + i];
+        }
+        for (int i = M1 - 1; i >= 0; i--) {
+            float sum = 0.0f;
+            for (int j = i + 1; j < M1; j++) sum += L[(size_t)j * M1 + i] * v[j];
+            v[i] = (y[i] - sum) / L[(size_t)i * M1 + i];
+        }
+        for (int q = 0; q < k; q++) {
+            out[q] = 0.0f;
+            for (int j = 0; j < M1; j++) out[q] += X[(size_t)q * M1 + j] * v[j];
+        }
+    }
+    // predict (spectrum.hpp:77-147) without the element loop: the weights of this call and the ring slots they go with, oldest first; then the counters
+    int predict(float* w_out, int* slot_out) {
+        const int k = stored();
+        weights(config, T_buf.data(), k, taus(cnt), w_out);
+        for (int j = 0; j < k; j++) slot_out[j] = slot(j);
+        num_cached++;
+        total_steps_skipped++;
+        cnt++;
+        return k;
+    }
+};
+// the element loop of predict (spectrum.hpp:134-142) over ring slots `order` (oldest first) of `stride` floats each
+inline void spectrum_predict_host(const float* ring, size_t stride, const int* order, int k, const float* weights, float w, size_t n, float* out) {
+    const float w_taylor = 1.0f - w;
+    const float *h_last = ring + (size_t)order[k - 1] * stride, *h_prev = ring + (size_t)order[k - 2] * stride;
+    for (size_t f = 0; f < n; ++f) {
+        float pc = 0.0f;
+        for (int j = 0; j < k; ++j) {
+            const float m = weights[j] * ring[(size_t)order[j] * stride + f];
+            pc            = pc + m;
+        }
+        const float d  = h_last[f] - h_prev[f];
+        const float e  = 0.5f * d;
+        const float pt = h_last[f] + e;
+        const float a  = w_taylor * pt;
+        const float b  = w * pc;
+        out[f]         = a + b;
+    }
+}
+
+// SampleCacheRuntime + SampleStepCacheDispatcher (sample-cache.cpp), and the trace of include/sd-mi355x.h
 struct StepCacheRuntime {
-    int mode = SDM_CACHE_DISABLED;  // what is ARMED for this trajectory (SampleCacheMode)
+    int mode = SDM_CACHE_DISABLED;  // the CONDITION-LEVEL cache armed for this trajectory (SampleCacheMode; the three CacheDIT modes keep their own number)
     EasyCacheState easycache;
     UCacheState ucache;
+    CacheDitCondState cachedit;
+    SpectrumState spectrum;
+    bool spectrum_enabled = false;  // SampleCacheRuntime::spectrum_enabled: beside `mode`, never together with it
     std::string status = "disabled";
     std::vector<sdm_cache_step_t> trace;
     int step_index = -1;  // of the current denoise call
@@ -282,30 +495,61 @@ struct StepCacheRuntime {
     }
     // Rule (sample-cache.cpp:29-39): 0 <= start < end <= 1 (which already keeps start below 1 and end above 0; NaN fails every comparison)
     static bool has_valid_cache_percent_range(const sdm_cache_params_t& p) {
-        const bool ranged = p.mode == SDM_CACHE_EASYCACHE || p.mode == SDM_CACHE_UCACHE;
+        const bool ranged = p.mode >= SDM_CACHE_EASYCACHE && p.mode <= SDM_CACHE_SPECTRUM;  // (sample-cache.cpp:185: checked in front of every mode)
         return !ranged || (p.start_percent >= 0.0f && p.start_percent < p.end_percent && p.end_percent <= 1.0f && p.start_percent < 1.0f && p.end_percent > 0.0f);
     }
     // init_sample_cache_runtime (sample-cache.cpp:176-212) with init_easycache_runtime (:41-67) / init_ucache_runtime (:69-103): the range is checked first, then
     // the family (EasyCache: DiT only, UCache: UNet only); a request that cannot be served leaves the trajectory uncached (the reference logs a warning; here
     // `status` keeps the reason).  UCache clamps error_decay_rate to [0, 1] and takes its window from the ladder.
-    void init(const sdm_cache_params_t* params, bool is_dit, bool is_unet, const std::function<float(float)>& t_to_sigma, const std::vector<float>& sigmas) {
+    // The CacheDIT modes (init_cachedit_runtime, :105-146): DiT only, window from the ladder.  Spectrum (init_spectrum_runtime, :148-174): UNet and DiT alike, and
+    // switched off again for the two CFG++ sample methods (stable-diffusion.cpp:2583-2590), which need an unconditional prediction a forecast does not have.
+    static bool is_cachedit_mode(int m) { return m == SDM_CACHE_DBCACHE || m == SDM_CACHE_TAYLORSEER || m == SDM_CACHE_CACHE_DIT; }
+    void init(const sdm_cache_params_t* params, bool is_dit, bool is_unet, const std::function<float(float)>& t_to_sigma, const std::vector<float>& sigmas,
+              const sdm_cache_dit_params_t* dit_params = nullptr, const sdm_spectrum_params_t* spectrum_params = nullptr, bool method_needs_uncond = false) {
         mode = SDM_CACHE_DISABLED;
         trace.clear();
-        step_index = -1;
-        easycache  = EasyCacheState();
-        ucache     = UCacheState();
-        status     = "disabled";
+        step_index       = -1;
+        easycache        = EasyCacheState();
+        ucache           = UCacheState();
+        cachedit         = CacheDitCondState();
+        spectrum         = SpectrumState();
+        spectrum_enabled = false;
+        status           = "disabled";
         if (!params || params->mode == SDM_CACHE_DISABLED) return;
-        const bool easy = params->mode == SDM_CACHE_EASYCACHE;
-        if (!easy && params->mode != SDM_CACHE_UCACHE)
+        const bool easy = params->mode == SDM_CACHE_EASYCACHE, dit_mode = is_cachedit_mode(params->mode), spec = params->mode == SDM_CACHE_SPECTRUM;
+        if (!easy && params->mode != SDM_CACHE_UCACHE && !dit_mode && !spec)
             status = "not armed: unknown cache mode";
         else if (!has_valid_cache_percent_range(*params))
             status = "not armed: the percent range is not valid (0 <= start < end <= 1)";
-        else if (easy ? !is_dit : !is_unet)
+        else if (dit_mode && !is_dit)
+            status = "not armed: dbcache / taylorseer / cache-dit serve the DiT families only";
+        else if (spec && method_needs_uncond)
+            status = "not armed: spectrum does not serve the CFG++ sample methods";
+        else if (!spec && !dit_mode && (easy ? !is_dit : !is_unet))
             status = easy ? "not armed: easycache serves the DiT families only" : "not armed: ucache serves the UNet families only";
-        else if (!t_to_sigma)
+        else if (!spec && !dit_mode && !t_to_sigma)
             status = "not armed: the family has no t_to_sigma";
         if (status != "disabled") return;
+        if (spec) {
+            SpectrumConfig config;
+            if (spectrum_params)
+                config = SpectrumConfig{spectrum_params->w, spectrum_params->m, spectrum_params->lam, spectrum_params->window_size, spectrum_params->flex_window,
+                                        spectrum_params->warmup_steps, spectrum_params->stop_percent};
+            spectrum.init(config, sigmas.size() > 0 ? sigmas.size() - 1 : 0);
+            spectrum_enabled = true;
+            status           = "spectrum";
+            return;
+        }
+        if (dit_mode) {
+            CacheDitConfig config;
+            config.enabled = true;
+            if (dit_params) config.Fn_compute_blocks = dit_params->Fn_compute_blocks, config.Bn_compute_blocks = dit_params->Bn_compute_blocks, config.residual_diff_threshold = dit_params->residual_diff_threshold;
+            cachedit.init(config);
+            cachedit.set_sigmas(sigmas);
+            mode   = params->mode;
+            status = mode == SDM_CACHE_DBCACHE ? "dbcache" : (mode == SDM_CACHE_TAYLORSEER ? "taylorseer" : "cache-dit");
+            return;
+        }
         const float threshold = get_cache_reuse_threshold(*params);
         if (easy) {
             EasyCacheConfig config{true, threshold, params->start_percent, params->end_percent};
@@ -324,9 +568,23 @@ struct StepCacheRuntime {
         status = easy ? "easycache" : "ucache";
     }
     bool armed() const { return mode != SDM_CACHE_DISABLED; }
-    ConditionCacheState& core() { return mode == SDM_CACHE_UCACHE ? (ConditionCacheState&)ucache : (ConditionCacheState&)easycache; }
-    const ConditionCacheState& core() const { return mode == SDM_CACHE_UCACHE ? (const ConditionCacheState&)ucache : (const ConditionCacheState&)easycache; }
-    int total_steps_skipped() const { return armed() ? core().total_steps_skipped : 0; }
+    bool is_cachedit() const { return is_cachedit_mode(mode); }
+    ConditionCacheState& core() { return const_cast<ConditionCacheState&>(static_cast<const StepCacheRuntime*>(this)->core()); }
+    const ConditionCacheState& core() const {
+        if (is_cachedit()) return cachedit;
+        return mode == SDM_CACHE_UCACHE ? (const ConditionCacheState&)ucache : (const ConditionCacheState&)easycache;
+    }
+    int total_steps_skipped() const { return armed() ? core().total_steps_skipped : (spectrum_enabled ? spectrum.total_steps_skipped : 0); }
+    // Spectrum's record of one denoise call, pushed in front of its decision; returns should_predict()
+    bool spectrum_begin_call(int step, float sigma_) {
+        sdm_cache_step_t r{};
+        r.step    = step;
+        r.sigma   = sigma_;
+        r.active  = spectrum.past_warmup_before_stop();
+        r.skipped = spectrum.should_predict();
+        trace.push_back(r);
+        return r.skipped;
+    }
     bool in_window(float s) const { return armed() && core().in_window(s); }
 
     // SampleStepCacheDispatcher's constructor (sample-cache.cpp:214-233): one per denoise call; step is what the sampler hands the call (i + 1, negated for the
@@ -337,8 +595,10 @@ struct StepCacheRuntime {
         if (armed() && step_index >= 0) {
             if (mode == SDM_CACHE_EASYCACHE)
                 easycache.begin_step(step_index, sigma);
-            else
+            else if (mode == SDM_CACHE_UCACHE)
                 ucache.begin_step(step_index, sigma);
+            else
+                cachedit.begin_step(step_index, sigma);
         }
         sdm_cache_step_t r{};
         r.step   = step;
@@ -350,8 +610,19 @@ struct StepCacheRuntime {
     bool is_step_skipped() const { return armed() && step_index >= 0 && core().is_step_skipped(); }
     StepCacheAction before_condition(int cond) {  // sample-cache.cpp:235-254
         if (!armed() || step_index < 0) return SC_COMPUTE;
+        if (is_cachedit()) return ConditionCacheState::before_condition(cachedit, cond, sigma, step_index);
         return mode == SDM_CACHE_EASYCACHE ? ConditionCacheState::before_condition(easycache, cond, sigma, step_index)
                                            : ConditionCacheState::before_condition(ucache, cond, sigma, step_index);
+    }
+    // the CacheDIT modes' decision from the two sums; the trace shows the relative residual diff as input_change and rate
+    bool decide_rel(float sum_diff, float sum_abs, sdm_cache_step_t* rec = nullptr) {
+        const bool skip     = cachedit.decide(sum_diff, sum_abs);
+        sdm_cache_step_t& r = rec ? *rec : trace.back();
+        r.input_change = r.rate = cachedit.trace_rate;
+        r.accumulated  = cachedit.trace_accumulated;
+        r.threshold    = cachedit.trace_threshold;
+        r.skipped      = skip;
+        return skip;
     }
     bool decide(float input_change, sdm_cache_step_t* rec = nullptr) {
         const bool skip = mode == SDM_CACHE_EASYCACHE ? easycache.decide(input_change) : ucache.decide(input_change);
@@ -366,6 +637,7 @@ struct StepCacheRuntime {
     // sample-cache.cpp:256-276; rec: the trace record of the step the measurements belong to (the device sampler delivers them one step late)
     void after_condition(int cond, float output_change, float mean_abs, sdm_cache_step_t* rec = nullptr) {
         if (!armed() || step_index < 0) return;
+        if (is_cachedit()) return cachedit.after_condition(cond);  // (no output metrics: the trace keeps 0)
         const bool anchor = step_is_active() && cond == core().anchor_condition;
         if (anchor) {
             sdm_cache_step_t& r = rec ? *rec : trace.back();
@@ -404,9 +676,9 @@ struct HostStepCacheStore {
         float output_change = 0.0f, norm = 0.0f;
         if (cond == rt.core().anchor_condition) {
             prev_input.assign(in, in + ne);
-            if (rt.core().has_prev_output && prev_output.size() == ne) output_change = mean_abs_diff(out, prev_output.data(), ne);
+            if (!rt.is_cachedit() && rt.core().has_prev_output && prev_output.size() == ne) output_change = mean_abs_diff(out, prev_output.data(), ne);
             prev_output.assign(out, out + ne);
-            norm = mean_abs(out, ne);
+            if (!rt.is_cachedit()) norm = mean_abs(out, ne);
         }
         rt.after_condition(cond, output_change, norm);
     }
@@ -417,7 +689,13 @@ struct HostStepCacheStore {
     // before_condition for one condition: true = `out` was rebuilt from the cache, the forward must not run
     bool before_condition(StepCacheRuntime& rt, int cond, const float* in, float* out, size_t ne) {
         StepCacheAction a = rt.before_condition(cond);
-        if (a == SC_MEASURE) a = rt.decide(mean_abs_diff(in, prev_input.data(), ne)) ? SC_APPLY : SC_COMPUTE;
+        if (a == SC_MEASURE && rt.is_cachedit()) {  // calculate_residual_diff (cache_dit.hpp:293-306): two float accumulators, sequential
+            float sum_diff = 0.0f, sum_abs = 0.0f;
+            for (size_t i = 0; i < ne; ++i) sum_diff += std::fabs(prev_input[i] - in[i]), sum_abs += std::fabs(prev_input[i]);
+            a = rt.decide_rel(sum_diff, sum_abs) ? SC_APPLY : SC_COMPUTE;
+        } else if (a == SC_MEASURE) {
+            a = rt.decide(mean_abs_diff(in, prev_input.data(), ne)) ? SC_APPLY : SC_COMPUTE;
+        }
         if (a != SC_APPLY) return false;
         apply(cond, in, out, ne);
         return true;

@@ -73,6 +73,11 @@ bool launch_step_cache_probe(hipStream_t s, const float* x, float c_in, const fl
 // stats2[0] = sum |out_0 - prev_out(old)| (0 without has_prev_out: prev_out is not read), stats2[1] = sum |out_0|
 bool launch_step_cache_record(hipStream_t s, const float* in, const float* out, float* prev_in, float* prev_out, float* diff, int64_t per, int k, int64_t nb, bool has_prev_out,
                               float* partial, float* stats2);
+// probe plus stats[3] = sum |prev_in| (the CacheDIT modes); stats: 4 floats, [1] and [2] are left alone
+bool launch_step_cache_probe_rel(hipStream_t s, const float* x, float c_in, const float* prev_in, int64_t n, float* partial, float* stats);
+// Spectrum's forecast: out[f] = (1 - w) * (h_last + 0.5 * (h_last - h_prev)) + w * sum_j weights[j] * H_j[f] with H_j = ring + order[j] * slot_stride, oldest first,
+// every operation rounded on its own; order / weights: k (2 .. 16) HOST values, order[j] in 0 .. 15.  false (nothing enqueued): bad arguments
+bool launch_spectrum_predict(hipStream_t s, const float* ring, int64_t slot_stride, const int* order, int k, const float* weights, float w, int64_t n, float* out);
 
 // ---- norm.hip ---------------------------------------------------------------------------------------
 // GROUP_NORM over [W*H, C, N] contiguous f32; optional fused affine (w,b per channel) and SiLU

@@ -1,11 +1,13 @@
-// step_cache.hip — the two device passes of the step caches (EasyCache / UCache, csrc/host/step_cache.hpp) on the device-resident sampler:
-//   probe : stats[0] = sum |x * c_in - prev_in|                         (the input change the host state machine decides on)
+// step_cache.hip — the device passes of the step caches (csrc/host/step_cache.hpp) on the device-resident sampler:
+//   probe : stats[0] = sum |x * c_in - prev_in|                         (the input change the host state machine decides on; EasyCache / UCache)
+//   probe_rel: the same sum and stats[3] = sum |prev_in|                 (the CacheDIT modes' relative residual diff, one pass over the two tensors)
 //   record: diff_j = out_j - in, prev_in = in, prev_out = out_0,
 //           stats[1] = sum |out_0 - prev_out(old)|, stats[2] = sum |out_0|   (what after_condition measures, one pass over the step's tensors)
 // The sums are DETERMINISTIC: the grid is a function of the element count only, every thread owns a fixed set of elements, a workgroup combines its 256
 // accumulators through wave64 shuffles and LDS and stores ONE partial per sum; a second one-workgroup launch adds the partials in a fixed order.  No floating-point
 // atomics.  Summation depth of any element: <= SC_ITEMS_MAX additions on a thread's accumulator (+ 2 inside a 16-byte item), 6 across the wave, 2 across the four
 // waves, and in the finish pass 4 + 6 + 2 — at most 86 <= 128, so with non-negative terms the relative error is below 128 * 2^-24.
+//   spectrum_predict: Spectrum's forecast from its ring of denoised tensors — a streaming kernel, no sum across elements (at the end of the file)
 #include "device_utils.h"
 
 namespace mi355x {
@@ -45,6 +47,31 @@ __global__ __launch_bounds__(SC_THREADS) void k_step_cache_probe(const float* __
     for (int64_t e = 4 * nq + t; e < n; e += gt) acc += sc_absdiff_scaled(x[e], c_in, prev_in[e]);
     const float s = sc_block_sum(acc, lds);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// probe plus sum |prev_in| from the value already loaded: same grid, same ownership of elements, same depth
+__global__ __launch_bounds__(SC_THREADS) void k_step_cache_probe_rel(const float* __restrict__ x, float c_in, const float* __restrict__ prev_in, int64_t n, int vec,
+                                                                      float* __restrict__ partial) {
+    __shared__ float lds[4];
+    const int64_t gt = (int64_t)gridDim.x * SC_THREADS, t = (int64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+    const int64_t nq = vec ? (n >> 2) : 0;
+    float acc = 0.f, mag = 0.f;
+    for (int64_t q = t; q < nq; q += gt) {
+        const float4 a = ((const float4*)x)[q], p = ((const float4*)prev_in)[q];
+        acc += (sc_absdiff_scaled(a.x, c_in, p.x) + sc_absdiff_scaled(a.y, c_in, p.y)) + (sc_absdiff_scaled(a.z, c_in, p.z) + sc_absdiff_scaled(a.w, c_in, p.w));
+        mag += (fabsf(p.x) + fabsf(p.y)) + (fabsf(p.z) + fabsf(p.w));
+    }
+    for (int64_t e = 4 * nq + t; e < n; e += gt) {
+        const float p = prev_in[e];
+        acc += sc_absdiff_scaled(x[e], c_in, p);
+        mag += fabsf(p);
+    }
+    const float s1 = sc_block_sum(acc, lds);
+    const float s2 = sc_block_sum(mag, lds);
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x]                 = s1;
+        partial[SC_MAX_BLOCKS + blockIdx.x] = s2;
+    }
 }
 
 // in / prev_in / prev_out: [per, nb]; out / diff: [per, k, nb] (the k conditions of an image adjacent, condition 0 first: the step graph's eps layout).
@@ -101,14 +128,14 @@ __global__ __launch_bounds__(SC_THREADS) void k_step_cache_record(const float* _
     }
 }
 
-// one workgroup: stats[s] = the nblocks partials of sum s, thread t adding partials t, t + 256, t + 512, t + 768 in that order
-__global__ __launch_bounds__(SC_THREADS) void k_step_cache_finish(const float* __restrict__ partial, int nblocks, int nsums, float* __restrict__ stats) {
+// one workgroup: stats[s * stat_stride] = the nblocks partials of sum s, thread t adding partials t, t + 256, t + 512, t + 768 in that order
+__global__ __launch_bounds__(SC_THREADS) void k_step_cache_finish(const float* __restrict__ partial, int nblocks, int nsums, float* __restrict__ stats, int stat_stride) {
     __shared__ float lds[4];
     for (int s = 0; s < nsums; ++s) {
         float acc = 0.f;
         for (int i = threadIdx.x; i < nblocks; i += SC_THREADS) acc += partial[s * SC_MAX_BLOCKS + i];
         const float r = sc_block_sum(acc, lds);
-        if (threadIdx.x == 0) stats[s] = r;
+        if (threadIdx.x == 0) stats[s * stat_stride] = r;
     }
 }
 
@@ -131,7 +158,18 @@ bool launch_step_cache_probe(hipStream_t s, const float* x, float c_in, const fl
     const int blocks    = sc_grid(items);
     if (!blocks) return false;
     hipLaunchKernelGGL(k_step_cache_probe, dim3(blocks), dim3(SC_THREADS), 0, s, x, c_in, prev_in, n, vec, partial);
-    hipLaunchKernelGGL(k_step_cache_finish, dim3(1), dim3(SC_THREADS), 0, s, (const float*)partial, blocks, 1, stats);
+    hipLaunchKernelGGL(k_step_cache_finish, dim3(1), dim3(SC_THREADS), 0, s, (const float*)partial, blocks, 1, stats, 1);
+    return hipGetLastError() == hipSuccess;
+}
+
+bool launch_step_cache_probe_rel(hipStream_t s, const float* x, float c_in, const float* prev_in, int64_t n, float* partial, float* stats) {
+    if (n < 1) return false;
+    const int vec       = sc_aligned16(x) && sc_aligned16(prev_in) ? 1 : 0;
+    const int64_t items = vec ? (n >> 2) + (n & 3) : n;
+    const int blocks    = sc_grid(items);
+    if (!blocks) return false;
+    hipLaunchKernelGGL(k_step_cache_probe_rel, dim3(blocks), dim3(SC_THREADS), 0, s, x, c_in, prev_in, n, vec, partial);
+    hipLaunchKernelGGL(k_step_cache_finish, dim3(1), dim3(SC_THREADS), 0, s, (const float*)partial, blocks, 2, stats, 3);  // stats[0] and stats[3]
     return hipGetLastError() == hipSuccess;
 }
 
@@ -144,7 +182,78 @@ bool launch_step_cache_record(hipStream_t s, const float* in, const float* out, 
     const int blocks    = sc_grid(items);
     if (!blocks) return false;
     hipLaunchKernelGGL(k_step_cache_record, dim3(blocks), dim3(SC_THREADS), 0, s, in, out, prev_in, prev_out, diff, per, k, nb, has_prev_out ? 1 : 0, vec, partial);
-    hipLaunchKernelGGL(k_step_cache_finish, dim3(1), dim3(SC_THREADS), 0, s, (const float*)partial, blocks, 2, stats2);
+    hipLaunchKernelGGL(k_step_cache_finish, dim3(1), dim3(SC_THREADS), 0, s, (const float*)partial, blocks, 2, stats2, 1);
+    return hipGetLastError() == hipSuccess;
+}
+
+// ---- Spectrum's forecast (csrc/host/step_cache.hpp: SpectrumState) ----------------------------------------------------------------------------------------
+// out[f] = (1 - w) * (h_last + 0.5 * (h_last - h_prev)) + w * sum_j weights[j] * H_j[f], H_j the j-th oldest slot of the ring.  Every operation is ONE rounded f32
+// operation in the order of the host loop's (contraction off), so the device sampler and the host loop forecast the same bits.  Pure streaming: k reads and one
+// write per element, 16 bytes per lane where every base and the slot stride allow it; no LDS, nothing shared between elements.  Weights and slot offsets are
+// kernel arguments, read with a uniform index.
+constexpr int SPECTRUM_MAX_K      = 16;
+constexpr int SPECTRUM_MAX_BLOCKS = 2048;  // 256 CUs x 8 workgroups of 256 threads; larger inputs stride over the grid
+struct SpectrumArgs {
+    float weights[SPECTRUM_MAX_K];
+    int64_t offset[SPECTRUM_MAX_K];  // of slot j in floats, oldest first
+};
+
+__device__ __forceinline__ float spectrum_mac(float pc, float wj, float h) {
+#pragma clang fp contract(off)
+    const float m = wj * h;
+    return pc + m;
+}
+__device__ __forceinline__ float spectrum_blend(float pc, float h_last, float h_prev, float w_taylor, float w_cheb) {
+#pragma clang fp contract(off)
+    const float d  = h_last - h_prev;
+    const float e  = 0.5f * d;
+    const float pt = h_last + e;
+    const float a  = w_taylor * pt;
+    const float b  = w_cheb * pc;
+    return a + b;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void k_spectrum_predict(const float* __restrict__ ring, SpectrumArgs a, int k, float w_taylor, float w_cheb, int64_t n, int vec,
+                                                                  float* __restrict__ out) {
+    const int64_t gt = (int64_t)gridDim.x * SC_THREADS, t = (int64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+    const int64_t nq = vec ? (n >> 2) : 0;
+    for (int64_t q = t; q < nq; q += gt) {
+        float4 pc   = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 last = pc, prev = pc;
+        for (int j = 0; j < k; ++j) {
+            const float4 h = ((const float4*)(ring + a.offset[j]))[q];
+            const float wj = a.weights[j];
+            pc.x = spectrum_mac(pc.x, wj, h.x), pc.y = spectrum_mac(pc.y, wj, h.y), pc.z = spectrum_mac(pc.z, wj, h.z), pc.w = spectrum_mac(pc.w, wj, h.w);
+            prev = last, last = h;
+        }
+        ((float4*)out)[q] = make_float4(spectrum_blend(pc.x, last.x, prev.x, w_taylor, w_cheb), spectrum_blend(pc.y, last.y, prev.y, w_taylor, w_cheb),
+                                        spectrum_blend(pc.z, last.z, prev.z, w_taylor, w_cheb), spectrum_blend(pc.w, last.w, prev.w, w_taylor, w_cheb));
+    }
+    for (int64_t e = 4 * nq + t; e < n; e += gt) {
+        float pc = 0.f, last = 0.f, prev = 0.f;
+        for (int j = 0; j < k; ++j) {
+            const float h = ring[a.offset[j] + e];
+            pc            = spectrum_mac(pc, a.weights[j], h);
+            prev = last, last = h;
+        }
+        out[e] = spectrum_blend(pc, last, prev, w_taylor, w_cheb);
+    }
+}
+
+bool launch_spectrum_predict(hipStream_t s, const float* ring, int64_t slot_stride, const int* order, int k, const float* weights, float w, int64_t n, float* out) {
+    if (k < 2 || k > SPECTRUM_MAX_K || n < 1 || slot_stride < n) return false;
+    SpectrumArgs a{};
+    for (int j = 0; j < k; ++j) {
+        if (order[j] < 0 || order[j] >= SPECTRUM_MAX_K) return false;
+        a.weights[j] = weights[j];
+        a.offset[j]  = (int64_t)order[j] * slot_stride;
+    }
+    const int vec       = (sc_aligned16(ring) && sc_aligned16(out) && slot_stride % 4 == 0) ? 1 : 0;
+    const int64_t items = vec ? (n >> 2) + (n & 3) : n;
+    int64_t blocks      = (items + SC_THREADS - 1) / SC_THREADS;
+    if (blocks > SPECTRUM_MAX_BLOCKS) blocks = SPECTRUM_MAX_BLOCKS;
+    const float w_taylor = 1.0f - w;
+    hipLaunchKernelGGL(k_spectrum_predict, dim3((unsigned)blocks), dim3(SC_THREADS), 0, s, ring, a, k, w_taylor, w, n, vec, out);
     return hipGetLastError() == hipSuccess;
 }
 
