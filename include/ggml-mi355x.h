@@ -208,6 +208,18 @@ GGML_MI355X_API bool ggml_backend_mi355x_spectrum_predict(ggml_backend_t backend
                                                           int64_t n, float* out);
 /* a computed step's `denoised` into its ring slot: a device-to-device copy of n floats enqueued on that stream (no kernel) */
 GGML_MI355X_API bool ggml_backend_mi355x_spectrum_push(ggml_backend_t backend, const float* src, float* dst, int64_t n);
+/* The latent previews' byte stages (kernels/preview.hip), enqueued on that stream between two graphs: the kernel writes a byte buffer the backend owns (made on first
+ * use, grown on demand, freed with the backend) and ONE asynchronous device-to-host copy of plane * n * 3 bytes into out_rgb follows on the same stream — the caller
+ * synchronises (ggml_backend_synchronize) before it reads them.  latents / chw: DEVICE addresses of planar f32 data; proj ([c][3]), bias ([3]) and out_rgb: HOST.
+ *   latent_preview: [plane, c, n] -> RGB [n][plane][3].  v = x * in_scale (one rounded multiply, only when in_scale != 1); r = g = b = 0, for d ascending
+ *                   r = r + v * proj[d][0] ... (multiply and add rounded separately); + bias; m * .5f + .5f; (0 < m) ? m : 0, (m < 1) ? m : 1 (NaN -> 0);
+ *                   (uint8_t)(m * 255).  proj NULL (c must be 3): the channels are r, g, b and no bias is added; bias NULL: zeros.  c <= 128.
+ *   planar_to_u8  : [plane, 3, n] -> RGB [n][plane][3].  v = x * in_mul + in_add (rounded separately, only when (in_mul, in_add) != (1, 0)); v <= 0 or NaN -> 0,
+ *                   v >= 1 -> 255, else (uint8_t)(v * 255.0f + 0.5f).
+ * false: bad arguments or no memory for the byte buffer — nothing was enqueued. */
+GGML_MI355X_API bool ggml_backend_mi355x_latent_preview(ggml_backend_t backend, const float* latents, int64_t plane, int c, int64_t n, float in_scale, const float* proj,
+                                                        const float* bias, uint8_t* out_rgb);
+GGML_MI355X_API bool ggml_backend_mi355x_planar_to_u8(ggml_backend_t backend, const float* chw, int64_t plane, int64_t n, float in_mul, float in_add, uint8_t* out_rgb);
 /* path of the HIP runtime library this plug-in is bound to, and hipSetDevice through it (for companions that must share its streams: RCCL) */
 GGML_MI355X_API const char* ggml_backend_mi355x_hip_library(void);
 GGML_MI355X_API int ggml_backend_mi355x_set_device(int hip_device);

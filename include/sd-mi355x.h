@@ -357,6 +357,30 @@ SD_API bool sd_spectrum_schedule(const sdm_spectrum_params_t* params, int n_call
 SD_API bool sd_spectrum_weights(const sdm_spectrum_params_t* params, const float* taus, int k, float tau_at, float* weights);
 SD_API bool sd_spectrum_kernels(sdm_ctx_t* ctx, const float* hist, int k, int64_t n, const float* weights, float w, float* out);
 
+/* ---- latent previews while sampling: the reference's sd_set_preview_callback / `--preview proj|tae|vae` (include/stable-diffusion.h:152-157, 441-446) -----------
+ * The callback receives an RGB picture of the trajectory at denoise calls of sd_sample_latents / sdm_generate_image, on the host loop (every sample method) and on
+ * the device-resident sampler: `step` is what the sampler hands the denoise call (i + 1, negated for the first stage of the two-stage methods), frames are
+ * frame_count images of the current device group, is_noisy tells the model input (x * c_in, before the model call; not delivered on a Spectrum forecast call) from
+ * the denoised prediction (after the inpainting blend; also delivered on calls a step cache skipped or forecast).  Frames belong to the engine and are valid only
+ * during the callback.  PROJ: the family's latent -> RGB projection at latent resolution (w/8 x h/8); TAE / VAE: the latent decoded by TAESD / the first-stage
+ * decoder (sd_set_vae_tiling honoured) at full resolution.  The byte stages run as HIP kernels on the MI355X backend (kernels/preview.hip); on the device-resident
+ * sampler only the bytes (decode modes: and the small latent) cross to the host, and every delivered preview is one stream synchronisation.
+ * Differences from the reference: the state is per context (the reference's is process-global, hence the sdm_ prefix); `interval` is honoured — a call is
+ * previewed when abs(step) % max(interval, 1) == 0 — where the reference stores it and never reads it (interval 1 is its behaviour).
+ * With no callback installed every sampler path is exactly the one without previews.  Refused at sampling time (sd_last_error): an installed preview on the
+ * device-resident sampler together with a CFG-pair exchange (sd_set_pair_exchange*). */
+enum sdm_preview_t { SDM_PREVIEW_NONE, SDM_PREVIEW_PROJ, SDM_PREVIEW_TAE, SDM_PREVIEW_VAE };   /* preview_t's values */
+typedef void (*sdm_preview_cb_t)(int step, int frame_count, sdm_image_t* frames, bool is_noisy, void* data);
+SD_API bool sdm_set_preview_callback(sdm_ctx_t* ctx, sdm_preview_cb_t cb, int mode, int interval, bool denoised, bool noisy, void* data); /* cb NULL or mode NONE: off */
+SD_API int  sdm_preview_first_image(sdm_ctx_t* ctx);   /* inside a callback: batch index of frames[0] (device groups) */
+/* inside a callback: the f32 latent [w, h, c, frame_count] the frames were made from, BEFORE in_scale (the noisy preview of the device-resident sampler hands x with
+ * in_scale = c_in; everywhere else in_scale is 1).  Copies at most `capacity` floats; returns the latent's float count (0 outside a callback) */
+SD_API int64_t sdm_preview_latent(sdm_ctx_t* ctx, float* out, int64_t capacity, float* in_scale);
+SD_API bool sdm_set_preview_projection(sdm_ctx_t* ctx, const float* proj /* [c][3] */, const float* bias /* [3] or NULL */, int c); /* NULL proj: back to the family table */
+SD_API bool sdm_latent_preview(sdm_ctx_t* ctx, const float* latents, int w, int h, int c, int n, float in_scale, uint8_t* out_rgb); /* the PROJ pass on caller memory, through the path the sampler uses */
+SD_API bool sdm_planar_to_u8(sdm_ctx_t* ctx, const float* chw, int w, int h, int n, uint8_t* out_rgb);                               /* the decode modes' byte stage, same */
+SD_API bool sdm_preview_device_passes(sdm_ctx_t* ctx);  /* like sd_step_cache_device_passes */
+
 /* ---- host-side sampler pieces exposed for known-answer tests ---- */
 SD_API void sd_philox_randn(uint64_t seed, uint32_t offset, uint32_t n, float* out); /* rng_philox.hpp:101-122 */
 SD_API void sd_philox_uint32(uint64_t seed, uint32_t offset, uint32_t n, uint32_t* out /* 4*n words */); /* the integer stage alone: philox4_32, rng_philox.hpp:63-77 */

@@ -40,6 +40,9 @@ SCHED_BONG_TANGENT, SCHED_FLUX, SCHED_BETA, SCHEDULER_DEFAULT = 10, 14, 15, 16  
 # sdm_cache_mode_t (include/sd-mi355x.h): the reference's sd_cache_mode_t values
 CACHE_DISABLED, CACHE_EASYCACHE, CACHE_UCACHE = 0, 1, 2
 CACHE_DBCACHE, CACHE_TAYLORSEER, CACHE_CACHE_DIT, CACHE_SPECTRUM = 3, 4, 5, 6
+# sdm_preview_t (include/sd-mi355x.h): the reference's preview_t values; sdm_preview_cb_t: (step, frame_count, frames, is_noisy, user)
+PREVIEW_NONE, PREVIEW_PROJ, PREVIEW_TAE, PREVIEW_VAE = 0, 1, 2, 3
+PREVIEW_CB_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, C.c_bool, C.c_void_p)
 
 
 class EngineError(RuntimeError):
@@ -860,6 +863,97 @@ class Engine:
         if not L.sd_step_cache_kernels(self._ctx, _fptr(a), _fptr(o), _fptr(pi), _fptr(po), n, k, nb, float(c_in), _fptr(stats), _fptr(diff), _fptr(pin2), _fptr(pout2)):
             raise EngineError("sd_step_cache_kernels failed: " + L.sd_last_error().decode())
         return stats, diff, pin2, pout2
+
+    # ---- latent previews while sampling ----
+    def set_preview(self, fn, mode: int = PREVIEW_PROJ, interval: int = 1, denoised: bool = True, noisy: bool = False) -> None:
+        """sdm_set_preview_callback — the reference's sd_set_preview_callback / `--preview proj|tae|vae`, per engine: during sample_latents / generate_image
+        `fn(step, frames, is_noisy, first_image)` receives frames uint8 [n, H, W, 3] of the current device group (PROJ: latent resolution; TAE / VAE: pixels) at
+        every denoise call whose sampler step satisfies abs(step) % max(interval, 1) == 0; first_image is the batch index of frames[0].  The array is only valid
+        during the call (copy it to keep it); inside fn, preview_latent() returns the f32 latent behind the frames.  fn = None turns previews off."""
+        L = lib()
+        L.sdm_set_preview_callback.argtypes = [C.c_void_p, PREVIEW_CB_FN, C.c_int, C.c_int, C.c_bool, C.c_bool, C.c_void_p]
+        L.sdm_set_preview_callback.restype = C.c_bool
+        L.sdm_preview_first_image.argtypes = [C.c_void_p]
+        L.sdm_preview_first_image.restype = C.c_int
+        if fn is None:
+            cb = PREVIEW_CB_FN(0)
+        else:
+            def call(step, count, frames, is_noisy, _user, _fn=fn):
+                try:
+                    im = C.cast(frames, C.POINTER(SdImage))
+                    h, w = int(im[0].height), int(im[0].width)
+                    arr = np.empty((count, h, w, 3), dtype=np.uint8)
+                    for i in range(count):
+                        arr[i] = np.ctypeslib.as_array(im[i].data, shape=(h, w, 3))
+                    _fn(int(step), arr, bool(is_noisy), int(L.sdm_preview_first_image(self._ctx)))
+                except Exception:  # never unwind through the C frames
+                    import traceback
+                    traceback.print_exc()
+            cb = PREVIEW_CB_FN(call)
+        if not L.sdm_set_preview_callback(self._ctx, cb, int(mode), int(interval), bool(denoised), bool(noisy), None):
+            raise EngineError("sdm_set_preview_callback failed: " + L.sd_last_error().decode())
+        self._preview_cb = cb   # kept alive as long as it is installed
+
+    def preview_latent(self):
+        """sdm_preview_latent, inside a preview callback: (the f32 latent behind the frames as a flat array [n * C * h * w], in_scale) — the frames show
+        latent * in_scale (in_scale is c_in for the device-resident sampler's noisy preview, 1 everywhere else).  Outside a callback: (empty, 1.0)."""
+        L = lib()
+        L.sdm_preview_latent.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
+        L.sdm_preview_latent.restype = C.c_int64
+        sc = C.c_float(1.0)
+        n = L.sdm_preview_latent(self._ctx, None, 0, C.byref(sc))
+        out = np.empty(n, dtype=np.float32)
+        if n:
+            L.sdm_preview_latent(self._ctx, _fptr(out), n, C.byref(sc))
+        return out, float(sc.value)
+
+    def set_preview_projection(self, proj, bias=None) -> None:
+        """sdm_set_preview_projection: proj [c, 3] (+ bias [3]) replaces the family's latent -> RGB table for c-channel latents; proj = None restores it."""
+        L = lib()
+        L.sdm_set_preview_projection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.sdm_set_preview_projection.restype = C.c_bool
+        if proj is None:
+            ok = L.sdm_set_preview_projection(self._ctx, None, None, 0)
+        else:
+            pj = _f32(proj)
+            assert pj.ndim == 2 and pj.shape[1] == 3
+            bs = None if bias is None else _f32(bias)
+            assert bs is None or bs.size == 3
+            ok = L.sdm_set_preview_projection(self._ctx, _fptr(pj), _fptr(bs), pj.shape[0])
+        if not ok:
+            raise EngineError("sdm_set_preview_projection failed: " + L.sd_last_error().decode())
+
+    def latent_preview(self, latents: np.ndarray, in_scale: float = 1.0) -> np.ndarray:
+        """sdm_latent_preview: the PROJ pass on caller arrays through the path the sampler uses — latents [N, C, h, w] -> uint8 [N, h, w, 3]"""
+        z = _f32(latents)
+        n, c, h, w = z.shape
+        out = np.empty((n, h, w, 3), dtype=np.uint8)
+        L = lib()
+        L.sdm_latent_preview.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]
+        L.sdm_latent_preview.restype = C.c_bool
+        if not L.sdm_latent_preview(self._ctx, _fptr(z), w, h, c, n, float(in_scale), out.ctypes.data_as(C.c_void_p)):
+            raise EngineError("sdm_latent_preview failed: " + L.sd_last_error().decode())
+        return out
+
+    def planar_to_u8(self, rgb: np.ndarray) -> np.ndarray:
+        """sdm_planar_to_u8: the decode modes' byte stage on caller arrays — rgb [N, 3, H, W] f32 -> uint8 [N, H, W, 3]"""
+        x = _f32(rgb)
+        n, c, h, w = x.shape
+        assert c == 3
+        out = np.empty((n, h, w, 3), dtype=np.uint8)
+        L = lib()
+        L.sdm_planar_to_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.sdm_planar_to_u8.restype = C.c_bool
+        if not L.sdm_planar_to_u8(self._ctx, _fptr(x), w, h, n, out.ctypes.data_as(C.c_void_p)):
+            raise EngineError("sdm_planar_to_u8 failed: " + L.sd_last_error().decode())
+        return out
+
+    def preview_device_passes(self) -> bool:
+        """sdm_preview_device_passes: True when the previews' byte stages are the backend's HIP kernels, False on a backend without them (host restatement)."""
+        L = lib()
+        L.sdm_preview_device_passes.argtypes = [C.c_void_p]
+        L.sdm_preview_device_passes.restype = C.c_bool
+        return bool(L.sdm_preview_device_passes(self._ctx))
 
     def vae_encode(self, rgb: np.ndarray, seed: int = 42, return_moments: bool = False):
         """sd_vae_encode: rgb [N,3,H,W] in [0,1] -> diffusion latents [N,zc,H/8,W/8] sampled with Philox(seed) (+ the moments [N,2*zc,H/8,W/8] the graph produced)."""

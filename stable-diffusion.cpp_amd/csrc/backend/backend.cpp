@@ -154,6 +154,8 @@ struct BackendCtx {
     Planner* planner;
     UploadStaging up;
     float* step_cache_partial = nullptr;  // per-workgroup partial sums of the step-cache passes (kernels/step_cache.hip), made on first use
+    uint8_t* preview_bytes    = nullptr;  // RGB bytes of the latest preview (kernels/preview.hip), made on first use, grown on demand
+    size_t preview_capacity   = 0;
 };
 static const char* be_get_name(ggml_backend_t b) { return ((BackendCtx*)b->context)->dev->name.c_str(); }
 static void be_free(ggml_backend_t b) {
@@ -162,6 +164,7 @@ static void be_free(ggml_backend_t b) {
     HIP_OK(hipStreamSynchronize(c->stream));
     planner_destroy(c->planner);
     if (c->step_cache_partial) (void)hipFree(c->step_cache_partial);
+    if (c->preview_bytes) (void)hipFree(c->preview_bytes);
     if (c->up.base) {
         (void)hipEventDestroy(c->up.done[0]);
         (void)hipEventDestroy(c->up.done[1]);
@@ -289,6 +292,8 @@ static void* reg_get_proc(ggml_backend_reg_t, const char* name) {
     if (strcmp(name, "ggml_backend_mi355x_step_cache_probe_rel") == 0) return (void*)ggml_backend_mi355x_step_cache_probe_rel;
     if (strcmp(name, "ggml_backend_mi355x_spectrum_predict") == 0) return (void*)ggml_backend_mi355x_spectrum_predict;
     if (strcmp(name, "ggml_backend_mi355x_spectrum_push") == 0) return (void*)ggml_backend_mi355x_spectrum_push;
+    if (strcmp(name, "ggml_backend_mi355x_latent_preview") == 0) return (void*)ggml_backend_mi355x_latent_preview;
+    if (strcmp(name, "ggml_backend_mi355x_planar_to_u8") == 0) return (void*)ggml_backend_mi355x_planar_to_u8;
     if (strcmp(name, "ggml_backend_mi355x_hip_library") == 0) return (void*)ggml_backend_mi355x_hip_library;
     if (strcmp(name, "ggml_backend_mi355x_set_device") == 0) return (void*)ggml_backend_mi355x_set_device;
     if (strcmp(name, "ggml_backend_mi355x_get_device") == 0) return (void*)ggml_backend_mi355x_get_device;
@@ -519,6 +524,43 @@ GGML_MI355X_API bool ggml_backend_mi355x_spectrum_push(ggml_backend_t backend, c
     mi355x::BackendCtx* c = (mi355x::BackendCtx*)backend->context;
     if (hipSetDevice(c->dev->id) != hipSuccess) return false;
     return hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
+}
+// The previews' byte stages (include/ggml-mi355x.h): the kernel writes the backend's own byte buffer, one asynchronous copy brings the bytes to the caller
+static uint8_t* preview_scratch(mi355x::BackendCtx* c, size_t need) {
+    if (c->preview_capacity >= need) return c->preview_bytes;
+    if (c->preview_bytes) {  // an earlier preview may still be reading it
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return nullptr;
+        (void)hipFree(c->preview_bytes);
+        c->preview_bytes    = nullptr;
+        c->preview_capacity = 0;
+    }
+    const size_t cap = (need + 4095) / 4096 * 4096;
+    if (hipMalloc((void**)&c->preview_bytes, cap) != hipSuccess) {
+        (void)hipGetLastError();
+        c->preview_bytes = nullptr;
+        return nullptr;
+    }
+    c->preview_capacity = cap;
+    return c->preview_bytes;
+}
+GGML_MI355X_API bool ggml_backend_mi355x_latent_preview(ggml_backend_t backend, const float* latents, int64_t plane, int c, int64_t n, float in_scale, const float* proj,
+                                                        const float* bias, uint8_t* out_rgb) {
+    if (!backend || !latents || !out_rgb || plane < 1 || n < 1 || c < 1 || c > 128 || (!proj && c != 3)) return false;
+    mi355x::BackendCtx* bc = (mi355x::BackendCtx*)backend->context;
+    if (hipSetDevice(bc->dev->id) != hipSuccess) return false;
+    const size_t bytes = (size_t)plane * (size_t)n * 3;
+    uint8_t* dev       = preview_scratch(bc, bytes);
+    if (!dev || !mi355x::launch_latent_preview(bc->stream, latents, plane, c, n, in_scale, proj, bias, dev)) return false;
+    return hipMemcpyAsync(out_rgb, dev, bytes, hipMemcpyDeviceToHost, bc->stream) == hipSuccess;
+}
+GGML_MI355X_API bool ggml_backend_mi355x_planar_to_u8(ggml_backend_t backend, const float* chw, int64_t plane, int64_t n, float in_mul, float in_add, uint8_t* out_rgb) {
+    if (!backend || !chw || !out_rgb || plane < 1 || n < 1) return false;
+    mi355x::BackendCtx* bc = (mi355x::BackendCtx*)backend->context;
+    if (hipSetDevice(bc->dev->id) != hipSuccess) return false;
+    const size_t bytes = (size_t)plane * (size_t)n * 3;
+    uint8_t* dev       = preview_scratch(bc, bytes);
+    if (!dev || !mi355x::launch_planar_to_u8(bc->stream, chw, plane, n, in_mul, in_add, dev)) return false;
+    return hipMemcpyAsync(out_rgb, dev, bytes, hipMemcpyDeviceToHost, bc->stream) == hipSuccess;
 }
 // The HIP runtime THIS plug-in is bound to (a process may hold a second copy, e.g. the one a torch wheel bundles): a companion library that
 // must share streams with the backend — RCCL for the native CFG-pair exchange — is loaded from the same directory.

@@ -32,6 +32,7 @@
 #include "conditioner.hpp"
 #include "sampler.hpp"
 #include "step_cache.hpp"
+#include "preview.hpp"
 #include "model_io.hpp"
 #include "torch_ckpt_io.hpp"
 #include "name_conversion.hpp"
@@ -257,6 +258,8 @@ struct Runner {
     int64_t calls                 = 0;
     int64_t last_nodes            = 0;
     double build_ms = 0, alloc_ms = 0, submit_ms = 0;  // cumulative host time: graph construction, gallocr, uploads + graph_compute call
+    const void* last_res_data = nullptr;  // where the last compute's result tensor lies in the compute buffer: valid until this runner places another graph (a decode preview
+    size_t last_res_bytes     = 0;        // converts the image there, behind the graph on the backend stream, instead of reading it back as f32)
 
     ~Runner() {
         drop_cache();
@@ -458,7 +461,9 @@ struct Runner {
             }
             ggml_backend_tensor_get(res, out, 0, out_bytes);
         }
-        last_nodes = gf->n_nodes;
+        last_nodes     = gf->n_nodes;
+        last_res_data  = res->data;
+        last_res_bytes = ggml_nbytes(res);
         ++calls;
         if (!keep) ggml_free(cctx);
         return true;
@@ -551,9 +556,25 @@ struct sdm_ctx_t {
             }
         };
         std::unique_ptr<Spectrum> spectrum;
+        // latent previews (sdm_set_preview_callback), made only when a denoised preview is installed: the tensor `denoised` passes through on the steps a preview is due,
+        // and the runners of those capturing graphs — their own cached graph and compute buffer, so that the step graphs of the steps in between (and of every later
+        // trajectory without previews) keep the cached graph, the buffer placement and the backend plan they had
+        struct Preview {
+            ggml_context* cctx        = nullptr;
+            ggml_backend_buffer_t buf = nullptr;
+            ggml_tensor* denoised     = nullptr;
+            uint64_t serial = 0;
+            Runner step_runner, skip_runner;
+            ~Preview() {
+                if (buf) ggml_backend_buffer_free(buf);
+                if (cctx) ggml_free(cctx);
+            }
+        };
+        std::unique_ptr<Preview> preview;
         ~SamplerState() {
             cache.reset();
             spectrum.reset();
+            preview.reset();
             if (buf) ggml_backend_buffer_free(buf);
             if (sctx) ggml_free(sctx);
         }
@@ -571,6 +592,28 @@ struct sdm_ctx_t {
     sdm_spectrum_params_t spectrum_params{0.40f, 3, 1.0f, 2, 0.50f, 4, 0.9f};
     StepCacheRuntime step_cache;
     Runner skip_runner;
+    // latent previews (sdm_set_preview_callback; csrc/host/preview.hpp): the request, and — made on the first PROJ preview of the host loop on a backend with the
+    // byte-stage exports — the tensor the group's latent is uploaded to
+    PreviewState preview;
+    struct PreviewUpload {
+        ggml_context* cctx        = nullptr;
+        ggml_backend_buffer_t buf = nullptr;
+        ggml_tensor* latent       = nullptr;
+        ~PreviewUpload() {
+            if (buf) ggml_backend_buffer_free(buf);
+            if (cctx) ggml_free(cctx);
+        }
+    };
+    std::unique_ptr<PreviewUpload> preview_upload;
+    struct PreviewCurrent {  // while a callback runs: the batch index of frames[0] and where the latent behind the frames lies (host memory or a backend tensor)
+        bool active         = false;
+        int first_image     = 0;
+        const float* host   = nullptr;
+        ggml_tensor* dev    = nullptr;
+        int64_t floats      = 0;
+        float in_scale      = 1.0f;
+    };
+    PreviewCurrent preview_current;
     float t_to_sigma(float t) const { return is_flux ? flux_denoiser.t_to_sigma(t) : (is_dit ? flow_denoiser.t_to_sigma(t) : denoiser.t_to_sigma(t)); }
     // whether the request would arm a cache on this family (init_sample_cache_runtime's tests that do not need the ladder)
     // method: the resolved sample method (Spectrum does not serve the two CFG++ methods)
@@ -1768,6 +1811,147 @@ bool sd_use_tae(sdm_ctx_t* ctx, bool on) {
     return true;
 }
 
+// ---- latent previews (csrc/host/preview.hpp) ----------------------------------------------------------------
+// The two byte stages (include/ggml-mi355x.h) as the samplers and sdm_latent_preview / sdm_planar_to_u8 reach them: plug-in exports found through the registry's
+// get_proc_address, enqueued on the backend's stream.  A backend without them (the CPU oracle of the tests) takes the host restatement; the product backend
+// without them is an error at sampling time, never a quiet fall-back (the step caches' rule).
+struct PreviewDevice {
+    typedef bool (*proj_fn)(ggml_backend_t, const float*, int64_t, int, int64_t, float, const float*, const float*, uint8_t*);
+    typedef bool (*u8_fn)(ggml_backend_t, const float*, int64_t, int64_t, float, float, uint8_t*);
+    ggml_backend_t backend = nullptr;
+    proj_fn proj_k         = nullptr;
+    u8_fn u8_k             = nullptr;
+    bool exports_missing   = false;
+    explicit PreviewDevice(ggml_backend_t be) : backend(be) {
+        ggml_backend_dev_t dev = ggml_backend_get_device(be);
+        ggml_backend_reg_t reg = dev ? ggml_backend_dev_backend_reg(dev) : nullptr;
+        if (reg) {
+            proj_k = (proj_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_latent_preview");
+            u8_k   = (u8_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_planar_to_u8");
+        }
+        if (!proj_k || !u8_k) proj_k = nullptr, u8_k = nullptr;
+        exports_missing = !proj_k && reg && strcmp(ggml_backend_reg_name(reg), "MI355X") == 0;
+    }
+    bool on_device() const { return proj_k != nullptr; }
+    // t: [plane, c, n] f32 on the backend -> out (host bytes, complete on return: the one synchronisation of a preview)
+    bool latent(ggml_tensor* t, int64_t plane, int c, int64_t n, float in_scale, const float* proj, const float* bias, uint8_t* out, std::vector<float>& tmp) {
+        if (proj_k) {
+            const bool ok = proj_k(backend, (const float*)t->data, plane, c, n, in_scale, proj, bias, out);
+            ggml_backend_synchronize(backend);
+            return ok;
+        }
+        tmp.resize((size_t)(plane * c * n));
+        ggml_backend_tensor_get(t, tmp.data(), 0, tmp.size() * sizeof(float));
+        return latent_preview_host(tmp.data(), plane, c, n, in_scale, proj, bias, out);
+    }
+};
+// the projection of a c-channel latent on this context: the installed table when it fits, else the family's, else (3 channels) none; false: no table known
+static bool preview_table(const sdm_ctx_t* ctx, int c, const float** proj, const float** bias) {
+    const PreviewState& pv = ctx->preview;
+    if (pv.custom_c == c && !pv.custom_proj.empty()) {
+        *proj = pv.custom_proj.data(), *bias = pv.custom_bias;
+        return true;
+    }
+    const PreviewTable ft = preview_family_table(ctx->params.model);
+    if (ft.channels == c) {
+        *proj = &ft.proj[0][0], *bias = ft.bias;
+        return true;
+    }
+    *proj = nullptr, *bias = nullptr;
+    return c == 3;
+}
+// the PROJ pass over host memory through the path the sampler uses: upload + kernel on a backend with the exports, the restatement otherwise
+static bool preview_proj_host_latent(sdm_ctx_t* ctx, PreviewDevice& dev, const float* x, int w, int h, int c, int n, float in_scale, const float* proj, const float* bias,
+                                     uint8_t* out) {
+    const int64_t plane = (int64_t)w * h;
+    if (!dev.on_device()) return latent_preview_host(x, plane, c, n, in_scale, proj, bias, out);
+    auto& up = ctx->preview_upload;
+    if (!up || up->latent->ne[0] != w || up->latent->ne[1] != h || up->latent->ne[2] != c || up->latent->ne[3] != n) {
+        up.reset(new sdm_ctx_t::PreviewUpload());
+        ggml_init_params ip{0, nullptr, true};
+        up->cctx   = ggml_init(ip);
+        up->latent = ggml_new_tensor_4d(up->cctx, GGML_TYPE_F32, w, h, c, n);
+        ggml_set_name(up->latent, "preview.latent");
+        up->buf = ggml_backend_alloc_ctx_tensors(up->cctx, ctx->backend);
+        if (!up->buf) {
+            up.reset();
+            set_error("preview: upload buffer allocation failed");
+            return false;
+        }
+    }
+    ggml_backend_tensor_set_async(ctx->backend, up->latent, x, 0, (size_t)plane * c * n * sizeof(float));
+    std::vector<float> unused;
+    return dev.latent(up->latent, plane, c, n, in_scale, proj, bias, out, unused);
+}
+// One preview of the current device group: host (host loop) or dev (device-resident sampler) holds the latent [W, H, C, nb]; in_scale != 1 only for the device sampler's
+// noisy preview (x, c_in).  Runs the mode's byte stage, hands the callback nb frames.  false (error set): the pass could not be run.
+static bool emit_preview(sdm_ctx_t* ctx, int step, bool is_noisy, int b0, int W, int H, int C, int nb, const float* host, ggml_tensor* dev, float in_scale) {
+    PreviewState& pv = ctx->preview;
+    PreviewDevice pd(ctx->backend);
+    if (pd.exports_missing) {
+        set_error("preview: the MI355X backend does not export its preview passes (ggml_backend_mi355x_latent_preview / _planar_to_u8)");
+        return false;
+    }
+    const size_t n = (size_t)W * H * C * nb;
+    int FW = W, FH = H;
+    bool ok = true;
+    if (pv.mode == SDM_PREVIEW_PROJ) {
+        const float *proj, *bias;
+        if (!preview_table(ctx, C, &proj, &bias)) {
+            set_error("preview: no latent to RGB projection known for " + std::to_string(C) + " channels (sdm_set_preview_projection)");
+            return false;
+        }
+        pv.bytes.resize((size_t)W * H * 3 * nb);
+        ok = dev ? pd.latent(dev, (int64_t)W * H, C, nb, in_scale, proj, bias, pv.bytes.data(), pv.staging)
+                 : preview_proj_host_latent(ctx, pd, host, W, H, C, nb, in_scale, proj, bias, pv.bytes.data());
+        if (!ok) set_error("preview: the projection pass could not be run");
+    } else {
+        // the decode modes: the (small) latent comes to the host, the decoders' entry points run their graphs, the image stays on the device until the byte stage has
+        // converted it — except through the tiling driver, whose canvas is read back as f32 and converted with the same arithmetic on the host
+        std::vector<float> lat;
+        const float* z = host;
+        if (dev) {
+            lat.resize(n);
+            ggml_backend_tensor_get(dev, lat.data(), 0, n * sizeof(float));
+            if (in_scale != 1.0f)
+                for (size_t k = 0; k < n; ++k) lat[k] = lat[k] * in_scale;
+            z = lat.data();
+        }
+        FW = W * 8, FH = H * 8;
+        const int64_t plane = (int64_t)FW * FH;
+        const bool tae      = pv.mode == SDM_PREVIEW_TAE;
+        const float mul = tae ? 1.0f : 0.5f, add = tae ? 0.0f : 0.5f;  // VAE::decode's (x + 1) / 2 (vae.hpp:216-218) folded into the byte stage; TAESD's output is the image
+        pv.bytes.resize((size_t)plane * 3 * nb);
+        if (pd.on_device() && (tae || !ctx->tiling.enabled)) {
+            Runner& r = tae ? ctx->tae_runner : ctx->vae_runner;
+            ok        = tae ? sd_tae_decode(ctx, z, W, H, C, nb, nullptr) : sd_vae_decode_raw(ctx, z, W, H, C, nb, nullptr);  // (no output buffer: enqueued, nothing read back)
+            if (ok && r.last_res_bytes != (size_t)plane * 3 * nb * sizeof(float)) {
+                set_error("preview: decode output size mismatch");
+                ok = false;
+            }
+            if (ok && !pd.u8_k(ctx->backend, (const float*)r.last_res_data, plane, nb, mul, add, pv.bytes.data())) {
+                set_error("preview: the byte pass could not be enqueued");
+                ok = false;
+            }
+            ggml_backend_synchronize(ctx->backend);
+        } else {
+            pv.staging.resize((size_t)plane * 3 * nb);
+            ok = tae ? sd_tae_decode(ctx, z, W, H, C, nb, pv.staging.data()) : sd_vae_decode_raw(ctx, z, W, H, C, nb, pv.staging.data());
+            ok = ok && planar_to_u8_host(pv.staging.data(), plane, nb, mul, add, pv.bytes.data());
+        }
+    }
+    if (!ok) return false;
+    std::vector<sdm_image_t> frames((size_t)nb);
+    for (int b = 0; b < nb; ++b) frames[(size_t)b] = sdm_image_t{(uint32_t)FW, (uint32_t)FH, 3, pv.bytes.data() + (size_t)b * FW * FH * 3};
+    struct Current {  // what sdm_preview_first_image / sdm_preview_latent answer with while the callback runs
+        sdm_ctx_t* ctx;
+        ~Current() { ctx->preview_current = sdm_ctx_t::PreviewCurrent(); }
+    } current{ctx};
+    ctx->preview_current = sdm_ctx_t::PreviewCurrent{true, b0, host, dev, (int64_t)n, in_scale};
+    pv.cb(step, nb, frames.data(), is_noisy, pv.user);
+    return true;
+}
+
 // ---- sample(): the denoise loop -------------------------------------------------------------------
 // resolve_sample_method / sd_get_default_sample_method (stable-diffusion.cpp:3965-3975, 4006-4013): DiT families default to plain Euler
 static int resolve_sample_method(const sdm_ctx_t* ctx, int m) {
@@ -1856,8 +2040,9 @@ struct HostDenoise {
             const int k = sc->spectrum.predict(weights, order);
             spectrum_predict_host(spectrum_ring.data(), n, order, k, weights, sc->spectrum.config.w, n, denoised);
             blend_mask(denoised);
-            return true;
+            return preview(step, false, denoised);  // stable-diffusion.cpp:2672-2674 (a forecast call never reaches the noisy preview)
         }
+        if (!preview(step, true, noised.data())) return false;  // stable-diffusion.cpp:2681-2683
         const bool cached = sc && sc->armed();
         if (cached) sc->begin_call(step, sigma);  // SampleStepCacheDispatcher step_cache(cache_runtime, step, sigma), stable-diffusion.cpp:2688
         auto run = [&](const sd_condition_t& cd, float* dst) {
@@ -1959,8 +2144,11 @@ struct HostDenoise {
             memcpy(&spectrum_ring[(size_t)sc->spectrum.update() * n], denoised, n * sizeof(float));
         }
         blend_mask(denoised);
-        return true;
+        return preview(step, false, denoised);  // stable-diffusion.cpp:2888-2892
     }
+    // sd_set_preview_callback's hook: nothing happens (no tensor, no launch) unless a callback is installed and this call is due (csrc/host/preview.hpp)
+    int b0 = 0;  // batch index of the group's first image
+    bool preview(int step, bool is_noisy, const float* latent) { return !ctx->preview.wants(step, is_noisy) || emit_preview(ctx, step, is_noisy, b0, W, H, C, nb, latent, nullptr, 1.0f); }
     void blend_mask(float* denoised) const {
         if (p->denoise_mask && p->init_latent) {  // inpainting: denoised * mask + init_latent * (1 - mask), the mask broadcast over channels and images (stable-diffusion.cpp:2888-2890)
             const size_t plane = (size_t)W * H;
@@ -2035,6 +2223,7 @@ static bool sample_group(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, 
     }, 2);
     HostDenoise denoise(ctx, p, W, H, C, nb);
     denoise.n_sigmas = (int)sigmas.size();
+    denoise.b0       = b0;
     ctx->step_cache_begin_trajectory(sigmas, method);  // init_sample_cache_runtime per sample() call, stable-diffusion.cpp:2578
     denoise.sc = &ctx->step_cache;
     std::vector<float> denoised(per * nb);
@@ -2383,6 +2572,30 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
         }
     }
     sdm_ctx_t::SamplerState::Cache* cc = rt.armed() ? st.cache.get() : nullptr;
+    // latent previews: with a denoised preview installed, `denoised` of a due step passes through preview.denoised (like variant 3 passes it through
+    // spectrum.denoised) and the byte stage reads it there behind the step graph; with none installed nothing below exists
+    const PreviewState& pvs = ctx->preview;
+    if (pvs.on() && pvs.denoised && !st.preview) {
+        st.preview.reset(new sdm_ctx_t::SamplerState::Preview());
+        auto& sp_ = *st.preview;
+        ggml_init_params ip{0, nullptr, true};
+        sp_.cctx     = ggml_init(ip);
+        sp_.denoised = ggml_new_tensor_4d(sp_.cctx, GGML_TYPE_F32, W, H, C, nb);
+        ggml_set_name(sp_.denoised, "preview.denoised");
+        sp_.buf = ggml_backend_alloc_ctx_tensors(sp_.cctx, ctx->backend);
+        if (!sp_.buf) {
+            st.preview.reset();
+            set_error("preview state allocation failed");
+            return false;
+        }
+        static std::atomic<uint64_t> g_preview_serial{0};
+        sp_.serial = ++g_preview_serial;
+        sp_.step_runner.backend = sp_.skip_runner.backend = ctx->backend;
+        sp_.step_runner.graph_size = ctx->unet_runner.graph_size;
+        sp_.skip_runner.graph_size = ctx->skip_runner.graph_size;
+    }
+    sdm_ctx_t::SamplerState::Preview* pvt = (pvs.on() && pvs.denoised) ? st.preview.get() : nullptr;
+    const std::string preview_tag         = pvt ? " preview" + std::to_string(pvt->serial) : std::string();
     int pending = -1;  // trace record of the computed step whose record-pass sums have not been read back yet
     auto book_pending = [&](const float* stats) {  // after_condition of that step: cond, then uncond (which only marks its difference as stored)
         sdm_cache_step_t* rec = &rt.trace[(size_t)pending];
@@ -2473,6 +2686,7 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             predict_step    = rt.spectrum_begin_call(i + 1, sigma);
             spectrum_record = !predict_step && !(rt.spectrum.stop_step > 0 && rt.spectrum.cnt >= rt.spectrum.stop_step);
         }
+        const bool pv_den = pvt && pvs.wants(i + 1, false);  // this call's denoised is previewed: variants 0, 1 and 2 pass it through preview.denoised
         // variant 0: the step graph; 1: the same, recording (noised passes through cache.in, eps through cache.out); 2: the skip-step graph (no model call);
         // 3: the step graph with denoised passing through spectrum.denoised; 4: the predicted-step graph (denoised IS spectrum.denoised, no model call)
         auto build_variant = [&](int variant) {
@@ -2521,6 +2735,7 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             }
             ggml_tensor* den = variant == 4 ? ss->denoised : ggml_add(c, ggml_mul(c, guided, S(2)), ggml_mul(c, xs, S(3)));  // stable-diffusion.cpp:2876
             if (variant == 3) den = ggml_cpy(c, den, ss->denoised);
+            if (pv_den && variant <= 2) den = ggml_cpy(c, den, pvt->denoised);
             ggml_tensor* xn;
             if (euler_a) {  // denoiser.hpp:1513-1546
                 xn = ggml_add(c, ggml_mul(c, xs, S(4)), ggml_mul(c, den, S(5)));
@@ -2539,8 +2754,11 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             ptrs.push_back(si.guidance.data());
             ptrs.push_back(si.pe().data());
         }
+        const std::string pv_tag = pv_den ? preview_tag : std::string();  // a capturing graph is a plan of its own; steps without a preview keep the signatures they had
+        if (pvs.wants(i + 1, true) && !predict_step && !emit_preview(ctx, i + 1, true, b0, W, H, C, nb, nullptr, st.x, c_in)) return false;  // the model input, x * c_in
         if (skip_step) {
-            if (!ctx->skip_runner.compute(build_variant(2), nullptr, 0, skip_sig, {sc})) return false;
+            if (!(pv_den ? pvt->skip_runner : ctx->skip_runner).compute(build_variant(2), nullptr, 0, skip_sig + pv_tag, {sc})) return false;
+            if (pv_den && !emit_preview(ctx, i + 1, false, b0, W, H, C, nb, nullptr, pvt->denoised, 1.0f)) return false;
             continue;
         }
         if (predict_step) {
@@ -2552,11 +2770,15 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
                 return false;
             }
             if (!ctx->skip_runner.compute(build_variant(4), nullptr, 0, spectrum_step_sig, {sc})) return false;
+            if (pv_den && !emit_preview(ctx, i + 1, false, b0, W, H, C, nb, nullptr, ss->denoised, 1.0f)) return false;  // the forecast
             continue;
         }
-        if (!r.compute(build_variant(record_step ? 1 : (spectrum_record ? 3 : 0)), nullptr, 0,
-                       record_step ? record_sig : (spectrum_record ? spectrum_record_sig : std::string(step_sig)), ptrs))
+        const int variant = record_step ? 1 : (spectrum_record ? 3 : 0);  // (3 already has its denoised in spectrum.denoised: no capture, the signature it had)
+        const bool capture = pv_den && variant != 3;
+        if (!(capture ? pvt->step_runner : r).compute(build_variant(variant), nullptr, 0,
+                                                      (record_step ? record_sig : (spectrum_record ? spectrum_record_sig : std::string(step_sig))) + (capture ? pv_tag : std::string()), ptrs))
             return false;
+        if (capture) ++r.calls;  // (sd_stats_t::unet_calls counts the step graphs issued, whichever runner held them)
         if (ss) {  // SpectrumState::update: the counters, and — while a forecast can still follow — the tensor
             const int slot = rt.spectrum.update();
             if (spectrum_record && !cache_dev.spectrum_push(ss->denoised, ss->ring, ss->stride, slot, (int64_t)(per * (size_t)nb))) {
@@ -2571,6 +2793,7 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
             }
             pending = (int)rt.trace.size() - 1;
         }
+        if (pv_den && !emit_preview(ctx, i + 1, false, b0, W, H, C, nb, nullptr, variant == 3 ? ss->denoised : pvt->denoised, 1.0f)) return false;
         if (pair) {
             if (!ctx->pair_fn(st.eps->data, (int64_t)(per * nb), pair_stream, ctx->pair_user)) {
                 set_error("CFG-pair exchange failed");
@@ -2799,6 +3022,102 @@ bool sd_step_cache_kernels(sdm_ctx_t* ctx, const float* in, const float* out, co
     return ok;
 }
 
+// ---- latent previews (csrc/host/preview.hpp) -----------------------------------------------------------------------------------
+bool sdm_set_preview_callback(sdm_ctx_t* ctx, sdm_preview_cb_t cb, int mode, int interval, bool denoised, bool noisy, void* data) {
+    if (cb && (mode < SDM_PREVIEW_NONE || mode > SDM_PREVIEW_VAE)) {
+        set_error("sdm_set_preview_callback: mode must be one of sdm_preview_t");
+        return false;
+    }
+    PreviewState& pv = ctx->preview;
+    pv.cb            = (cb && mode != SDM_PREVIEW_NONE) ? cb : nullptr;
+    pv.user          = data;
+    pv.mode          = pv.cb ? mode : SDM_PREVIEW_NONE;
+    pv.interval      = interval;
+    pv.denoised      = denoised;
+    pv.noisy         = noisy;
+    // off: every sampler path is the one without previews again.  What a preview allocated (preview.denoised, the capturing graphs' compute buffer, the upload tensor)
+    // stays until the sampler state or the context goes: freeing a backend buffer makes the backend drop every cached plan, and a front end that installs a callback per
+    // generation must not pay a re-plan of the step graph for it
+    return true;
+}
+int sdm_preview_first_image(sdm_ctx_t* ctx) { return ctx->preview_current.first_image; }
+int64_t sdm_preview_latent(sdm_ctx_t* ctx, float* out, int64_t capacity, float* in_scale) {
+    const sdm_ctx_t::PreviewCurrent& cur = ctx->preview_current;
+    if (!cur.active) return 0;
+    if (in_scale) *in_scale = cur.in_scale;
+    const int64_t n = std::min(cur.floats, capacity);
+    if (out && n > 0) {
+        if (cur.host)
+            memcpy(out, cur.host, (size_t)n * sizeof(float));
+        else
+            ggml_backend_tensor_get(cur.dev, out, 0, (size_t)n * sizeof(float));
+    }
+    return cur.floats;
+}
+bool sdm_set_preview_projection(sdm_ctx_t* ctx, const float* proj, const float* bias, int c) {
+    PreviewState& pv = ctx->preview;
+    if (!proj) {
+        pv.custom_proj.clear();
+        pv.custom_c = 0;
+        return true;
+    }
+    if (c < 1 || c > PREVIEW_MAX_CHANNELS) {
+        set_error("sdm_set_preview_projection: 1 .. 128 channels");
+        return false;
+    }
+    pv.custom_proj.assign(proj, proj + 3 * (size_t)c);
+    for (int k = 0; k < 3; ++k) pv.custom_bias[k] = bias ? bias[k] : 0.0f;
+    pv.custom_c = c;
+    return true;
+}
+bool sdm_preview_device_passes(sdm_ctx_t* ctx) { return PreviewDevice(ctx->backend).on_device(); }
+bool sdm_latent_preview(sdm_ctx_t* ctx, const float* latents, int w, int h, int c, int n, float in_scale, uint8_t* out_rgb) {
+    const float *proj = nullptr, *bias = nullptr;
+    if (!latents || !out_rgb || w < 1 || h < 1 || n < 1 || c < 1 || c > PREVIEW_MAX_CHANNELS || !preview_table(ctx, c, &proj, &bias)) {
+        set_error("sdm_latent_preview: bad arguments (a NULL buffer, more than 128 channels, or no projection known for this channel count)");
+        return false;
+    }
+    PreviewDevice pd(ctx->backend);
+    if (pd.exports_missing) {
+        set_error("sdm_latent_preview: the MI355X backend does not export its preview passes");
+        return false;
+    }
+    if (!preview_proj_host_latent(ctx, pd, latents, w, h, c, n, in_scale, proj, bias, out_rgb)) {
+        set_error("sdm_latent_preview: the pass could not be run");
+        return false;
+    }
+    return true;
+}
+bool sdm_planar_to_u8(sdm_ctx_t* ctx, const float* chw, int w, int h, int n, uint8_t* out_rgb) {
+    if (!chw || !out_rgb || w < 1 || h < 1 || n < 1) {
+        set_error("sdm_planar_to_u8: bad arguments");
+        return false;
+    }
+    PreviewDevice pd(ctx->backend);
+    if (pd.exports_missing) {
+        set_error("sdm_planar_to_u8: the MI355X backend does not export its preview passes");
+        return false;
+    }
+    const int64_t plane = (int64_t)w * h;
+    if (!pd.on_device()) return planar_to_u8_host(chw, plane, n, 1.0f, 0.0f, out_rgb);
+    ggml_init_params ip{0, nullptr, true};
+    ggml_context* c  = ggml_init(ip);
+    ggml_tensor* t   = ggml_new_tensor_4d(c, GGML_TYPE_F32, w, h, 3, n);
+    ggml_backend_buffer_t buf = ggml_backend_alloc_ctx_tensors(c, ctx->backend);
+    if (!buf) {
+        ggml_free(c);
+        set_error("sdm_planar_to_u8: allocation failed");
+        return false;
+    }
+    ggml_backend_tensor_set_async(ctx->backend, t, chw, 0, (size_t)plane * 3 * n * sizeof(float));
+    const bool ok = pd.u8_k(ctx->backend, (const float*)t->data, plane, n, 1.0f, 0.0f, out_rgb);
+    ggml_backend_synchronize(ctx->backend);
+    if (!ok) set_error("sdm_planar_to_u8: the pass could not be enqueued");
+    ggml_backend_buffer_free(buf);
+    ggml_free(c);
+    return ok;
+}
+
 bool sd_sample_latents(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, float* out_latents) {
     const int W = p->width / 8, H = p->height / 8, C = ctx->in_channels();
     const size_t per = (size_t)W * H * C;
@@ -2816,6 +3135,10 @@ bool sd_sample_latents(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, float* out
             set_error("step cache: not available with a CFG-pair exchange (the anchor condition lives on one rank only)");
             return false;
         }
+    }
+    if (ctx->preview.on() && ctx->pair_fn != nullptr && p->device_sampler) {
+        set_error("preview: not available with a CFG-pair exchange on the device-resident sampler (both ranks would synchronise and deliver the same frames)");
+        return false;
     }
     for (int b0 = 0; b0 < p->batch_count; b0 += group) {
         const int nb = std::min(group, p->batch_count - b0);

@@ -79,6 +79,15 @@ bool launch_step_cache_probe_rel(hipStream_t s, const float* x, float c_in, cons
 // every operation rounded on its own; order / weights: k (2 .. 16) HOST values, order[j] in 0 .. 15.  false (nothing enqueued): bad arguments
 bool launch_spectrum_predict(hipStream_t s, const float* ring, int64_t slot_stride, const int* order, int k, const float* weights, float w, int64_t n, float* out);
 
+// ---- preview.hip: the byte stages of the latent previews (one rounded f32 operation per step, bytes equal to the host restatement in csrc/host/preview.hpp) ----
+// x [plane, c, n] f32 planar -> out [n * plane][3] RGB bytes: v = x * in_scale (only when in_scale != 1), the c x 3 projection in ascending channel order + bias,
+// * .5f + .5f, clamp to [0, 1] (NaN -> 0), truncation.  proj: c * 3 HOST floats ([c][3]) or NULL (c == 3: the channels are r, g, b); bias: 3 HOST floats or NULL
+// (zeros).  false (nothing enqueued): c > 128, no table with c != 3, an empty input or a NULL buffer
+bool launch_latent_preview(hipStream_t s, const float* x, int64_t plane, int c, int64_t n, float in_scale, const float* proj, const float* bias, uint8_t* out);
+// x [plane, 3, n] f32 planar -> out [n * plane][3]: v = x * in_mul + in_add (only when (in_mul, in_add) != (1, 0)); v <= 0 or NaN -> 0, v >= 1 -> 255, else
+// (uint8_t)(v * 255.0f + 0.5f)
+bool launch_planar_to_u8(hipStream_t s, const float* x, int64_t plane, int64_t n, float in_mul, float in_add, uint8_t* out);
+
 // ---- norm.hip ---------------------------------------------------------------------------------------
 // GROUP_NORM over [W*H, C, N] contiguous f32; optional fused affine (w,b per channel) and SiLU
 void launch_group_norm(hipStream_t s, float* dst, const float* x, int64_t hw, int64_t C, int64_t N, int groups, float eps,
