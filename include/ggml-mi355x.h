@@ -106,6 +106,21 @@ struct ggml_backend_mi355x_stats {
     int64_t flash_generic_launches; /* ... that took a !FAST instantiation (generic staging: f32 or strided K / V, d % 8 != 0) */
     int64_t fused_gn_epilogue;   /* GroupNorms (direct, or over a skip CONCAT) whose statistics pass was replaced by k_gn_finalize over the per-channel records the producing conv epilogues wrote (option fuse_gn_epilogue) */
     int64_t fused_tile_merge;    /* overlap merges of a VAE tile batch (MUL by the row ramps -> MUL by the column ramps -> per tile ADD in place / CPY into a view of the canvas) run as ONE gather launch of k_tile_merge (option fuse_tile_merge) */
+    /* elementwise.hip: launches per kernel route, counted where each launcher chooses (per launch call, not per plan; a hipGraph replay launches without choosing) */
+    int64_t ew_bin_same;         /* launch_binary: k_bin_same (same shape, contiguous, 16-byte aligned) */
+    int64_t ew_bin_rowvec;       /* ... k_bin_rowvec ([ne0] over rows) */
+    int64_t ew_bin_tokvec;       /* ... k_bin_tokvec ([C,1,N] over [C,L,N]) */
+    int64_t ew_bin_chan;         /* ... k_bin_chan ([1,1,C,N'] over [W,H,C,N]) */
+    int64_t ew_bin_generic;      /* ... k_bin_generic (byte strides, broadcast by modulo) */
+    int64_t ew_copy_contig;      /* launch_copy: k_copy_contig */
+    int64_t ew_copy_transpose;   /* ... k_transpose (LDS-tiled batched 2-D transpose) */
+    int64_t ew_copy_rows;        /* ... k_copy_rows (rows of ne0 contiguous on both sides) */
+    int64_t ew_copy_generic;     /* ... k_copy_generic */
+    int64_t ew_concat_dim2;      /* launch_concat: k_concat_dim2 */
+    int64_t ew_concat_planes;    /* ... k_concat_planes */
+    int64_t ew_concat_generic;   /* ... k_concat */
+    int64_t ew_tile_merge_v4;    /* launch_tile_merge: k_tile_merge<4> */
+    int64_t ew_tile_merge_v1;    /* ... k_tile_merge<1> */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and

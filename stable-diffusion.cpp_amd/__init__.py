@@ -207,7 +207,7 @@ ggml_soft_max_inplace ggml_soft_max_ext ggml_im2col ggml_conv_2d ggml_conv_2d_di
 ggml_timestep_embedding ggml_flash_attn_ext ggml_new_graph ggml_new_graph_custom ggml_graph_node ggml_set_name
 ggml_gallocr_new ggml_backend_load ggml_backend_dev_get ggml_backend_dev_by_name ggml_backend_dev_init
 ggml_backend_get_default_buffer_type ggml_backend_alloc_ctx_tensors ggml_backend_dev_buffer_type ggml_unary
-ggml_unary_inplace ggml_get_rows ggml_dup sdm_new_ctx""".split()
+ggml_unary_inplace ggml_get_rows ggml_dup ggml_neg ggml_exp ggml_pad_ext sdm_new_ctx""".split()
 
 
 def lib() -> C.CDLL:
@@ -229,11 +229,12 @@ def lib() -> C.CDLL:
     L.ggml_view_4d.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int64] * 4 + [C.c_size_t] * 4
     L.ggml_view_3d.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int64] * 3 + [C.c_size_t] * 3
     L.ggml_view_2d.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int64] * 2 + [C.c_size_t] * 2
+    L.ggml_view_1d.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_size_t]
     for n in ("ggml_add", "ggml_add_inplace", "ggml_sub", "ggml_mul", "ggml_mul_inplace", "ggml_div", "ggml_mul_mat",
               "ggml_cpy", "ggml_repeat", "ggml_get_rows"):
         getattr(L, n).argtypes = [C.c_void_p] * 3
     for n in ("ggml_silu", "ggml_silu_inplace", "ggml_gelu", "ggml_gelu_inplace", "ggml_gelu_quick", "ggml_sigmoid",
-              "ggml_tanh", "ggml_relu", "ggml_cont", "ggml_transpose", "ggml_soft_max", "ggml_soft_max_inplace", "ggml_dup"):
+              "ggml_tanh", "ggml_relu", "ggml_neg", "ggml_exp", "ggml_cont", "ggml_transpose", "ggml_soft_max", "ggml_soft_max_inplace", "ggml_dup"):
         getattr(L, n).argtypes = [C.c_void_p] * 2
     L.ggml_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
     L.ggml_scale_inplace.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
@@ -249,6 +250,7 @@ def lib() -> C.CDLL:
     L.ggml_conv_2d_direct.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6
     L.ggml_upscale.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.ggml_pad.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4
+    L.ggml_pad_ext.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 8
     L.ggml_timestep_embedding.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.ggml_flash_attn_ext.argtypes = [C.c_void_p] * 5 + [C.c_float] * 3
     L.ggml_flash_attn_ext_set_prec.argtypes = [C.c_void_p, C.c_int]
@@ -408,7 +410,9 @@ def load_mi355x_backend() -> None:
 _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned kernels_launched fused_conv fused_conv_bounced fused_linear "
                         "fused_norm fused_geglu fused_attention generic_matmul swizzled_weight_bytes graph_replays fused_linear_geglu "
                         "split_k_gemms head_major_gemms fused_modulate fused_gate fused_gelu fused_rope fused_concat_heads qgemv_linears fused_chan_add fused_proj_tokens gemm_attention fused_q16 split_k_inlaunch qgemm16_linears fgemv_linears fused_presilu fused_sibling_linears hoisted_kv_linears window_convs hoisted_emb_linears fused_rows16 fused_joint_qkv jit_images fused_cat_rows16 fused_gn_stats fused_ln_reduce redirect_fallbacks fused_concat_gn fused_conv_scale view_graphs plans_evicted hoisted_mod_linears view_external_nodes qinloop_linears flash_out_alias flash_slice_images "
-                        "flash_short_launches flash_qb2_launches flash_mslot_launches flash_generic_launches fused_gn_epilogue fused_tile_merge").split()
+                        "flash_short_launches flash_qb2_launches flash_mslot_launches flash_generic_launches fused_gn_epilogue fused_tile_merge "
+                        "ew_bin_same ew_bin_rowvec ew_bin_tokvec ew_bin_chan ew_bin_generic ew_copy_contig ew_copy_transpose ew_copy_rows ew_copy_generic "
+                        "ew_concat_dim2 ew_concat_planes ew_concat_generic ew_tile_merge_v4 ew_tile_merge_v1").split()
 
 
 class BackendStats(C.Structure):

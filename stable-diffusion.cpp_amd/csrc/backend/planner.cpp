@@ -2895,11 +2895,16 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
         case GGML_OP_IM2COL: {
             const int32_t* p = n->op_params;
             View4 x          = view_of(n->src[1]);
+            if (!p[6]) {  // 1-D form: input [IW, IC, N] -> the kernel's [IW, IH = 1, IC, N] (ih is always 0: s1 = p1 = d1 = 0 and OH = KH = 1)
+                x.ne[3] = x.ne[2], x.nb[3] = x.nb[2];
+                x.ne[2] = x.ne[1], x.nb[2] = x.nb[1];
+                x.ne[1] = 1;
+            }
             const int64_t KW = n->src[0]->ne[0], KH = p[6] ? n->src[0]->ne[1] : 1;
             const int64_t OW = n->ne[1], OH = p[6] ? n->ne[2] : 1;
             void* dst        = n->data;
             const int dt     = (int)n->type;
-            const int s0 = p[0], s1 = p[1], p0 = p[2], p1 = p[3], d0 = p[4], d1 = p[5];
+            const int s0 = p[0], s1 = p[6] ? p[1] : 0, p0 = p[2], p1 = p[6] ? p[3] : 0, d0 = p[4], d1 = p[6] ? p[5] : 0;
             B.emit([=](hipStream_t st) { launch_im2col_f16(st, dst, dt, x, KW, KH, OW, OH, s0, s1, p0, p1, d0, d1); });
             return true;
         }
@@ -4154,6 +4159,7 @@ bool planner_supports_op(const ggml_tensor* n) {
         case GGML_OP_UPSCALE:
         case GGML_OP_PAD:
             if (xop(n) == GGML_OP_UPSCALE && n->op_params[0] != GGML_SCALE_MODE_NEAREST) return false;
+            if (xop(n) == GGML_OP_CONCAT && !f32c(n->src[1])) return false;  // k_concat* read both sources as f32
             return f32c(n) && f32c(n->src[0]);
         case GGML_OP_GET_ROWS: {
             const ggml_tensor *a = n->src[0], *b = n->src[1];
@@ -4185,6 +4191,10 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     o->flash_qb2_launches     = flash_attn_variant_launches(FLASH_VAR_QB2);
     o->flash_mslot_launches   = flash_attn_variant_launches(FLASH_VAR_MSLOT);
     o->flash_generic_launches = flash_attn_variant_launches(FLASH_VAR_GENERIC);
+    // ... and where the elementwise launchers choose theirs: the ew_* fields lie in the order of EwRoute
+    static_assert(offsetof(ggml_backend_mi355x_stats, ew_tile_merge_v1) - offsetof(ggml_backend_mi355x_stats, ew_bin_same) == (EW_ROUTE_COUNT - 1) * sizeof(int64_t),
+                  "ggml_backend_mi355x_stats: one ew_* field per EwRoute, in its order");
+    for (int r = 0; r < EW_ROUTE_COUNT; ++r) (&o->ew_bin_same)[r] = elementwise_route_launches(r);
 }
 
 namespace {

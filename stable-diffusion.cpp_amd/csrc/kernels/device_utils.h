@@ -72,7 +72,7 @@ __device__ __forceinline__ float act_apply(float x) {
     if (OP == UN_TANH) return tanhf(x);
     if (OP == UN_RELU) return x > 0.f ? x : 0.f;
     if (OP == UN_NEG) return -x;
-    return __expf(x);
+    return expf(x);  // the EXP node is the library exp: __expf flushes a subnormal result to zero (exp(-88) = 6.05e-39, which ggml-cpu's expf keeps)
 }
 __device__ __forceinline__ float act_dyn(int op, float x) {
     switch (op) {
@@ -83,7 +83,7 @@ __device__ __forceinline__ float act_dyn(int op, float x) {
         case UN_TANH: return act_apply<UN_TANH>(x);
         case UN_RELU: return act_apply<UN_RELU>(x);
         case UN_NEG: return -x;
-        case UN_EXP: return __expf(x);
+        case UN_EXP: return expf(x);
         default: return x;
     }
 }

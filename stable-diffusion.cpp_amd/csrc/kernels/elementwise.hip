@@ -6,7 +6,16 @@
 #include "ktime.h"
 #include "device_utils.h"
 
+#include <atomic>
+#include <cstdio>
+#include <cstdlib>
+
 namespace mi355x {
+
+// launches per route (kernels.h EwRoute), for the statistics: one relaxed increment where a launcher has chosen its kernel
+static std::atomic<int64_t> g_route_launches[EW_ROUTE_COUNT];
+static inline void route_taken(EwRoute r) { g_route_launches[r].fetch_add(1, std::memory_order_relaxed); }
+int64_t elementwise_route_launches(int route) { return route >= 0 && route < EW_ROUTE_COUNT ? g_route_launches[route].load(std::memory_order_relaxed) : 0; }
 
 static inline double v4_elems(const View4& v) { return (double)v.ne[0] * (double)v.ne[1] * (double)v.ne[2] * (double)v.ne[3]; }
 static inline double v4_esize(const View4& v) { return v.type == 0 ? 4.0 : (v.type == 1 || v.type == 30 ? 2.0 : 4.0); }
@@ -117,15 +126,18 @@ static void binary_dispatch(hipStream_t s, void* dst, const int64_t dnb[4], cons
     if (ac && bc && al16) {
         const bool same = a.ne[0] == b.ne[0] && a.ne[1] == b.ne[1] && a.ne[2] == b.ne[2] && a.ne[3] == b.ne[3];
         if (same) {
+            route_taken(EW_BIN_SAME);
             k_bin_same<OP><<<grid_for(n / 4 + 1, block), block, 0, s>>>((float*)dst, (const float*)a.data, (const float*)b.data, n / 4, n);
             return;
         }
         if (b.ne[0] == a.ne[0] && b.ne[1] == 1 && b.ne[2] == 1 && b.ne[3] == 1 && a.ne[0] % 4 == 0) {
+            route_taken(EW_BIN_ROWVEC);
             k_bin_rowvec<OP><<<grid_for(n / 4, block), block, 0, s>>>((float*)dst, (const float*)a.data, (const float*)b.data, n / 4, (int)(a.ne[0] / 4));
             return;
         }
         // [C,1,N] broadcast over the tokens of [C,L,N] (adaLN modulate / gate of the DiT blocks, mmdit.hpp:368-380)
         if (b.ne[0] == a.ne[0] && b.ne[1] == 1 && a.ne[1] > 1 && b.ne[2] == a.ne[2] && b.ne[3] == 1 && a.ne[3] == 1 && a.ne[0] % 4 == 0) {
+            route_taken(EW_BIN_TOKVEC);
             k_bin_tokvec<OP><<<grid_for(n / 4, block), block, 0, s>>>((float*)dst, (const float*)a.data, (const float*)b.data, n / 4, (int)(a.ne[0] / 4),
                                                                      a.ne[0] / 4 * a.ne[1]);
             return;
@@ -133,6 +145,7 @@ static void binary_dispatch(hipStream_t s, void* dst, const int64_t dnb[4], cons
         // [1,1,C,N'] broadcast over [W,H,C,N] (conv bias, group-norm affine, time-embedding add)
         const int64_t inner = a.ne[0] * a.ne[1];
         if (b.ne[0] == 1 && b.ne[1] == 1 && b.ne[2] == a.ne[2] && inner % 4 == 0 && (b.ne[3] == 1 || b.ne[3] == a.ne[3])) {
+            route_taken(EW_BIN_CHAN);
             k_bin_chan<OP><<<grid_for(n / 4, block), block, 0, s>>>((float*)dst, (const float*)a.data, (const float*)b.data, n / 4, inner / 4,
                                                                    (int)a.ne[2], (int)b.ne[3], (int)a.ne[3]);
             return;
@@ -146,6 +159,7 @@ static void binary_dispatch(hipStream_t s, void* dst, const int64_t dnb[4], cons
         g.dnb[i] = dnb[i];
         g.bne[i] = b.ne[i];
     }
+    route_taken(EW_BIN_GENERIC);
     k_bin_generic<OP><<<grid_for(n, block), block, 0, s>>>((char*)dst, (const char*)a.data, (const char*)b.data, g, n);
 }
 
@@ -230,6 +244,7 @@ void launch_tile_merge(hipStream_t s, float* canvas, const float* tiles, const f
     KScope ks_(s, KF_BINARY, 0.0, cells * a.planes * 4.0 + (double)a.bw * a.bh * a.planes * 8.0);  // read every tile cell once, read + write the box of the canvas
     const int64_t n = (int64_t)(a.bw / (v4 ? 4 : 1)) * a.bh * a.planes;
     if (n <= 0) return;
+    route_taken(v4 ? EW_TILE_MERGE_V4 : EW_TILE_MERGE_V1);
     if (v4)
         k_tile_merge<4><<<grid_for(n, 256), 256, 0, s>>>(canvas, tiles, wx, wy, a);
     else
@@ -352,6 +367,7 @@ static void copy_typed(hipStream_t s, const View4& dst, const View4& src) {
     };
     const bool dc = contig(dst, sizeof(TD)), sc = contig(src, sizeof(TS));
     if (dc && sc && (((uintptr_t)dst.data | (uintptr_t)src.data) & 15) == 0) {
+        route_taken(EW_COPY_CONTIG);
         k_copy_contig<TS, TD><<<grid_for(n / 4 + 1, 256), 256, 0, s>>>((TD*)dst.data, (const TS*)src.data, n);
         return;
     }
@@ -368,11 +384,14 @@ static void copy_typed(hipStream_t s, const View4& dst, const View4& src) {
             sbs = 0;
             dbs = 0;
         }
-        const int Cc = (int)src.ne[0];
-        dim3 grid((unsigned)((R + 63) / 64), (unsigned)((Cc + 63) / 64), (unsigned)(nb1 * src.ne[3]));
-        k_transpose<TS, TD><<<grid, 256, 0, s>>>((TD*)dst.data, (const TS*)src.data, (int)R, Cc, src.nb[0] / sizeof(TS), Cc,
-                                                  sbs / sizeof(TS), dbs / sizeof(TD), (int)nb1, src.nb[3] / sizeof(TS), dst.nb[3] / sizeof(TD));
-        return;
+        if (nb1 * src.ne[3] <= 65535) {  // grid.z carries the batch: beyond its limit the launch would fail, the generic route below takes the copy
+            const int Cc = (int)src.ne[0];
+            dim3 grid((unsigned)((R + 63) / 64), (unsigned)((Cc + 63) / 64), (unsigned)(nb1 * src.ne[3]));
+            route_taken(EW_COPY_TRANSPOSE);
+            k_transpose<TS, TD><<<grid, 256, 0, s>>>((TD*)dst.data, (const TS*)src.data, (int)R, Cc, src.nb[0] / sizeof(TS), Cc,
+                                                      sbs / sizeof(TS), dbs / sizeof(TD), (int)nb1, src.nb[3] / sizeof(TS), dst.nb[3] / sizeof(TD));
+            return;
+        }
     }
     CopyArgs g;
     for (int i = 0; i < 4; ++i) {
@@ -387,10 +406,12 @@ static void copy_typed(hipStream_t s, const View4& dst, const View4& src) {
                     ((uintptr_t)dst.data % da) == 0;
         for (int i = 1; i < 4; ++i) rows = rows && src.nb[i] % sa == 0 && dst.nb[i] % da == 0;
         if (rows) {
+            route_taken(EW_COPY_ROWS);
             k_copy_rows<TS, TD><<<grid_for(n / 4, 256), 256, 0, s>>>((char*)dst.data, (const char*)src.data, g, n / 4);
             return;
         }
     }
+    route_taken(EW_COPY_GENERIC);
     k_copy_generic<TS, TD><<<grid_for(n, 256), 256, 0, s>>>((char*)dst.data, (const char*)src.data, g, n);
 }
 
@@ -403,6 +424,8 @@ void launch_copy(hipStream_t s, const View4& dst, const View4& src) {
     if (src.type == F16 && dst.type == F16) return copy_typed<__half, __half>(s, dst, src);
     if (src.type == F32 && dst.type == BF16) return copy_typed<float, bf16_t>(s, dst, src);
     if (src.type == BF16 && dst.type == F32) return copy_typed<bf16_t, float>(s, dst, src);
+    fprintf(stderr, "[ggml-mi355x] launch_copy: unsupported type pair %d -> %d (planner_supports_op admits f32/f16 <-> f32/f16 and f32 <-> bf16)\n", src.type, dst.type);
+    abort();
 }
 
 // ---------------------------------------------------------------------------------------- rotary embedding (interleaved pairs)
@@ -557,6 +580,7 @@ void launch_concat(hipStream_t s, const View4& dst, const View4& a, const View4&
     if (dim == 2 && contig_f32(a.ne, a.nb) && contig_f32(b.ne, b.nb) && contig_f32(dst.ne, dst.nb)) {
         const int64_t sa = a.ne[0] * a.ne[1] * a.ne[2], sb = b.ne[0] * b.ne[1] * b.ne[2];
         if (sa % 4 == 0 && sb % 4 == 0 && (((uintptr_t)a.data | (uintptr_t)b.data | (uintptr_t)dst.data) & 15) == 0) {
+            route_taken(EW_CONCAT_DIM2);
             k_concat_dim2<<<grid_for(n / 4, 256), 256, 0, s>>>((float4*)dst.data, (const float4*)a.data, (const float4*)b.data, sa / 4, sb / 4, n / 4);
             return;
         }
@@ -567,11 +591,13 @@ void launch_concat(hipStream_t s, const View4& dst, const View4& a, const View4&
             return v.nb[0] == 4 && (v.ne[1] == 1 || v.nb[1] == v.ne[0] * 4) && v.nb[2] % 16 == 0 && v.nb[3] % 16 == 0 && (((uintptr_t)v.data) & 15) == 0;
         };
         if (plane % 4 == 0 && plane_ok(a) && plane_ok(b) && (((uintptr_t)dst.data) & 15) == 0) {
+            route_taken(EW_CONCAT_PLANES);
             k_concat_planes<<<grid_for(n / 4, 256), 256, 0, s>>>((float4*)dst.data, (const char*)a.data, (const char*)b.data, plane / 4, a.ne[2], b.ne[2], a.nb[2], a.nb[3],
                                                                 b.nb[2], b.nb[3], n / 4);
             return;
         }
     }
+    route_taken(EW_CONCAT_GENERIC);
     k_concat<<<grid_for(n, 256), 256, 0, s>>>((char*)dst.data, (const char*)a.data, (const char*)b.data, mk(dst), mk(a), mk(b), dim, n);
 }
 

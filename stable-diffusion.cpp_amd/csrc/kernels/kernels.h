@@ -19,6 +19,15 @@ enum BinOp { BIN_ADD = 0, BIN_SUB = 1, BIN_MUL = 2, BIN_DIV = 3 };
 enum UnOp { UN_SILU = 0, UN_GELU = 1, UN_GELU_QUICK = 2, UN_SIGMOID = 3, UN_TANH = 4, UN_RELU = 5, UN_NEG = 6, UN_EXP = 7 };
 
 // ---- elementwise.hip --------------------------------------------------------------------------------
+// Which kernel a launcher chose, counted per launch call where the choice is made (as FlashVariant is): the tests assert the route a shape takes.
+enum EwRoute {
+    EW_BIN_SAME = 0, EW_BIN_ROWVEC, EW_BIN_TOKVEC, EW_BIN_CHAN, EW_BIN_GENERIC,
+    EW_COPY_CONTIG, EW_COPY_TRANSPOSE, EW_COPY_ROWS, EW_COPY_GENERIC,
+    EW_CONCAT_DIM2, EW_CONCAT_PLANES, EW_CONCAT_GENERIC,
+    EW_TILE_MERGE_V4, EW_TILE_MERGE_V1,
+    EW_ROUTE_COUNT
+};
+int64_t elementwise_route_launches(int route);
 // dst = a (op) broadcast(b); a/dst f32 with arbitrary strides, b f32 broadcast by modulo on every dim
 void launch_binary(hipStream_t s, BinOp op, void* dst, const int64_t dnb[4], const View4& a, const View4& b);
 // Overlap merge of one VAE tile batch (planner: plan_tile_merge; the reference's sd_tensor_merge_2d, src/core/ggml_extend.hpp:771-821, for up to TILE_MERGE_MAX tiles

@@ -145,8 +145,14 @@ class Graph:
         ts = tensor_struct(t)
         shape = [int(ts.ne[i]) for i in range(3, -1, -1)]
         nbytes = L.ggml_nbytes(t)
-        dt = {F32: np.float32, F16: np.float16}[ts.type]
+        dt = {F32: np.float32, F16: np.float16, BF16: np.uint16}[ts.type]
         out = np.empty(shape, dtype=dt)
-        assert out.nbytes == nbytes, (out.nbytes, nbytes, shape)
-        L.ggml_backend_tensor_get(t, out.ctypes.data_as(C.c_void_p), 0, nbytes)
+        if out.nbytes != nbytes:  # a strided view (the result of an in-place op on one): read the bytes it spans, pick its elements
+            raw = np.empty(nbytes, dtype=np.uint8)
+            L.ggml_backend_tensor_get(t, raw.ctypes.data_as(C.c_void_p), 0, nbytes)
+            out = np.lib.stride_tricks.as_strided(raw.view(dt), shape, [int(ts.nb[i]) for i in range(3, -1, -1)]).copy()
+        else:
+            L.ggml_backend_tensor_get(t, out.ctypes.data_as(C.c_void_p), 0, nbytes)
+        if ts.type == BF16:  # the stored bits are the top half of the float32 with the same value
+            return (out.astype(np.uint32) << 16).view(np.float32)
         return out.astype(np.float32)

@@ -64,7 +64,13 @@ def test_merge_exact_and_batches_match_oracle(sd, engines, name, w, h, n):
         o.set_vae_tiling(False)
 
 
-def _fusion_ab(sd, run, n_batches):
+def _merge_routes(s0, s1):
+    """launches of k_tile_merge<4> and k_tile_merge<1> between two statistics snapshots"""
+    return s1["ew_tile_merge_v4"] - s0["ew_tile_merge_v4"], s1["ew_tile_merge_v1"] - s0["ew_tile_merge_v1"]
+
+
+def _fusion_ab(sd, run, n_batches, route=None):
+    """route: "v4" = every merge launch takes the float4 kernel, "v1" = at least one takes the scalar kernel (asserted with the fused merge on)"""
     out, launched, fused = {}, {}, {}
     for on in (0, 1):
         if ON_GPU:
@@ -75,6 +81,9 @@ def _fusion_ab(sd, run, n_batches):
             s1 = sd.backend_stats()
             launched[on] = s1["kernels_launched"] - s0["kernels_launched"]
             fused[on] = s1["fused_tile_merge"] - s0["fused_tile_merge"]
+            v4, v1 = _merge_routes(s0, s1)
+            if not os.environ.get("SDCPP_BACKEND_OPTS"):
+                assert (v4, v1) == (0, 0) if not on else (v4 > 0 and v1 == 0) if route == "v4" else v1 > 0 if route == "v1" else True, (on, route, v4, v1)
     np.testing.assert_array_equal(out[0], out[1])
     if ON_GPU:
         print(f"kernels launched: plain {launched[0]}, fused {launched[1]}; fused merges planned {fused[1]} for {n_batches} tile batches")
@@ -89,12 +98,13 @@ def test_fused_merge_decode(sd, engines):
     p = sd.tiling_plan(19, 17, **TILE)
     try:
         g.set_vae_tiling(True, tile_batch=4, **TILE)
-        _fusion_ab(sd, lambda: g.vae_decode(z, raw=True), -(-len(p["tiles"]) // 4))
+        # decode geometry: positions and skips are multiples of 8 pixels, every launch takes k_tile_merge<4>
+        _fusion_ab(sd, lambda: g.vae_decode(z, raw=True), -(-len(p["tiles"]) // 4), route="v4")
         # overlap 0 in both axes: the store path (CPY), 16 x 16 latent in four tiles, two per batch
         g.set_vae_tiling(True, tile_size_x=8, tile_size_y=8, target_overlap=0.0, tile_batch=2)
         q = sd.tiling_plan(16, 16, tile_size_x=8, tile_size_y=8, target_overlap=0.0)
         assert q["overlap"] == (0, 0) and len(q["tiles"]) == 4
-        _fusion_ab(sd, lambda: g.vae_decode(latent("SD15_TINY", 16, 16, 1), raw=True), 2)
+        _fusion_ab(sd, lambda: g.vae_decode(latent("SD15_TINY", 16, 16, 1), raw=True), 2, route="v4")
     finally:
         if ON_GPU:
             sd.backend_set_option("fuse_tile_merge", 1)
@@ -110,21 +120,33 @@ def test_fused_merge_encode_odd_offsets(sd, engines):
     assert any(t[0] % 2 or t[1] % 2 for t in p["tiles"]) and any(t[2] or t[3] for t in p["tiles"])
     try:
         g.set_vae_tiling(True, tile_batch=3, **kw)
-        mom = _fusion_ab(sd, lambda: g.vae_encode(img, seed=4, return_moments=True)[1], -(-len(p["tiles"]) // 3))
+        mom = _fusion_ab(sd, lambda: g.vae_encode(img, seed=4, return_moments=True)[1], -(-len(p["tiles"]) // 3), route="v1")
         o.set_vae_tiling(True, **kw)
         want = o.vae_encode(img, seed=4, return_moments=True)[1]
         err = float(np.linalg.norm((mom - want).astype(np.float64)) / np.linalg.norm(want.astype(np.float64)))
         print(f"tiled encode moments vs the oracle's: rel-L2 {err:.2e}")
         assert np.isfinite(mom).all() and err < 5e-3   # the per-forward bar of tests/test_gpu_model.py
-        # the identity in place of the model: the merge alone, bit for bit against numpy, at odd sizes (scalar path) and at multiples of 4 (float4 path)
-        for (w, h, tx, ty, ov, tb) in ((19, 17, 8, 8, 0.3, 3), (11, 9, 8, 4, 0.25, 2), (64, 40, 32, 32, 0.5, 4), (8, 8, 4, 4, 0.0, 3)):
+        # the identity in place of the model: the merge alone, bit for bit against numpy, at odd sizes (scalar path), at multiples of 4 (float4 path), and at the
+        # float4 path's near miss: a canvas and tiles of multiples of 4 cells with one tile per batch at x = 0, 6, 12 (the middle batch has bx % 4 != 0)
+        for (w, h, tx, ty, ov, tb, route) in ((19, 17, 8, 8, 0.3, 3, "v1"), (11, 9, 8, 4, 0.25, 2, "v1"), (64, 40, 32, 32, 0.5, 4, "v4"), (8, 8, 4, 4, 0.0, 3, None),
+                                              (20, 8, 8, 8, 0.25, 1, "v1+v4")):
             x = np.random.default_rng(w + h).standard_normal((2, 3, h, w)).astype(np.float32)
             g.set_vae_tiling(True, tile_size_x=tx, tile_size_y=ty, target_overlap=ov, tile_batch=tb)
             q = sd.tiling_plan(w, h, tile_size_x=tx, tile_size_y=ty, target_overlap=ov)
             canvas = np.zeros_like(x)
             for (px, py, dx, dy) in q["tiles"]:
                 ref.merge(canvas, x[:, :, py:py + q["tile_size"][1], px:px + q["tile_size"][0]], px, py, q["overlap"][0], q["overlap"][1], dx, dy)
+            s0 = sd.backend_stats() if ON_GPU else None
             np.testing.assert_array_equal(g.tiling_blend(x), canvas)
+            if ON_GPU and not os.environ.get("SDCPP_BACKEND_OPTS"):
+                v4, v1 = _merge_routes(s0, sd.backend_stats())
+                print(f"blend {w}x{h} tiles {tx}x{ty} batch {tb}: k_tile_merge<4> launches {v4}, k_tile_merge<1> launches {v1}")
+                if route == "v1":
+                    assert v4 == 0 and v1 > 0
+                elif route == "v4":
+                    assert v4 > 0 and v1 == 0
+                elif route == "v1+v4":
+                    assert [t[0] for t in q["tiles"]] == [0, 6, 12] and v1 > 0 and v4 > 0
     finally:
         if ON_GPU:
             sd.backend_set_option("fuse_tile_merge", 1)
