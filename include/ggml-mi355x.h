@@ -121,6 +121,25 @@ struct ggml_backend_mi355x_stats {
     int64_t ew_concat_generic;   /* ... k_concat */
     int64_t ew_tile_merge_v4;    /* launch_tile_merge: k_tile_merge<4> */
     int64_t ew_tile_merge_v1;    /* ... k_tile_merge<1> */
+    /* conv3w.hip / gemm16.hip: conv launches per kernel route, counted where each launcher chooses (per launch call, as the ew_* fields are) */
+    int64_t c3w_tw16_bn256;      /* launch_conv3w: k_conv3w<TW = 16, BN = 256> (16-wide maps, 256-column tile) */
+    int64_t c3w_tw16_bn320;      /* ... k_conv3w<16, 320> */
+    int64_t c3w_tw32_bn256;      /* ... k_conv3w<32, 256> */
+    int64_t c3w_tw32_bn320;      /* ... k_conv3w<32, 320> */
+    int64_t c3w_tw64_bn256;      /* ... k_conv3w<64, 256> */
+    int64_t c3w_tw64_bn320;      /* ... k_conv3w<64, 320> */
+    int64_t c3w_tw128_bn256;     /* ... k_conv3w<128, 256> */
+    int64_t c3w_tw128_bn320;     /* ... k_conv3w<128, 320> */
+    int64_t g16_conv_t128;       /* launch_gemm16_conv: k_gemm16<128, 128, CONV> */
+    int64_t g16_conv_t128n64;    /* ... k_gemm16<128, 64, CONV> (the 64-column form: OC <= 64) */
+    int64_t g16_conv_t256;       /* ... 256 x 128, eight waves */
+    int64_t g16_conv_t256w;      /* ... 256 x 128, four waves */
+    int64_t g16_conv_t160;       /* ... 256 x 160, four waves */
+    int64_t g16_conv_t160n;      /* ... 256 x 160, eight waves */
+    int64_t g16_conv_t320;       /* ... 256 x 320, pipelined */
+    int64_t g16_conv_t256p;      /* ... 256 x 256, pipelined */
+    int64_t g16_conv_splitk_reduce; /* plain k_splitk_reduce launches behind a split conv (either kernel family; not k_splitk_reduce_gn, not the in-launch combine) */
+    int64_t g16_conv_wmajor;     /* conv launches (either kernel family) that took the weight-major workgroup order (option conv_wmajor) */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and

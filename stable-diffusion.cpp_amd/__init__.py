@@ -412,7 +412,10 @@ _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned 
                         "split_k_gemms head_major_gemms fused_modulate fused_gate fused_gelu fused_rope fused_concat_heads qgemv_linears fused_chan_add fused_proj_tokens gemm_attention fused_q16 split_k_inlaunch qgemm16_linears fgemv_linears fused_presilu fused_sibling_linears hoisted_kv_linears window_convs hoisted_emb_linears fused_rows16 fused_joint_qkv jit_images fused_cat_rows16 fused_gn_stats fused_ln_reduce redirect_fallbacks fused_concat_gn fused_conv_scale view_graphs plans_evicted hoisted_mod_linears view_external_nodes qinloop_linears flash_out_alias flash_slice_images "
                         "flash_short_launches flash_qb2_launches flash_mslot_launches flash_generic_launches fused_gn_epilogue fused_tile_merge "
                         "ew_bin_same ew_bin_rowvec ew_bin_tokvec ew_bin_chan ew_bin_generic ew_copy_contig ew_copy_transpose ew_copy_rows ew_copy_generic "
-                        "ew_concat_dim2 ew_concat_planes ew_concat_generic ew_tile_merge_v4 ew_tile_merge_v1").split()
+                        "ew_concat_dim2 ew_concat_planes ew_concat_generic ew_tile_merge_v4 ew_tile_merge_v1 "
+                        "c3w_tw16_bn256 c3w_tw16_bn320 c3w_tw32_bn256 c3w_tw32_bn320 c3w_tw64_bn256 c3w_tw64_bn320 c3w_tw128_bn256 c3w_tw128_bn320 "
+                        "g16_conv_t128 g16_conv_t128n64 g16_conv_t256 g16_conv_t256w g16_conv_t160 g16_conv_t160n g16_conv_t320 g16_conv_t256p "
+                        "g16_conv_splitk_reduce g16_conv_wmajor").split()
 
 
 class BackendStats(C.Structure):

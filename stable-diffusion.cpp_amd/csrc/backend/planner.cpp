@@ -4195,6 +4195,10 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     static_assert(offsetof(ggml_backend_mi355x_stats, ew_tile_merge_v1) - offsetof(ggml_backend_mi355x_stats, ew_bin_same) == (EW_ROUTE_COUNT - 1) * sizeof(int64_t),
                   "ggml_backend_mi355x_stats: one ew_* field per EwRoute, in its order");
     for (int r = 0; r < EW_ROUTE_COUNT; ++r) (&o->ew_bin_same)[r] = elementwise_route_launches(r);
+    // ... and where the conv launchers choose theirs: the c3w_* / g16_conv_* fields lie in the order of ConvRoute
+    static_assert(offsetof(ggml_backend_mi355x_stats, g16_conv_wmajor) - offsetof(ggml_backend_mi355x_stats, c3w_tw16_bn256) == (CONV_ROUTE_COUNT - 1) * sizeof(int64_t),
+                  "ggml_backend_mi355x_stats: one c3w_* / g16_conv_* field per ConvRoute, in its order");
+    for (int r = 0; r < CONV_ROUTE_COUNT; ++r) (&o->c3w_tw16_bn256)[r] = conv_route_launches(r);
 }
 
 namespace {

@@ -364,6 +364,8 @@ bool conv3w_gn_rec_supported(int64_t OHOW, int64_t OC, int64_t N) { return OHOW 
 
 template <int TW, int BN>
 static void c3_launch(hipStream_t s, const G16Args& g, unsigned tiles, unsigned ny) {
+    conv_route_taken((ConvRoute)(CONV_C3W_TW16_BN256 + (TW == 16 ? 0 : TW == 32 ? 2 : TW == 64 ? 4 : 6) + (BN == 320 ? 1 : 0)));
+    if (g.worder > 0) conv_route_taken(CONV_WMAJOR);
     if constexpr (BN == 320 && TW <= 64) {
         if (g_conv3w_prio == 0) return (void)k_conv3w<TW, BN, 0><<<dim3(tiles, ny), 512, 0, s>>>(g);
     }

@@ -1255,6 +1255,10 @@ int gemm16_worder_rows(const G16Args& g, unsigned gx, unsigned ny) {
     return wts >= 2.0 * act ? nrow : 0;
 }
 static bool g16_trace();
+// conv launches per route (kernels.h ConvRoute), for the statistics: one relaxed increment where a launcher has chosen its kernel
+static std::atomic<int64_t> g_conv_route_launches[CONV_ROUTE_COUNT];
+void conv_route_taken(ConvRoute r) { g_conv_route_launches[r].fetch_add(1, std::memory_order_relaxed); }
+int64_t conv_route_launches(int route) { return route >= 0 && route < CONV_ROUTE_COUNT ? g_conv_route_launches[route].load(std::memory_order_relaxed) : 0; }
 // conv launches whose epilogue fills a GroupNorm side band (Epilogue::gn_rec, epi_conv_gn): unsplit, a 256-row tile with four wave rows of two row blocks
 // or eight wave rows of one (256 x 160 with four or eight waves, 256 x 320, 256 x 256 pipelined; not the 256 x 128 tiles), whole column tiles, whole GN_REC_CHUNK-position tiles per image
 static bool g16_gn_rec_tile_ok(int tile, int64_t C, int64_t ohow, int ny) {
@@ -1322,6 +1326,8 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                 G16Args t    = g;
                 t.ncol_tiles = tile == G16_T320 ? (int)((g.C + 319) / 320) : (tile == G16_T256P ? (int)((g.C + 255) / 256) : ((tile == G16_T160 || tile == G16_T160N) ? (int)(g.C / 160) : g.ncol_tiles));
                 g.worder     = gemm16_worder_rows(t, (unsigned)(rt256 * t.ncol_tiles * mul), ny);
+                if (g.worder > 0) conv_route_taken(CONV_WMAJOR);
+                conv_route_taken(tile == G16_T320 ? CONV_G16_T320 : tile == G16_T256P ? CONV_G16_T256P : tile == G16_T160 ? CONV_G16_T160 : tile == G16_T160N ? CONV_G16_T160N : tile == G16_T256W ? CONV_G16_T256W : CONV_G16_T256);
             }
             if (tile == G16_T320) {
                 g.ncol_tiles = (int)((g.C + 319) / 320);
@@ -1399,6 +1405,7 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
         }
     }
     if (CONV_ && g.ep.gn_rec) g16_gn_rec_contract_violation();  // 128-row tiles do not fill a side band
+    if (CONV_) conv_route_taken(BN_ == 64 ? CONV_G16_T128N64 : CONV_G16_T128);
     const dim3 grid((unsigned)(((rows + 127) / 128) * g.ncol_tiles * mul), ny);
     KScope ks_(s, CONV_ ? KF_CONV_T128 : KF_LINEAR, flops, bytes);
     // (measured and rejected: the hand-pipelined loop of the 256x320 tile instantiated for a 128x128 tile — 2 waves of 64x128, 4 stages, two
@@ -1804,6 +1811,7 @@ const _Float16* gemm16_zero_page() { return zero_page(); }
 }
 void launch_splitk_reduce_conv(hipStream_t s, float* dst, const float* ws, int S, int64_t n, const float* bias, int64_t inner, int64_t C, const float* residual,
                                const float* chan_add, int64_t chan_ld) {
+    conv_route_taken(CONV_SPLITK_REDUCE);
     launch_splitk_reduce(s, dst, ws, S, n, bias, inner, C, residual, chan_add, chan_ld);
 }
 // the same with the statistics of the GroupNorm that reads the output next (e.gn_*); falls back to the plain pass when the shape is not served
@@ -1812,8 +1820,10 @@ void launch_splitk_reduce_conv_gn(hipStream_t s, float* dst, const float* ws, in
     if (e.gn_scale && !gn_ok) g16_gn_contract_violation();
     if (e.gn_scale)
         launch_splitk_reduce_gn(s, dst, ws, S, hw, C, N, e);
-    else
+    else {
+        conv_route_taken(CONV_SPLITK_REDUCE);
         launch_splitk_reduce(s, dst, ws, S, hw * C * N, e.bias, hw, C, e.residual, e.chan_add, e.chan_ld);
+    }
 }
 
 // GGML_MI355X_TRACE=1: one stderr line per launch (shape), in launch order — joined with a rocprofv3 kernel trace by scripts/shape_stats.py
@@ -2088,8 +2098,10 @@ void launch_gemm16_conv(hipStream_t s, float* dst, const void* x16_nhwc, const v
         if (e.gn_scale && !gn_ok) g16_gn_contract_violation();
         if (e.gn_scale)
             launch_splitk_reduce_gn(s, dst, splitk_ws, S, g.OHOW, OC, N, e);
-        else
+        else {
+            conv_route_taken(CONV_SPLITK_REDUCE);
             launch_splitk_reduce(s, dst, splitk_ws, S, g.R * OC, e.bias, g.OHOW, OC, e.residual, e.chan_add, e.chan_ld);
+        }
     }
 }
 

@@ -243,6 +243,17 @@ void launch_gemm16_conv(hipStream_t s, float* dst, const void* x16_nhwc, const v
                         int ksize, int stride, int pad, bool upscale2x, const Epilogue& ep, float* splitk_ws = nullptr, int* splitk_cnt = nullptr, int splitk_S = 0);
 // an UNSPLIT launch_gemm16_conv of this shape can fill a GnRec side band (Epilogue::gn_rec): a 256-row tile = GN_REC_CHUNK positions of one image
 bool gemm16_conv_gn_rec_supported(int64_t OHOW, int64_t N, int64_t OC, int64_t ICp, int ksize);
+// Which kernel a conv launcher chose, counted per launch call where the choice is made (as EwRoute is): the tests assert the route a shape takes.
+// CONV_C3W_*: c3_launch<TW, BN> in the order (TW 16 / 32 / 64 / 128) x (BN 256 / 320); CONV_G16_*: the conv branch of g16_launch
+enum ConvRoute {
+    CONV_C3W_TW16_BN256 = 0, CONV_C3W_TW16_BN320, CONV_C3W_TW32_BN256, CONV_C3W_TW32_BN320, CONV_C3W_TW64_BN256, CONV_C3W_TW64_BN320, CONV_C3W_TW128_BN256, CONV_C3W_TW128_BN320,
+    CONV_G16_T128, CONV_G16_T128N64, CONV_G16_T256, CONV_G16_T256W, CONV_G16_T160, CONV_G16_T160N, CONV_G16_T320, CONV_G16_T256P,
+    CONV_SPLITK_REDUCE,  // plain k_splitk_reduce behind a split conv
+    CONV_WMAJOR,         // the launch took the weight-major workgroup order
+    CONV_ROUTE_COUNT
+};
+void conv_route_taken(ConvRoute r);
+int64_t conv_route_launches(int route);
 // ---- conv3w.hip: 3x3 / stride-1 conv with the input window resident in LDS (weights in the kblk = 32 image)
 // K slices the window kernel would run this shape with (>= 1), or 0: the shape stays on launch_gemm16_conv
 int conv3w_plan(int64_t W, int64_t H, int64_t IC, int64_t N, int64_t OC, int ksize, int stride, bool upscale2x, int* bn_out = nullptr);
