@@ -140,6 +140,11 @@ struct ggml_backend_mi355x_stats {
     int64_t g16_conv_t256p;      /* ... 256 x 256, pipelined */
     int64_t g16_conv_splitk_reduce; /* plain k_splitk_reduce launches behind a split conv (either kernel family; not k_splitk_reduce_gn, not the in-launch combine) */
     int64_t g16_conv_wmajor;     /* conv launches (either kernel family) that took the weight-major workgroup order (option conv_wmajor) */
+    /* guidance.hip: the device-resident sampler's glue around an inpaint / pix2pix UNet */
+    int64_t fused_model_input;   /* [MUL by the step's c_in ->] [RESHAPE -> REPEAT over the K branches -> RESHAPE ->] CONCAT(dim 2) with the [REPEATed] concat latent run as ONE launch of k_model_input (option fuse_model_input) */
+    int64_t fused_guidance3;     /* the six nodes of the three-conditioning CFG combine over views of one [per, 3, nb] tensor run as ONE launch of k_guidance3 (option fuse_guidance3) */
+    int64_t ew_model_input_v4;   /* launch_model_input: k_model_input<4> (plane a multiple of 4 floats, bases 16-byte aligned); per launch call, as the ew_* fields above */
+    int64_t ew_model_input_v1;   /* ... k_model_input<1> */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and
@@ -205,7 +210,15 @@ GGML_MI355X_API int ggml_backend_mi355x_get_kernel_timings(struct ggml_backend_m
  * "fuse_gn_epilogue" (1: an unsplit LDS-window conv read by a GroupNorm, or by a skip CONCAT a GroupNorm reads, writes per-channel (mean, M2) records of the values it
  * stores; the GroupNorm's statistics pass over the tensor becomes one small finalize launch over the records; 0 = the plan without it);
  * "fuse_tile_merge" (1: the overlap merge of a VAE tile batch — two MULs by the ramp vectors and one ADD in place / CPY per tile into views of the canvas — as one
- * launch of k_tile_merge: every canvas cell of the batch's bounding box is read and written once, results bit-identical to the plain nodes; timed in family 11).
+ * launch of k_tile_merge: every canvas cell of the batch's bounding box is read and written once, results bit-identical to the plain nodes; timed in family 11);
+ * "fuse_model_input" (1: the model input of the device-resident sampler on an inpaint / pix2pix UNet — x * c_in, tiled over the K branches of every image, with the
+ * branch's constant concat latent appended along the channels — as one launch of k_model_input instead of MUL, REPEAT, [REPEAT,] CONCAT and three intermediates.
+ * The MUL is folded in only when the chain is its sole reader; otherwise it runs and the kernel copies its result.  Refused — the nodes run plain — when an
+ * intermediate is a graph output or has a reader outside the chain (a sub-graph view that cuts the chain included), when a tensor is not f32 or not contiguous;
+ * bit-identical to the plain nodes; timed in family 12),
+ * "fuse_guidance3" (1: the three-conditioning CFG combine iu + img * (u - iu) + txt * (c - u) over the views (c, u, iu) of one [per, 3, nb] tensor — SUB, MUL, ADD,
+ * SUB, MUL, ADD — as one launch of k_guidance3, the two scales read from the step's scalar tensor on the device, every operation rounded on its own; the same
+ * refusals; bit-identical to the plain nodes; timed in family 11).
  * An unknown key changes nothing and is named on stderr.  Wrong-result timing ablations exist only in builds with -DMI355X_EXPERIMENTS ("gemm16_abl"). */
 GGML_MI355X_API void ggml_backend_mi355x_set_option(const char* key, int value);
 /* What the calling thread's current device delivers, measured in about a second (csrc/kernels/calib.hip): an MFMA loop from registers (f16, 32x32x16: the

@@ -183,6 +183,22 @@ SD_API void sdm_img_gen_params_init(sdm_img_gen_params_t* p);
 SD_API sdm_ctx_t* sdm_new_ctx(const sdm_ctx_params_t* params); /* NULL on failure (no device, alloc failure) */
 SD_API void sdm_free_ctx(sdm_ctx_t* ctx);
 SD_API const char* sd_last_error(void);
+/* UNet variants whose first conv is wider than the latent: the SD1.x / SDXL inpainting checkpoints (9 input channels: x 4 | mask 1 | masked-image latent 4, the
+ * concat order of stable-diffusion.cpp:5166-5169) and the instruct-pix2pix edit checkpoints (8: x 4 | image latent 4), the reference's VERSION_*_INPAINT /
+ * VERSION_*_PIX2PIX (src/model_loader.cpp: input_blocks.0.0.weight ne[2] == 9 / 8).  Only "model.diffusion_model.input_blocks.0.0.weight" changes shape
+ * ([3,3,9|8,mc]; synthetic weights from the same seeded initialiser, sd_load_weights takes a real one); out channels, the latent (noise, x, VAE) and everything else
+ * stay the family's.  The extra channels enter every model call as c_concat (unet.hpp:554-559): sd_unet_forward_concat, sd_set_concat_condition.
+ * Valid for SD_MODEL_SD15 / SDXL / SD15_TINY / SDXL_TINY; any other family with a non-plain variant returns NULL (sd_last_error).  sdm_new_ctx(p) is
+ * sdm_new_ctx_variant(p, SDM_UNET_PLAIN).  (A separate entry point and not a field: sdm_ctx_params_t is mirrored by every binding.)
+ * SD1.x pix2pix quirk of the reference: sd_vae_encode on an SD15 / SD15_TINY PIX2PIX context returns the MEAN of the moments, neither sampled nor scaled to the
+ * diffusion range (auto_encoder_kl.hpp:764-765, stable-diffusion.cpp:3056-3058); SDXL pix2pix encodes normally. */
+enum sdm_unet_variant_t { SDM_UNET_PLAIN = 0, SDM_UNET_INPAINT = 1, SDM_UNET_PIX2PIX = 2 };
+SD_API sdm_ctx_t* sdm_new_ctx_variant(const sdm_ctx_params_t* params, int variant);
+SD_API int sd_unet_variant(sdm_ctx_t* ctx);
+SD_API int sd_concat_channels(sdm_ctx_t* ctx);   /* 0, 5 or 4 */
+/* reads only the header of a safetensors / GGUF / PyTorch checkpoint, finds "model.diffusion_model.input_blocks.0.0.weight" after name conversion (a diffusers
+ * "conv_in.weight" counts) and returns the variant from its input width ne[2]: 4 -> 0, 9 -> 1, 8 -> 2; -1 (sd_last_error) when the tensor is absent or has another width */
+SD_API int sd_probe_unet_variant(const char* path);
 
 /* ---- weights by name ("model.diffusion_model.<...>", "first_stage_model.<...>") ---- */
 SD_API int64_t sd_tensor_count(sdm_ctx_t* ctx);
@@ -216,6 +232,11 @@ SD_API bool sd_convert_tensor_name(sdm_ctx_t* ctx, const char* name, char* out, 
 SD_API bool sd_unet_forward(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps,
                             const float* context, int64_t ctx_dim, int64_t n_tokens, int64_t ctx_n,
                             const float* y, int64_t y_dim, int64_t y_n, float* out);
+/* the forward of an inpaint / pix2pix UNet (sdm_new_ctx_variant): c_concat [w,h,cc,concat_n], concat_n 1 or n, cc = sd_concat_channels(ctx).  The graph emits what
+ * UnetModelBlock::forward emits (unet.hpp:554-559): [REPEAT to batch n,] CONCAT(x, c_concat, dim 2) in front of input_blocks.0.0.  sd_unet_forward on a variant
+ * context is an error ("model needs c_concat"), never a silent zero-fill; so is a wrong cc */
+SD_API bool sd_unet_forward_concat(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim, int64_t n_tokens,
+                                   int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const float* c_concat, int cc, int concat_n, float* out);
 /* the same forward WITHOUT the listed joint blocks — MMDiT::forward's skip_layers (mmdit.hpp:854-866), the extra evaluation of skip-layer guidance; MMDiT family only */
 SD_API bool sd_unet_forward_skip_layers(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim,
                                         int64_t n_tokens, int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const int* skip_layers, int n_skip, float* out);
@@ -406,6 +427,41 @@ SD_API void sd_set_guidance(sdm_ctx_t* ctx, float guidance); /* FLUX distilled-g
 /* the host sampler's classifier-free-guidance combine on n floats: out = uncond + scale * (cond - uncond), three separately rounded f32 operations like
  * sd::guidance::ClassifierFreeGuidance::forward on sd::Tensor<float> (src/runtime/guidance.cpp:171) — bit-exact against that code compiled into oracle/_ref */
 SD_API void sd_cfg_combine(const float* cond, const float* uncond, int64_t n, float scale, float* out);
+/* ---- c_concat and three-conditioning guidance of the inpaint / pix2pix UNets: the reference's mask_image + inpaint versions, guidance.img_cfg, ref_images[0] of the
+ * UNet edit models.  Context state like sd_set_vae_tiling, read by sd_sample_latents / sdm_generate_image on the host loop and the device-resident sampler.
+ * concat [w,h,cc,n] (latent cells; cc = sd_concat_channels): n = 1 shared by the batch (the reference's case) or n = batch_count (device groups take their slice);
+ * NULL clears.  img_uncond_concat NULL derives the reference's default (stable-diffusion.cpp:5145, 5168, 5173): inpaint keeps the mask channel and zeroes the masked
+ * latent, pix2pix is all zeros.  cond and uncond both see `concat`; the third condition is uncond's text with `img_uncond_concat` (:5236-5237, 5265-5266, 5273).
+ * Branches exactly as resolve_guidance (:4237-4255): uncond runs iff img_cfg != txt_cfg (img_cfg 1: today's txt_cfg != 1), img_uncond iff img_cfg != 1; img_cfg
+ * INFINITY (the default) = 1.  On a plain context a value other than 1 is accepted and ignored (the reference's warning is left in sd_last_error).  The combine has
+ * ClassifierFreeGuidance::forward's three forms (guidance.cpp:162-176), every operation a separately rounded f32, left to right:
+ *   three branches iu + img * (u - iu) + txt * (c - u);  img_uncond only iu + txt * (c - iu);  uncond only u + txt * (c - u).
+ * The CFG++ methods' denoised_uncond takes img_uncond first, then uncond, then cond (:2880-2883).  A variant context sampled without a concat condition fails.
+ * Refused at sampling time (sd_last_error): a third branch together with adaptive projected guidance, with an armed step cache (two-branch concat sampling with a
+ * cache works) or with a CFG-pair exchange.  The device-resident sampler assembles the model input and combines the three predictions in one launch each on the
+ * MI355X backend (k_model_input / k_guidance3, include/ggml-mi355x.h options fuse_model_input / fuse_guidance3). */
+SD_API bool sd_set_concat_condition(sdm_ctx_t* ctx, const float* concat, const float* img_uncond_concat, int w, int h, int cc, int n);
+SD_API bool sd_set_img_cfg(sdm_ctx_t* ctx, float img_cfg);
+/* the combine on n floats; uncond or img_uncond NULL selects the two-prediction forms — bit-exact against guidance.cpp compiled into oracle/_ref */
+SD_API void sd_cfg_combine3(const float* cond, const float* uncond, const float* img_uncond, int64_t n, float txt_cfg, float img_cfg, float* out);
+/* The device-resident sampler's two glue stages on caller memory, as the graphs the sampler emits through the backend it uses (tests).
+ *   model input: x [w,h,c,nb], concat [w,h,cc,k] (shared: row j is branch j's) or [w,h,cc,k*nb] (concat_per_image) -> xin_out [w,h,c+cc,k*nb]: plane p < c of model
+ *                image b*k + j is x[b] * c_in, plane p >= c is the concat row (MUL -> RESHAPE -> REPEAT -> RESHAPE, [REPEAT,] CONCAT; k = 1: MUL, [REPEAT,] CONCAT)
+ *   guidance:    e3 [per,3,nb] (cond, uncond, img_uncond adjacent per image), per = w*h*c -> guided_out [per,nb], the six nodes of the three-term combine with the
+ *                scales read from the step's scalar tensor on the device
+ * Either stage is skipped when its output pointer is NULL. */
+SD_API bool sd_guidance_kernels(sdm_ctx_t* ctx, const float* x, float c_in, const float* concat, int w, int h, int c, int cc, int k, int nb, bool concat_per_image,
+                                float* xin_out, const float* e3, float txt_cfg, float img_cfg, float* guided_out);
+/* pixels -> the concat condition (prepare_image_generation_latents, stable-diffusion.cpp:4986-5010, 5127-5173, 5197-5203): rgb planar [w,h,3] in [0,1], mask [w,h].
+ * INPAINT: the mask is rounded (sd::ops::round: halves away from zero), latent mask = interpolate(NearestMax) to w/8 x h/8, masked image (1 - mask) * (rgb - 0.5) + 0.5
+ * encoded with sd_vae_encode(seed); concat_out [w/8,h/8,5] = latent mask | masked latent; img_uncond_concat_out = latent mask | zeros; denoise_mask_out [w/8,h/8] =
+ * the 3x3 / stride 1 / pad 1 max-pool of the latent mask; init_latent_out = the encoded unmasked image (sdm_img_gen_params_t::init_latent / denoise_mask).
+ * PIX2PIX: concat_out [w/8,h/8,4] = the encoded image (mask ignored, may be NULL), img_uncond_concat_out zeros, no denoise mask (not written).
+ * Optional outputs may be NULL. */
+SD_API bool sd_make_inpaint_condition(sdm_ctx_t* ctx, const float* rgb, const float* mask, int w, int h, uint64_t seed, float* concat_out, float* img_uncond_concat_out,
+                                      float* denoise_mask_out, float* init_latent_out);
+SD_API bool sd_latent_mask(const float* mask, int w, int h, float* out /* [w/8,h/8] */);   /* the two mask stages alone, for known-answer tests */
+SD_API bool sd_mask_max_pool3(const float* in, int w, int h, float* out);
 /* the pixel stage of sdm_generate_image on caller memory: planar CHW floats in [0, 1] -> interleaved RGB bytes (src/runtime/preprocessing.hpp:27-60); for the
  * bit-exact test against that header compiled into oracle/_ref */
 SD_API void sd_planar_rgb_to_u8(const float* chw, int width, int height, uint8_t* out);

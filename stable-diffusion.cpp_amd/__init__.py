@@ -43,6 +43,8 @@ CACHE_DBCACHE, CACHE_TAYLORSEER, CACHE_CACHE_DIT, CACHE_SPECTRUM = 3, 4, 5, 6
 # sdm_preview_t (include/sd-mi355x.h): the reference's preview_t values; sdm_preview_cb_t: (step, frame_count, frames, is_noisy, user)
 PREVIEW_NONE, PREVIEW_PROJ, PREVIEW_TAE, PREVIEW_VAE = 0, 1, 2, 3
 PREVIEW_CB_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, C.c_bool, C.c_void_p)
+# sdm_unet_variant_t (include/sd-mi355x.h): UNets whose first conv also reads c_concat — inpainting (mask 1 | masked-image latent 4) and instruct-pix2pix (image latent 4)
+UNET_PLAIN, UNET_INPAINT, UNET_PIX2PIX = 0, 1, 2
 
 
 class EngineError(RuntimeError):
@@ -415,7 +417,8 @@ _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned 
                         "ew_concat_dim2 ew_concat_planes ew_concat_generic ew_tile_merge_v4 ew_tile_merge_v1 "
                         "c3w_tw16_bn256 c3w_tw16_bn320 c3w_tw32_bn256 c3w_tw32_bn320 c3w_tw64_bn256 c3w_tw64_bn320 c3w_tw128_bn256 c3w_tw128_bn320 "
                         "g16_conv_t128 g16_conv_t128n64 g16_conv_t256 g16_conv_t256w g16_conv_t160 g16_conv_t160n g16_conv_t320 g16_conv_t256p "
-                        "g16_conv_splitk_reduce g16_conv_wmajor").split()
+                        "g16_conv_splitk_reduce g16_conv_wmajor "
+                        "fused_model_input fused_guidance3 ew_model_input_v4 ew_model_input_v1").split()
 
 
 class BackendStats(C.Structure):
@@ -522,8 +525,11 @@ class Engine:
     batch is a numpy array of shape [N, C, H, W]."""
 
     def __init__(self, model: int = SD15, backend: str | None = None, wtype: int = F16, flash_attn: bool = False,
-                 conv_direct: bool = False, weight_seed: int = 1234):
+                 conv_direct: bool = False, weight_seed: int = 1234, variant: int = UNET_PLAIN):
+        """variant: UNET_INPAINT / UNET_PIX2PIX make the UNet's first conv 9 / 8 channels wide (sdm_new_ctx_variant); the model then takes c_concat."""
         L = lib()
+        L.sdm_new_ctx_variant.argtypes = [C.POINTER(SdCtxParams), C.c_int]
+        L.sdm_new_ctx_variant.restype = C.c_void_p
         p = SdCtxParams()
         L.sdm_ctx_params_init(C.byref(p))
         if backend is None:
@@ -536,10 +542,11 @@ class Engine:
         p.diffusion_flash_attn = flash_attn
         p.diffusion_conv_direct = conv_direct
         p.weight_seed = weight_seed
-        self._ctx = L.sdm_new_ctx(C.byref(p))
+        self._ctx = L.sdm_new_ctx(C.byref(p)) if variant == UNET_PLAIN else L.sdm_new_ctx_variant(C.byref(p), variant)
         if not self._ctx:
             raise EngineError("sdm_new_ctx failed: " + L.sd_last_error().decode())
         self.model = model
+        self.variant = variant
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -697,14 +704,25 @@ class Engine:
             raise EngineError(f"sd_set_tensor_f32({name}) failed")
 
     # ---- hot path ----
-    def unet_forward(self, x: np.ndarray, timesteps: np.ndarray, context: np.ndarray, y: np.ndarray | None = None) -> np.ndarray:
-        """x [N,C,H,W]; timesteps [N]; context [Nc,77,ctx_dim] (Nc in {1,N}); y [Ny,adm] or None."""
+    def unet_forward(self, x: np.ndarray, timesteps: np.ndarray, context: np.ndarray, y: np.ndarray | None = None, c_concat: np.ndarray | None = None) -> np.ndarray:
+        """x [N,C,H,W]; timesteps [N]; context [Nc,77,ctx_dim] (Nc in {1,N}); y [Ny,adm] or None; c_concat [1 or N, cc, H, W] on an inpaint / pix2pix engine."""
         x = _f32(x)
         t = _f32(timesteps)
         ctxt = _f32(context)
         n, c, h, w = x.shape
         out = np.empty_like(x)
         yy = None if y is None else _f32(y)
+        if c_concat is not None:
+            cat = _f32(c_concat)
+            L = lib()
+            L.sd_unet_forward_concat.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                 C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+            L.sd_unet_forward_concat.restype = C.c_bool
+            assert cat.ndim == 4 and cat.shape[2:] == (h, w), "c_concat is [1 or N, cc, H, W]"
+            if not L.sd_unet_forward_concat(self._ctx, _fptr(x), w, h, c, n, _fptr(t), _fptr(ctxt), ctxt.shape[2], ctxt.shape[1], ctxt.shape[0], _fptr(yy),
+                                            0 if yy is None else yy.shape[1], 0 if yy is None else yy.shape[0], _fptr(cat), cat.shape[1], cat.shape[0], _fptr(out)):
+                raise EngineError("sd_unet_forward_concat failed: " + L.sd_last_error().decode())
+            return out
         ok = lib().sd_unet_forward(self._ctx, _fptr(x), w, h, c, n, _fptr(t), _fptr(ctxt), ctxt.shape[2], ctxt.shape[1],
                                    ctxt.shape[0], _fptr(yy), 0 if yy is None else yy.shape[1], 0 if yy is None else yy.shape[0],
                                    _fptr(out))
@@ -725,6 +743,90 @@ class Engine:
         if not L.sd_unet_forward_skip_layers(self._ctx, _fptr(x), w, h, c, n, _fptr(t), _fptr(ctxt), ctxt.shape[2], ctxt.shape[1], ctxt.shape[0], _fptr(yy),
                                              0 if yy is None else yy.shape[1], 0 if yy is None else yy.shape[0], sk.ctypes.data_as(C.c_void_p), sk.size, _fptr(out)):
             raise EngineError("sd_unet_forward_skip_layers failed: " + L.sd_last_error().decode())
+        return out
+
+    # ---- inpaint / pix2pix UNets: c_concat state, image guidance, the condition from pixels ----
+    def concat_channels(self) -> int:
+        lib().sd_concat_channels.argtypes = [C.c_void_p]
+        return int(lib().sd_concat_channels(self._ctx))
+
+    def unet_variant(self) -> int:
+        lib().sd_unet_variant.argtypes = [C.c_void_p]
+        return int(lib().sd_unet_variant(self._ctx))
+
+    def set_concat_condition(self, concat: np.ndarray | None, img_uncond_concat: np.ndarray | None = None) -> None:
+        """sd_set_concat_condition: concat [n, cc, h/8, w/8] with n = 1 (shared by the batch) or the batch count; None clears.  img_uncond_concat None: the
+        reference's default (inpaint: mask kept, masked latent zeroed; pix2pix: zeros)."""
+        L = lib()
+        L.sd_set_concat_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.sd_set_concat_condition.restype = C.c_bool
+        if concat is None:
+            L.sd_set_concat_condition(self._ctx, None, None, 0, 0, 0, 0)
+            return
+        cat = _f32(concat)
+        if cat.ndim == 3:
+            cat = cat[None]
+        iu = None if img_uncond_concat is None else _f32(img_uncond_concat).reshape(cat.shape)
+        n, cc, h, w = cat.shape
+        if not L.sd_set_concat_condition(self._ctx, _fptr(cat), _fptr(iu), w, h, cc, n):
+            raise EngineError("sd_set_concat_condition failed: " + L.sd_last_error().decode())
+
+    def set_img_cfg(self, img_cfg: float = float("inf")) -> str:
+        """sd_set_img_cfg: the image guidance scale (inf = unset = 1).  Returns the note a plain context leaves when it ignores a scale other than 1, else ''."""
+        L = lib()
+        L.sd_set_img_cfg.argtypes = [C.c_void_p, C.c_float]
+        L.sd_set_img_cfg.restype = C.c_bool
+        if not L.sd_set_img_cfg(self._ctx, img_cfg):
+            raise EngineError("sd_set_img_cfg failed: " + L.sd_last_error().decode())
+        ignored = self.variant == UNET_PLAIN and np.isfinite(img_cfg) and img_cfg != 1.0
+        return L.sd_last_error().decode() if ignored else ""
+
+    def guidance_kernels(self, x=None, c_in: float = 1.0, concat=None, k: int = 1, concat_per_image: bool = False, e3=None, txt_cfg: float = 1.0, img_cfg: float = 1.0):
+        """sd_guidance_kernels: the device-resident sampler's two glue stages on caller memory.  x [nb,C,H,W] and concat [k or k*nb, cc, H, W] -> xin
+        [k*nb, C+cc, H, W]; e3 [nb, 3, per] -> guided [nb, per].  Returns (xin or None, guided or None)."""
+        L = lib()
+        L.sd_guidance_kernels.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_bool, C.c_void_p, C.c_void_p,
+                                          C.c_float, C.c_float, C.c_void_p]
+        L.sd_guidance_kernels.restype = C.c_bool
+        xin = guided = None
+        xx = cat = ee = None
+        w = h = c = cc = 1
+        nb = 1
+        if x is not None:
+            xx, cat = _f32(x), _f32(concat)
+            nb, c, h, w = xx.shape
+            cc = cat.shape[1]
+            assert cat.shape == ((k * nb if concat_per_image else k), cc, h, w)
+            xin = np.full((k * nb, c + cc, h, w), np.nan, dtype=np.float32)  # an unwritten cell shows
+        if e3 is not None:
+            ee = _f32(e3)
+            assert ee.ndim == 3 and ee.shape[1] == 3
+            if x is None:
+                nb, w, h, c = ee.shape[0], ee.shape[2], 1, 1
+            assert ee.shape == (nb, 3, w * h * c)
+            guided = np.full((nb, w * h * c), np.nan, dtype=np.float32)
+        if not L.sd_guidance_kernels(self._ctx, _fptr(xx), c_in, _fptr(cat), w, h, c, cc, k, nb, concat_per_image, _fptr(xin), _fptr(ee), txt_cfg, img_cfg, _fptr(guided)):
+            raise EngineError("sd_guidance_kernels failed: " + L.sd_last_error().decode())
+        return xin, guided
+
+    def make_inpaint_condition(self, rgb: np.ndarray, mask: np.ndarray | None, seed: int = 42) -> dict:
+        """sd_make_inpaint_condition: rgb [3,H,W] in [0,1], mask [H,W] -> {"concat", "img_uncond_concat", "denoise_mask" (inpaint only), "init_latent"}."""
+        L = lib()
+        L.sd_make_inpaint_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sd_make_inpaint_condition.restype = C.c_bool
+        img = _f32(rgb)
+        _, h, w = img.shape
+        m = None if mask is None else _f32(mask)
+        cc = self.concat_channels()
+        cat = np.zeros((cc, h // 8, w // 8), dtype=np.float32)
+        iu = np.zeros_like(cat)
+        dm = np.zeros((h // 8, w // 8), dtype=np.float32)
+        il = np.zeros((4, h // 8, w // 8), dtype=np.float32)
+        if not L.sd_make_inpaint_condition(self._ctx, _fptr(img), _fptr(m), w, h, seed, _fptr(cat), _fptr(iu), _fptr(dm), _fptr(il)):
+            raise EngineError("sd_make_inpaint_condition failed: " + L.sd_last_error().decode())
+        out = {"concat": cat, "img_uncond_concat": iu, "init_latent": il}
+        if self.variant == UNET_INPAINT:
+            out["denoise_mask"] = dm
         return out
 
     def vae_decode(self, latents: np.ndarray, raw: bool = False) -> np.ndarray:
@@ -1242,6 +1344,58 @@ def cfg_combine(cond: np.ndarray, uncond: np.ndarray, scale: float) -> np.ndarra
     L.sd_cfg_combine.restype = None
     L.sd_cfg_combine(c.ctypes.data, u.ctypes.data, c.size, float(scale), out.ctypes.data)
     return out.reshape(np.shape(cond))
+
+
+def cfg_combine3(cond: np.ndarray, uncond: np.ndarray | None, img_uncond: np.ndarray | None, txt_cfg: float, img_cfg: float) -> np.ndarray:
+    """sd_cfg_combine3: the three forms of the reference's combine by which predictions exist — iu + img * (u - iu) + txt * (c - u); iu + txt * (c - iu)
+    (uncond None); u + txt * (c - u) (img_uncond None) — every operation rounded to f32, left to right."""
+    c = _f32(cond).ravel()
+    u = None if uncond is None else _f32(uncond).ravel()
+    iu = None if img_uncond is None else _f32(img_uncond).ravel()
+    assert (u is None or u.size == c.size) and (iu is None or iu.size == c.size)
+    out = np.empty_like(c)
+    L = lib()
+    L.sd_cfg_combine3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]
+    L.sd_cfg_combine3.restype = None
+    L.sd_cfg_combine3(c.ctypes.data, None if u is None else u.ctypes.data, None if iu is None else iu.ctypes.data, c.size, float(txt_cfg), float(img_cfg), out.ctypes.data)
+    return out.reshape(np.shape(cond))
+
+
+def latent_mask(mask: np.ndarray) -> np.ndarray:
+    """sd_latent_mask: mask [H,W] -> rounded (halves away from zero), max over every 8x8 block: [H/8, W/8]."""
+    m = _f32(mask)
+    h, w = m.shape
+    out = np.empty((h // 8, w // 8), dtype=np.float32)
+    L = lib()
+    L.sd_latent_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.sd_latent_mask.restype = C.c_bool
+    if not L.sd_latent_mask(m.ctypes.data, w, h, out.ctypes.data):
+        raise EngineError("sd_latent_mask failed: " + L.sd_last_error().decode())
+    return out
+
+
+def mask_max_pool3(m: np.ndarray) -> np.ndarray:
+    """sd_mask_max_pool3: the 3x3 / stride 1 / pad 1 max-pool of a [h, w] map (cells outside the map do not take part)."""
+    a = _f32(m)
+    h, w = a.shape
+    out = np.empty_like(a)
+    L = lib()
+    L.sd_mask_max_pool3.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.sd_mask_max_pool3.restype = C.c_bool
+    if not L.sd_mask_max_pool3(a.ctypes.data, w, h, out.ctypes.data):
+        raise EngineError("sd_mask_max_pool3 failed: " + L.sd_last_error().decode())
+    return out
+
+
+def probe_unet_variant(path) -> int:
+    """sd_probe_unet_variant: UNET_PLAIN / UNET_INPAINT / UNET_PIX2PIX from the input width of the checkpoint's first conv; raises when it is absent or of another width."""
+    L = lib()
+    L.sd_probe_unet_variant.argtypes = [C.c_char_p]
+    L.sd_probe_unet_variant.restype = C.c_int
+    v = L.sd_probe_unet_variant(str(path).encode())
+    if v < 0:
+        raise EngineError(L.sd_last_error().decode())
+    return v
 
 
 def philox_randn(seed: int, offset: int, n: int) -> np.ndarray:

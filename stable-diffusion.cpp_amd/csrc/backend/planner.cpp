@@ -168,7 +168,7 @@ std::atomic<int64_t> g_stat_counters[N_STATS];
 #define STAT(field) g_stat_counters[offsetof(ggml_backend_mi355x_stats, field) / sizeof(int64_t)]
 
 struct Options {
-    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1}, fuse_gn_epilogue{1}, fuse_tile_merge{1};
+    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1}, fuse_gn_epilogue{1}, fuse_tile_merge{1}, fuse_model_input{1}, fuse_guidance3{1};
 } g_opt;
 
 using Step = std::function<void(hipStream_t)>;  // one launch (or a few) of a plan
@@ -3653,6 +3653,161 @@ bool plan_tile_merge(Builder& B, int i, std::vector<int>& chain) {
     return true;
 }
 
+// Model input of the device-resident sampler on an inpaint / pix2pix UNet (csrc/host/engine.cpp sample_group_device; UnetModelBlock::forward's c_concat,
+// src/model/diffusion/unet.hpp:554-559), for K evaluations per image:
+//   noised = MUL(x [W,H,C,nb], c_in [1]) -> RESHAPE [per,1,nb] -> REPEAT [per,K,nb] -> RESHAPE [W,H,C,K*nb]        (K = 1: noised itself)
+//   cc_all = REPEAT(concat [W,H,cc,R] -> [W,H,cc,K*nb])                                                              (R = K*nb: the tensor itself)
+//   xin    = CONCAT(.., cc_all, dim 2)
+// -> ONE launch of k_model_input writing xin.  Anchored at the MUL when the chain is its sole reader (the product is folded in, the scalar read on the device), else
+// at the REPEAT (the MUL ran — the recording variant of the step cache copies it to cache.in — and its result is copied).  The intermediates are never written, so
+// the match refuses whenever anything else could read them: a second consumer, an OUTPUT flag, a reader outside a sub-graph view (GInfo's phantom consumer), a
+// non-view node between the chain's nodes; whenever a tensor is not f32 or not contiguous; and whenever the result shares memory with an operand.
+bool plan_model_input(Builder& B, int i, std::vector<int>& chain) {
+    if (!g_opt.fusion || !g_opt.fuse_model_input) return false;
+    GInfo& gi            = B.gi;
+    const ggml_tensor* n = gi.node(i);
+    const ggml_tensor* X = nullptr;   // [.., nb] f32 contiguous: what is tiled over the branches
+    const float* scale   = nullptr;
+    int cur = i, jrep = -1;
+    if (xop(n) == GGML_OP_MUL) {
+        const ggml_tensor *a = n->src[0], *sc = n->src[1];
+        if (!a || !sc || !is_f32(n) || !is_f32(a) || !is_f32(sc) || !contig(n) || !contig(a) || ggml_abi_nelements(sc) != 1 || (n->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
+        for (int d = 0; d < 4; ++d)
+            if (a->ne[d] != n->ne[d]) return false;
+        X     = a;
+        scale = (const float*)sc->data;
+        chain.push_back(i);
+        int j = gi.sole(i);
+        if (j < 0) return false;
+        if (xop(gi.node(j)) == GGML_OP_RESHAPE) {
+            if (gi.node(j)->src[0] != n || (gi.node(j)->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
+            jrep = gi.sole(j);
+            if (jrep < 0 || xop(gi.node(jrep)) != GGML_OP_REPEAT) return false;
+        } else {
+            cur = i;  // K = 1: the CONCAT reads the product itself
+        }
+    } else {
+        jrep = i;
+        X    = n->src[0];
+        if (!X || !is_f32(X) || !contig(X)) return false;
+    }
+    int64_t K = 1;
+    const ggml_tensor* xk = n;  // the CONCAT's first operand
+    if (jrep >= 0) {
+        const ggml_tensor* rep = gi.node(jrep);
+        const ggml_tensor* rs  = rep->src[0];
+        if (!rs || !is_f32(rep) || !contig(rep) || !is_f32(rs) || !contig(rs) || (rep->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
+        if (rs->ne[1] != 1 || rs->ne[3] != 1 || rep->ne[0] != rs->ne[0] || rep->ne[2] != rs->ne[2] || rep->ne[3] != 1 || rep->ne[1] < 2) return false;
+        if (ggml_abi_nelements(rs) != ggml_abi_nelements(X) || rs->data != X->data) {
+            if (xop(n) == GGML_OP_MUL) {
+                if (rs->data != n->data) return false;  // (the RESHAPE of the product)
+            } else {
+                return false;
+            }
+        }
+        K = rep->ne[1];
+        chain.push_back(jrep);
+        const int j2 = gi.sole(jrep);
+        if (j2 < 0 || xop(gi.node(j2)) != GGML_OP_RESHAPE || gi.node(j2)->src[0] != rep || (gi.node(j2)->flags & GGML_TENSOR_FLAG_OUTPUT) || !contig(gi.node(j2))) return false;
+        xk  = gi.node(j2);
+        cur = j2;
+    }
+    const int jc = gi.sole(cur);
+    if (jc < 0) return false;
+    const ggml_tensor* cat = gi.node(jc);
+    if (xop(cat) != GGML_OP_CONCAT || cat->op_params[0] != 2 || cat->src[0] != xk || (cat->flags & GGML_TENSOR_FLAG_OUTPUT) || !is_f32(cat) || !contig(cat)) return false;
+    const ggml_tensor* cs = cat->src[1];
+    if (!cs || !is_f32(cs) || !contig(cs)) return false;
+    const int64_t W = xk->ne[0], H = xk->ne[1], C = xk->ne[2], M = xk->ne[3], cc = cs->ne[2];
+    if (cs->ne[0] != W || cs->ne[1] != H || cs->ne[3] != M || cat->ne[2] != C + cc || cat->ne[3] != M || M % K != 0 || C < 1 || cc < 1) return false;
+    const int64_t nb = M / K;
+    if (jrep >= 0 && (gi.node(jrep)->ne[0] != W * H * C || gi.node(jrep)->ne[2] != nb)) return false;
+    if (ggml_abi_nelements(X) != W * H * C * nb || C > INT32_MAX || cc > INT32_MAX || K > INT32_MAX) return false;
+    // the concat operand: tiled over the model batch by a REPEAT of this chain (dst image m = src row m % R), or a tensor with one row per model image
+    const ggml_tensor* rows_t = cs;
+    const int jcr             = gi.idx(cs);
+    if (jcr > i && !gi.done[jcr] && xop(cs) == GGML_OP_REPEAT && gi.sole(jcr) == jc) {
+        const ggml_tensor* r0 = cs->src[0];
+        if (!r0 || !is_f32(r0) || !contig(r0) || r0->ne[0] != W || r0->ne[1] != H || r0->ne[2] != cc || r0->ne[3] < 1 || M % r0->ne[3] != 0) return false;
+        rows_t = r0;
+        chain.push_back(jcr);
+    }
+    const int64_t R = rows_t->ne[3];
+    chain.push_back(jc);
+    if (!gi.only_noops_between(i, jc, chain)) return false;
+    // the result shares memory with an operand: the plain nodes define what that means, not this kernel
+    const size_t ob = ggml_abi_nbytes(cat);
+    if (overlaps(cat->data, ob, X->data, ggml_abi_nbytes(X)) || overlaps(cat->data, ob, rows_t->data, ggml_abi_nbytes(rows_t)) ||
+        (scale && overlaps(cat->data, ob, scale, sizeof(float))))
+        return false;
+    // the launch runs at the CONCAT's position: nothing in between may have rewritten what it reads
+    if (B.clobbered_between(i, jc, X->data, ggml_abi_nbytes(X), chain) || B.clobbered_between(i, jc, rows_t->data, ggml_abi_nbytes(rows_t), chain) ||
+        (scale && B.clobbered_between(i, jc, scale, sizeof(float), chain)))
+        return false;
+    float* out        = (float*)cat->data;
+    const float* xp   = (const float*)X->data;
+    const float* catp = (const float*)rows_t->data;
+    const int64_t plane = W * H;
+    const int Ci = (int)C, cci = (int)cc, Ki = (int)K;
+    B.emit_at(jc, i, [=](hipStream_t st) { launch_model_input(st, out, xp, scale, catp, plane, Ci, cci, Ki, nb, R); });
+    STAT(fused_model_input)++;
+    return true;
+}
+
+// The three-conditioning CFG combine of the device-resident sampler (csrc/host/engine.cpp; ClassifierFreeGuidance::forward, src/runtime/guidance.cpp:164-168) over the
+// views c, u, iu (rows 0, 1, 2 of every image) of one contiguous e3 [per,3,nb]:
+//   d1 = SUB(u, iu); s1 = MUL(d1, img [1]); a1 = ADD(iu, s1); d2 = SUB(c, u); s2 = MUL(d2, txt [1]); g = ADD(a1, s2)
+// -> ONE launch of k_guidance3 writing g [per,1,nb] (anchored at d1, the first of them in graph order).  The same refusals as plan_model_input.
+bool plan_guidance3(Builder& B, int i, std::vector<int>& chain) {
+    if (!g_opt.fusion || !g_opt.fuse_guidance3) return false;
+    GInfo& gi             = B.gi;
+    const ggml_tensor* d1 = gi.node(i);
+    const ggml_tensor *u = d1->src[0], *iu = d1->src[1];
+    if (!u || !iu || !is_f32(d1) || !contig(d1) || (d1->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
+    const int64_t per = d1->ne[0], nb = d1->ne[2];
+    if (d1->ne[1] != 1 || d1->ne[3] != 1 || per < 1 || nb < 1) return false;
+    auto row_view = [&](const ggml_tensor* v) {  // one of the three rows of every image of a contiguous [per,3,nb] f32 tensor
+        return v && is_f32(v) && v->ne[0] == per && v->ne[1] == 1 && v->ne[2] == nb && v->ne[3] == 1 && v->nb[0] == 4 && (int64_t)v->nb[2] == 3 * per * 4;
+    };
+    if (!row_view(u) || !row_view(iu)) return false;
+    const char* base = (const char*)iu->data - 2 * per * 4;
+    if ((const char*)u->data != base + per * 4) return false;
+    const int j1 = gi.sole(i);
+    if (j1 < 0) return false;
+    const ggml_tensor* s1 = gi.node(j1);
+    if (xop(s1) != GGML_OP_MUL || s1->src[0] != d1 || !s1->src[1] || !is_f32(s1->src[1]) || ggml_abi_nelements(s1->src[1]) != 1 || !is_f32(s1) || !contig(s1)) return false;
+    const int j2 = gi.sole(j1);
+    if (j2 < 0) return false;
+    const ggml_tensor* a1 = gi.node(j2);
+    if (xop(a1) != GGML_OP_ADD || a1->src[1] != s1 || !row_view(a1->src[0]) || a1->src[0]->data != iu->data || !is_f32(a1) || !contig(a1)) return false;
+    const int j3 = gi.sole(j2);
+    if (j3 < 0) return false;
+    const ggml_tensor* g = gi.node(j3);
+    if (xop(g) != GGML_OP_ADD || g->src[0] != a1 || !g->src[1] || !is_f32(g) || !contig(g)) return false;
+    const ggml_tensor* s2 = g->src[1];
+    const int js2         = gi.idx(s2);
+    if (js2 <= i || gi.done[js2] || gi.sole(js2) != j3 || xop(s2) != GGML_OP_MUL || !s2->src[1] || !is_f32(s2->src[1]) || ggml_abi_nelements(s2->src[1]) != 1 || !is_f32(s2) ||
+        !contig(s2))
+        return false;
+    const ggml_tensor* d2 = s2->src[0];
+    const int jd2         = d2 ? gi.idx(d2) : -1;
+    if (jd2 <= i || gi.done[jd2] || gi.sole(jd2) != js2 || xop(d2) != GGML_OP_SUB || !is_f32(d2) || !contig(d2)) return false;
+    if (!row_view(d2->src[0]) || (const char*)d2->src[0]->data != base || !row_view(d2->src[1]) || d2->src[1]->data != u->data) return false;
+    for (const ggml_tensor* t : {s1, a1, g, s2, d2})
+        for (int d = 0; d < 4; ++d)
+            if (t->ne[d] != d1->ne[d]) return false;
+    chain = {i, j1, j2, jd2, js2, j3};
+    if (!gi.only_noops_between(i, j3, chain)) return false;
+    const size_t eb = (size_t)(3 * per * nb * 4), gb = ggml_abi_nbytes(g);
+    const float *txt = (const float*)s2->src[1]->data, *img = (const float*)s1->src[1]->data;
+    if (overlaps(g->data, gb, base, eb) || overlaps(g->data, gb, txt, 4) || overlaps(g->data, gb, img, 4)) return false;
+    float* out      = (float*)g->data;
+    const float* e3 = (const float*)base;
+    B.emit_at(j3, i, [=](hipStream_t st) { launch_guidance3(st, out, e3, txt, img, per, nb); });
+    STAT(fused_guidance3)++;
+    return true;
+}
+
 bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, bool no_redirect = false) {
     Builder B(P, plan, g);
     B.no_redirect = no_redirect;
@@ -3699,7 +3854,15 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                     ok = plan_manual_attention(B, i, s, chain);
                 }
                 break;
-            case GGML_OP_MUL: ok = plan_tile_merge(B, i, chain); break;
+            case GGML_OP_MUL:
+                ok = plan_tile_merge(B, i, chain);
+                if (!ok) {
+                    chain.clear();
+                    ok = plan_model_input(B, i, chain);
+                }
+                break;
+            case GGML_OP_REPEAT: ok = plan_model_input(B, i, chain); break;
+            case GGML_OP_SUB: ok = plan_guidance3(B, i, chain); break;
             case GGML_OP_GROUP_NORM: ok = plan_group_norm(B, i, s, chain); break;
             case GGML_OP_NORM:
             case GGML_OP_RMS_NORM: ok = plan_layer_norm(B, i, s, chain); break;
@@ -4199,6 +4362,8 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     static_assert(offsetof(ggml_backend_mi355x_stats, g16_conv_wmajor) - offsetof(ggml_backend_mi355x_stats, c3w_tw16_bn256) == (CONV_ROUTE_COUNT - 1) * sizeof(int64_t),
                   "ggml_backend_mi355x_stats: one c3w_* / g16_conv_* field per ConvRoute, in its order");
     for (int r = 0; r < CONV_ROUTE_COUNT; ++r) (&o->c3w_tw16_bn256)[r] = conv_route_launches(r);
+    o->ew_model_input_v4 = model_input_route_launches(0);
+    o->ew_model_input_v1 = model_input_route_launches(1);
 }
 
 namespace {
@@ -4236,6 +4401,8 @@ const OptionRow g_option_table[] = {
     OPT(fuse_gn_stats),
     OPT(fuse_gn_epilogue),  // unsplit window convs fill a per-channel GroupNorm side band in their epilogue; the statistics pass becomes k_gn_finalize
     OPT(fuse_tile_merge),  // MUL -> MUL -> { ADD in place | CPY } x k of a VAE tile batch's overlap merge as one gather launch (k_tile_merge)
+    OPT(fuse_model_input),  // [MUL ->] [RESHAPE -> REPEAT -> RESHAPE ->] CONCAT(dim 2) with the [REPEATed] concat latent of an inpaint / pix2pix UNet as one launch (k_model_input)
+    OPT(fuse_guidance3),  // the six nodes of the three-conditioning CFG combine as one launch (k_guidance3)
     OPT(fuse_joint_qkv),
     OPT(fuse_ln_reduce),
     OPT(jit_qimages),

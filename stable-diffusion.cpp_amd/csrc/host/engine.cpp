@@ -484,7 +484,21 @@ struct sdm_ctx_t {
     VaeDecoder vae;
     CompVisDenoiser denoiser;
     DiscreteFlowDenoiser flow_denoiser;
-    int in_channels() const { return is_flux ? 16 : (is_dit ? (int)mmdit.cfg.in_channels : unet.cfg.in_channels); }
+    // the LATENT's channels (noise, x, what the VAE reads and writes): the family's, whatever the variant.  The UNet's first conv reads model_in_channels() =
+    // latent_channels() + concat_channels() (9 on an inpaint UNet, 8 on a pix2pix one)
+    int latent_channels() const { return is_flux ? 16 : (is_dit ? (int)mmdit.cfg.in_channels : unet.cfg.in_channels - concat_channels()); }
+    int model_in_channels() const { return latent_channels() + concat_channels(); }
+    int variant = SDM_UNET_PLAIN;  // sdm_unet_variant_t
+    int concat_channels() const { return variant == SDM_UNET_INPAINT ? 5 : (variant == SDM_UNET_PIX2PIX ? 4 : 0); }
+    // c_concat state (sd_set_concat_condition) and the image guidance scale (sd_set_img_cfg): context state like the VAE tiling parameters
+    struct ConcatCondition {
+        std::vector<float> concat, img_uncond;  // [w, h, cc, n] each; img_uncond is always filled (given or derived)
+        int w = 0, h = 0, cc = 0, n = 0;
+        bool set() const { return !concat.empty(); }
+    };
+    ConcatCondition concat_cond;
+    float img_cfg = INFINITY;      // INFINITY = not set = 1 (resolve_guidance, stable-diffusion.cpp:4237-4240)
+    std::string guidance_status;   // what sd_set_img_cfg had to say (a plain context ignores a scale other than 1, as the reference warns)
     int out_channels() const { return is_flux ? 16 : (is_dit ? (int)mmdit.cfg.out_channels : unet.cfg.out_channels); }
     // Denoiser::get_sigmas (denoiser.hpp:1046-1123): the scheduler sees this family's sigma_min / sigma_max / t_to_sigma.  sched = SCHED_COUNT: the family's own ladder
     std::vector<float> get_sigmas(uint32_t n, int image_seq_len, int sched = SCHED_COUNT) const {
@@ -571,7 +585,20 @@ struct sdm_ctx_t {
             }
         };
         std::unique_ptr<Preview> preview;
+        // c_concat of an inpaint / pix2pix UNet (sd_set_concat_condition), made only for such trajectories: constant over the steps, uploaded once per trajectory
+        struct Concat {
+            ggml_context* cctx        = nullptr;
+            ggml_backend_buffer_t buf = nullptr;
+            ggml_tensor* t            = nullptr;
+            uint64_t serial = 0;  // part of the step graphs' signatures: a cached graph never outlives the tensor it names
+            ~Concat() {
+                if (buf) ggml_backend_buffer_free(buf);
+                if (cctx) ggml_free(cctx);
+            }
+        };
+        std::unique_ptr<Concat> concat;
         ~SamplerState() {
+            concat.reset();
             cache.reset();
             spectrum.reset();
             preview.reset();
@@ -733,7 +760,17 @@ static std::string self_dir() {
     return ".";
 }
 
-sdm_ctx_t* sdm_new_ctx(const sdm_ctx_params_t* params) {
+sdm_ctx_t* sdm_new_ctx(const sdm_ctx_params_t* params) { return sdm_new_ctx_variant(params, SDM_UNET_PLAIN); }
+
+sdm_ctx_t* sdm_new_ctx_variant(const sdm_ctx_params_t* params, int variant) {
+    if (variant < SDM_UNET_PLAIN || variant > SDM_UNET_PIX2PIX) {
+        set_error("sdm_new_ctx_variant: variant must be one of sdm_unet_variant_t");
+        return nullptr;
+    }
+    if (variant != SDM_UNET_PLAIN && params->model != SD_MODEL_SD15 && params->model != SD_MODEL_SDXL && params->model != SD_MODEL_SD15_TINY && params->model != SD_MODEL_SDXL_TINY) {
+        set_error("sdm_new_ctx_variant: inpaint / pix2pix variants exist for the UNet families (SD15, SDXL and their tiny forms) only");
+        return nullptr;
+    }
     const char* dev_name = params->backend ? params->backend : "MI355X0";
     ggml_backend_dev_t dev = ggml_backend_dev_by_name(dev_name);
     if (!dev && !params->backend) {
@@ -757,6 +794,7 @@ sdm_ctx_t* sdm_new_ctx(const sdm_ctx_params_t* params) {
     sdm_ctx_t* ctx = new sdm_ctx_t();
     ctx->params   = *params;
     ctx->backend  = backend;
+    ctx->variant  = variant;
 
     const bool xl   = params->model == SD_MODEL_SDXL || params->model == SD_MODEL_SDXL_TINY;
     const bool tiny = params->model == SD_MODEL_SD15_TINY || params->model == SD_MODEL_SDXL_TINY;
@@ -764,6 +802,7 @@ sdm_ctx_t* sdm_new_ctx(const sdm_ctx_params_t* params) {
     const bool dit      = params->model == SD_MODEL_SD35_LARGE || params->model == SD_MODEL_SD35_TINY || params->model == SD_MODEL_SD35_WIDE2 || params->model == SD_MODEL_SD35_WIDE8 || params->model == SD_MODEL_SD3M_TINY || flux;
     const bool dit_tiny = params->model == SD_MODEL_SD35_TINY || params->model == SD_MODEL_FLUX_TINY || params->model == SD_MODEL_SD3M_TINY;
     UNetConfig ucfg = tiny ? UNetConfig::tiny(xl) : (xl ? UNetConfig::sdxl_base() : UNetConfig::sd15());
+    ucfg.in_channels += ctx->concat_channels();  // input_blocks.0.0 alone is wider (model_loader.cpp: ne[2] == 9 inpaint, 8 pix2pix)
     VaeConfig vcfg  = (tiny || dit_tiny) ? VaeConfig::tiny() : (xl ? VaeConfig::sdxl() : VaeConfig::sd15());
     if (tiny && xl) vcfg.scale_factor = 0.13025f;
     if (dit) {  // SD3 VAE: 16 latent channels, no post_quant_conv (auto_encoder_kl.hpp:548-556, 682-684)
@@ -1329,7 +1368,8 @@ static bool prepare_side_inputs(sdm_ctx_t* ctx, int w, int h, int n, int64_t n_t
 }
 // the denoiser network on an existing latent tensor tx [w,h,c,n]: declares the remaining graph inputs and calls the family's forward
 static ggml_tensor* build_model_call(sdm_ctx_t* ctx, GraphCtx& g, std::vector<HostInput>& in, ggml_tensor* tx, int n, const float* timesteps, const float* context,
-                                     int64_t ctx_dim, int64_t n_tokens, int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const ModelSideInputs& si) {
+                                     int64_t ctx_dim, int64_t n_tokens, int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const ModelSideInputs& si,
+                                     ggml_tensor* c_concat = nullptr) {
     g.flash_attn    = ctx->params.diffusion_flash_attn;
     g.conv_direct   = ctx->params.diffusion_conv_direct;
     ggml_tensor* tt = ggml_new_tensor_1d(g.ctx, GGML_TYPE_F32, n);
@@ -1355,13 +1395,26 @@ static ggml_tensor* build_model_call(sdm_ctx_t* ctx, GraphCtx& g, std::vector<Ho
         in.push_back({tp, si.pe().data(), ggml_nbytes(tp)});
         return ctx->flux.forward(g, tx, tt, tc, ty, tg, tp);
     }
-    return ctx->is_dit ? ctx->mmdit.forward(g, tx, tt, tc, ty) : ctx->unet.forward(g, tx, tt, tc, ty);
+    return ctx->is_dit ? ctx->mmdit.forward(g, tx, tt, tc, ty) : ctx->unet.forward(g, tx, tt, tc, ty, c_concat);
 }
 
 // skip: the joint blocks a skip-layer-guidance forward leaves out (MMDiT only; NULL / empty = the whole model)
 static bool unet_forward_skip(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim, int64_t n_tokens,
-                              int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, float* out, const std::vector<int>* skip) {
+                              int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, float* out, const std::vector<int>* skip, const float* c_concat = nullptr,
+                              int cc = 0, int concat_n = 0) {
     Runner& r = ctx->unet_runner;
+    if (ctx->variant != SDM_UNET_PLAIN && !c_concat) {  // never a silent zero-fill of the extra input channels
+        set_error("model needs c_concat (an inpaint / pix2pix UNet: sd_unet_forward_concat)");
+        return false;
+    }
+    if (c_concat && (cc != ctx->concat_channels() || cc < 1)) {
+        set_error("c_concat has " + std::to_string(cc) + " channels, the model takes " + std::to_string(ctx->concat_channels()));
+        return false;
+    }
+    if (c_concat && (concat_n < 1 || n % concat_n != 0)) {  // (a divisor in between is tiled like 1 is, image i reads row i % concat_n: the host loop's fused branches)
+        set_error("c_concat batch must be 1 or the batch of x");
+        return false;
+    }
     ModelSideInputs si;
     if (!prepare_side_inputs(ctx, w, h, n, n_tokens, y != nullptr, si)) return false;
     if (skip && skip->empty()) skip = nullptr;
@@ -1369,8 +1422,14 @@ static bool unet_forward_skip(sdm_ctx_t* ctx, const float* x, int w, int h, int 
         ggml_tensor* tx = ggml_new_tensor_4d(g.ctx, GGML_TYPE_F32, w, h, c, n);
         ggml_set_input(tx);
         in.push_back({tx, x, ggml_nbytes(tx)});
+        ggml_tensor* tcc = nullptr;
+        if (c_concat) {
+            tcc = ggml_new_tensor_4d(g.ctx, GGML_TYPE_F32, w, h, cc, concat_n);
+            ggml_set_input(tcc);
+            in.push_back({tcc, c_concat, ggml_nbytes(tcc)});
+        }
         g.skip_layers = skip;
-        return build_model_call(ctx, g, in, tx, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, si);
+        return build_model_call(ctx, g, in, tx, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, si, tcc);
     };
     char sig[256];
     int so = snprintf(sig, sizeof(sig), "fwd %d %d %d %d %lld %lld %lld %lld %lld %d", w, h, c, n, (long long)ctx_dim, (long long)n_tokens, (long long)ctx_n,
@@ -1378,7 +1437,11 @@ static bool unet_forward_skip(sdm_ctx_t* ctx, const float* x, int w, int h, int 
     if (skip)
         for (int l : *skip)
             if (so < (int)sizeof(sig) - 8) so += snprintf(sig + so, sizeof(sig) - so, " s%d", l);
-    std::vector<const void*> ptrs{x, timesteps, context};
+    if (c_concat && so < (int)sizeof(sig) - 24) so += snprintf(sig + so, sizeof(sig) - so, " cc%d n%d", cc, concat_n);
+    std::vector<const void*> ptrs{x};
+    if (c_concat) ptrs.push_back(c_concat);  // (the order the builder declares its inputs in)
+    ptrs.push_back(timesteps);
+    ptrs.push_back(context);
     if (y) ptrs.push_back(y);
     if (ctx->is_flux) {
         ptrs.push_back(si.guidance.data());
@@ -1394,6 +1457,21 @@ bool sd_unet_forward(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n,
                      int64_t ctx_dim, int64_t n_tokens, int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, float* out) {
     return unet_forward_skip(ctx, x, w, h, c, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, out, nullptr);
 }
+// the forward of an inpaint / pix2pix UNet: c_concat [w,h,cc,concat_n] is appended to x along the channels in front of input_blocks.0.0 (unet.hpp:554-559)
+bool sd_unet_forward_concat(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim, int64_t n_tokens,
+                            int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const float* c_concat, int cc, int concat_n, float* out) {
+    if (!c_concat) {
+        set_error("sd_unet_forward_concat: c_concat is NULL");
+        return false;
+    }
+    if (ctx->variant == SDM_UNET_PLAIN) {
+        set_error("sd_unet_forward_concat: the model takes no c_concat (a plain context)");
+        return false;
+    }
+    return unet_forward_skip(ctx, x, w, h, c, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, out, nullptr, c_concat, cc, concat_n);
+}
+int sd_unet_variant(sdm_ctx_t* ctx) { return ctx->variant; }
+int sd_concat_channels(sdm_ctx_t* ctx) { return ctx->concat_channels(); }
 
 // the same forward without the listed MMDiT joint blocks (MMDiT::forward's skip_layers, mmdit.hpp:854-866): what skip-layer guidance evaluates
 bool sd_unet_forward_skip_layers(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim, int64_t n_tokens,
@@ -1734,6 +1812,12 @@ bool sd_vae_encode(sdm_ctx_t* ctx, const float* rgb, int w, int h, int n, uint64
     } else if (!r.compute(build, moments.data(), moments.size() * sizeof(float), sig, {x.data()}))
         return false;
     if (moments_out) memcpy(moments_out, moments.data(), moments.size() * sizeof(float));
+    if (ctx->variant == SDM_UNET_PIX2PIX && (ctx->params.model == SD_MODEL_SD15 || ctx->params.model == SD_MODEL_SD15_TINY)) {
+        // VERSION_SD1_PIX2PIX: the latent is the mean of the moments (vae_output_to_latents, auto_encoder_kl.hpp:764-765), not sampled, and it is NOT scaled to the
+        // diffusion range (encode_first_stage, stable-diffusion.cpp:3056-3058).  SDXL pix2pix takes the ordinary path below
+        for (int b = 0; b < n; ++b) memcpy(out_latents + (size_t)b * per, &moments[(size_t)b * 2 * per], per * sizeof(float));
+        return true;
+    }
     PhiloxRNG rng(seed);
     const std::vector<float> noise = rng.randn((uint32_t)(per * n));  // randn_like(mean): one draw over the whole [lw, lh, zc, n] tensor
     const float sf = ctx->vae.cfg.scale_factor, sh = ctx->vae.cfg.shift_factor;
@@ -2000,6 +2084,36 @@ static void step_scalings(const sdm_ctx_t* ctx, const sdm_sample_params_t& sp, f
         c_out  = s_out;
     }
 }
+// Which model evaluations a denoise call makes — resolve_guidance, stable-diffusion.cpp:4237-4255: img_cfg unset = 1; a model without image conditioning ignores it;
+// the uncond branch runs iff img_cfg != txt_cfg (with img_cfg 1: txt_cfg != 1), the img_uncond branch iff img_cfg != 1.  Both need the uncond conditioning (its text
+// is the third condition's text too)
+struct GuidancePlan {
+    float img_cfg       = 1.0f;
+    bool use_uncond     = false;
+    bool use_img_uncond = false;
+    int branches() const { return 1 + (int)use_uncond + (int)use_img_uncond; }
+};
+static GuidancePlan resolve_guidance_plan(const sdm_ctx_t* ctx, const sdm_img_gen_params_t* p) {
+    GuidancePlan gp;
+    gp.img_cfg = (std::isfinite(ctx->img_cfg) && ctx->variant != SDM_UNET_PLAIN) ? ctx->img_cfg : 1.0f;
+    const bool has_uncond = p->uncond.c_crossattn != nullptr;
+    gp.use_uncond         = gp.img_cfg != p->sample_params.txt_cfg && has_uncond;
+    gp.use_img_uncond     = gp.img_cfg != 1.0f && has_uncond;
+    return gp;
+}
+// the concat condition of the device group (b0, nb): shared by the batch (n = 1, the reference's case) or the group's slice of a per-image one
+static void group_concat(const sdm_ctx_t* ctx, int b0, int nb, const float*& concat, const float*& img_concat, int& cc, int& concat_n) {
+    const sdm_ctx_t::ConcatCondition& s = ctx->concat_cond;
+    concat = img_concat = nullptr;
+    cc = concat_n = 0;
+    if (!s.set() || ctx->variant == SDM_UNET_PLAIN) return;
+    const size_t one = (size_t)s.w * s.h * s.cc;
+    const size_t off = s.n == 1 ? 0 : one * (size_t)b0;
+    concat     = s.concat.data() + off;
+    img_concat = s.img_uncond.data() + off;
+    cc         = s.cc;
+    concat_n   = s.n == 1 ? 1 : nb;
+}
 // One denoiser call of the host loop — the reference's `denoise` lambda (stable-diffusion.cpp:2620-2926) on nb images: scalings and timestep of sigma, x * c_in, the model
 // forward(s) (the cond / uncond pair in ONE graph when the conditionings allow it), classifier-free guidance, pred * c_out + x * c_skip.
 struct HostDenoise {
@@ -2018,9 +2132,20 @@ struct HostDenoise {
     StepCacheRuntime* sc = nullptr;
     HostStepCacheStore sc_store;
     std::vector<float> spectrum_ring;  // Spectrum's H_buf: K slots of the group's denoised tensor (SpectrumState keeps which slot is which)
-    HostDenoise(sdm_ctx_t* ctx_, const sdm_img_gen_params_t* p_, int W_, int H_, int C_, int nb_)
-        : ctx(ctx_), p(p_), W(W_), H(H_), C(C_), nb(nb_), per((size_t)W_ * H_ * C_), use_cfg(p_->sample_params.txt_cfg != 1.0f && p_->uncond.c_crossattn != nullptr),
-          noised(per * nb_), cond_out(per * nb_), uncond_out(per * nb_), ts(nb_) {}
+    // c_concat and image guidance (sd_set_concat_condition / sd_set_img_cfg; inpaint and pix2pix UNets): cond and uncond both see `concat`, the third condition is
+    // uncond's text with `img_concat` (stable-diffusion.cpp:5236-5237, 5265-5266, 5273).  Branches as resolve_guidance (:4249-4255) sets them; with no concat
+    // condition and img_cfg 1 everything below is exactly the two-branch loop
+    GuidancePlan gp;
+    const float *concat = nullptr, *img_concat = nullptr;  // this group's [W, H, cc, concat_n]
+    int cc = 0, concat_n = 0;
+    std::vector<float> img_uncond_out, cc2;
+    HostDenoise(sdm_ctx_t* ctx_, const sdm_img_gen_params_t* p_, int W_, int H_, int C_, int nb_, int b0_ = 0)
+        : ctx(ctx_), p(p_), W(W_), H(H_), C(C_), nb(nb_), per((size_t)W_ * H_ * C_), use_cfg(false), noised(per * nb_), cond_out(per * nb_), uncond_out(per * nb_), ts(nb_) {
+        gp      = resolve_guidance_plan(ctx, p);
+        use_cfg = gp.use_uncond;
+        group_concat(ctx, b0_, nb_, concat, img_concat, cc, concat_n);
+        if (gp.use_img_uncond) img_uncond_out.resize(per * nb_);
+    }
     // denoised_uncond (the CFG++ methods): GuiderOutput::pred_uncond = base_uncond * c_out + x * c_skip with the unconditional forward — or the conditional one when there is
     // no guidance pair (stable-diffusion.cpp:2877-2884)
     // step: the sampler's step index of this call (sample_k_diffusion hands the denoise callback i + 1, negated for the first stage of the two-stage methods): what
@@ -2045,12 +2170,21 @@ struct HostDenoise {
         if (!preview(step, true, noised.data())) return false;  // stable-diffusion.cpp:2681-2683
         const bool cached = sc && sc->armed();
         if (cached) sc->begin_call(step, sigma);  // SampleStepCacheDispatcher step_cache(cache_runtime, step, sigma), stable-diffusion.cpp:2688
-        auto run = [&](const sd_condition_t& cd, float* dst) {
+        auto run = [&](const sd_condition_t& cd, float* dst, const float* cat = nullptr) {
             const int cond_id = &cd == &p->uncond ? 1 : 0;
             if (cached && sc_store.before_condition(*sc, cond_id, noised.data(), dst, n)) return true;
-            if (!sd_unet_forward(ctx, noised.data(), W, H, C, nb, ts.data(), cd.c_crossattn, cd.ctx_dim, cd.n_tokens, 1, cd.c_vector, cd.vector_dim, 1, dst)) return false;
+            if (cat ? !sd_unet_forward_concat(ctx, noised.data(), W, H, C, nb, ts.data(), cd.c_crossattn, cd.ctx_dim, cd.n_tokens, 1, cd.c_vector, cd.vector_dim, 1, cat, cc, concat_n, dst)
+                    : !sd_unet_forward(ctx, noised.data(), W, H, C, nb, ts.data(), cd.c_crossattn, cd.ctx_dim, cd.n_tokens, 1, cd.c_vector, cd.vector_dim, 1, dst))
+                return false;
             if (cached) sc_store.after_condition(*sc, cond_id, noised.data(), dst, n);
             return true;
+        };
+        // the combine of the branches that ran (ClassifierFreeGuidance::forward, guidance.cpp:162-176; sd_cfg_combine3's arithmetic)
+        auto guide3 = [&](float* dst) {
+            if (gp.use_uncond)
+                for (size_t k = 0; k < n; ++k) dst[k] = cfg_guided3(cond_out[k], uncond_out[k], img_uncond_out[k], sp.txt_cfg, gp.img_cfg);
+            else
+                for (size_t k = 0; k < n; ++k) dst[k] = cfg_guided(cond_out[k], img_uncond_out[k], sp.txt_cfg);
         };
         // the primary guidance of the (cond, uncond) pair: classifier-free (guidance.cpp:171) or, with any apg_* parameter set, adaptive projected guidance per image
         // (guidance.cpp:209-294; the momentum buffer lives as long as the trajectory, like the reference's guider object)
@@ -2063,7 +2197,70 @@ struct HostDenoise {
                 for (size_t k = 0; k < n; ++k) dst[k] = cfg_guided(cond_out[k], uncond_out[k], sp.txt_cfg);
             }
         };
-        if (use_cfg && p->fuse_cfg_pair && p->cond.ctx_dim == p->uncond.ctx_dim && p->cond.n_tokens == p->uncond.n_tokens) {
+        const int K = gp.branches();
+        if (concat && K >= 2 && p->fuse_cfg_pair && p->cond.ctx_dim == p->uncond.ctx_dim && p->cond.n_tokens == p->uncond.n_tokens) {
+            // one graph for the K = 2 or 3 evaluations of every image, interleaved (b cond, b uncond, b img_uncond): context / y have batch K and are tiled by the
+            // graph's ggml_repeat; the concat has batch K (shared by the images: tiled the same way) or K * nb (per image)
+            const size_t cn  = (size_t)p->cond.ctx_dim * p->cond.n_tokens;
+            const bool has_y = p->cond.c_vector && p->uncond.c_vector;
+            const size_t ccper = (size_t)W * H * cc;
+            const int img_seat = gp.use_img_uncond ? K - 1 : -1;
+            if (x2.empty()) {
+                x2.resize((size_t)K * per * nb);
+                o2.resize((size_t)K * per * nb);
+                t2.resize((size_t)K * nb);
+                c2.resize((size_t)K * cn);
+                if (has_y) y2.resize((size_t)K * p->cond.vector_dim);
+                for (int j = 0; j < K; ++j) {
+                    const sd_condition_t& cd = j == 0 ? p->cond : p->uncond;
+                    memcpy(&c2[(size_t)j * cn], cd.c_crossattn, cn * sizeof(float));
+                    if (has_y) memcpy(&y2[(size_t)j * p->cond.vector_dim], cd.c_vector, p->cond.vector_dim * sizeof(float));
+                }
+                const int rows = concat_n == 1 ? 1 : nb;
+                cc2.resize((size_t)K * rows * ccper);
+                for (int b = 0; b < rows; ++b)
+                    for (int j = 0; j < K; ++j)
+                        memcpy(&cc2[((size_t)b * K + j) * ccper], (j == img_seat ? img_concat : concat) + (size_t)b * ccper, ccper * sizeof(float));
+            }
+            std::fill(t2.begin(), t2.end(), t);
+            // (a cache is armed with the cond / uncond pair only: the third branch is refused together with it)
+            if (cached && sc_store.before_condition(*sc, 0, noised.data(), cond_out.data(), n)) {
+                if (!sc_store.before_condition(*sc, 1, noised.data(), uncond_out.data(), n)) {
+                    set_error("step cache: no stored difference for the unconditional branch of a skipped step");
+                    return false;
+                }
+            } else {
+                for (int b = 0; b < nb; ++b)
+                    for (int j = 0; j < K; ++j) memcpy(&x2[((size_t)K * b + j) * per], &noised[(size_t)b * per], per * sizeof(float));
+                if (!sd_unet_forward_concat(ctx, x2.data(), W, H, C, K * nb, t2.data(), c2.data(), p->cond.ctx_dim, p->cond.n_tokens, K, has_y ? y2.data() : nullptr,
+                                            p->cond.vector_dim, K, cc2.data(), cc, concat_n == 1 ? K : K * nb, o2.data()))
+                    return false;
+                for (int b = 0; b < nb; ++b) {
+                    int j = 0;
+                    memcpy(&cond_out[(size_t)b * per], &o2[((size_t)K * b + j++) * per], per * sizeof(float));
+                    if (gp.use_uncond) memcpy(&uncond_out[(size_t)b * per], &o2[((size_t)K * b + j++) * per], per * sizeof(float));
+                    if (gp.use_img_uncond) memcpy(&img_uncond_out[(size_t)b * per], &o2[((size_t)K * b + j++) * per], per * sizeof(float));
+                }
+                if (cached) {
+                    sc_store.after_condition(*sc, 0, noised.data(), cond_out.data(), n);
+                    sc_store.after_condition(*sc, 1, noised.data(), uncond_out.data(), n);
+                }
+            }
+            if (gp.use_img_uncond)
+                guide3(denoised);
+            else
+                guide(denoised);
+        } else if (concat) {
+            if (!run(p->cond, cond_out.data(), concat)) return false;
+            if (gp.use_uncond && !run(p->uncond, uncond_out.data(), concat)) return false;
+            if (gp.use_img_uncond && !run(p->uncond, img_uncond_out.data(), img_concat)) return false;
+            if (gp.use_img_uncond)
+                guide3(denoised);
+            else if (gp.use_uncond)
+                guide(denoised);
+            else
+                for (size_t k = 0; k < n; ++k) denoised[k] = cond_out[k];
+        } else if (use_cfg && p->fuse_cfg_pair && p->cond.ctx_dim == p->uncond.ctx_dim && p->cond.n_tokens == p->uncond.n_tokens) {
             // one graph for the cond/uncond pair: images interleaved (b cond, b uncond, ...); context/y have batch 2 and are
             // tiled over the 2*nb images by the graph's ggml_repeat (dst[i] = src[i % 2])
             const size_t cn  = (size_t)p->cond.ctx_dim * p->cond.n_tokens;
@@ -2136,7 +2333,8 @@ struct HostDenoise {
         }
         for (size_t k = 0; k < n; ++k) denoised[k] = denoised[k] * c_out + x[k] * c_skip;  // stable-diffusion.cpp:2876
         if (denoised_uncond) {
-            const float* base = use_cfg ? uncond_out.data() : cond_out.data();
+            // base_uncond: img_uncond first, then uncond, then cond (stable-diffusion.cpp:2880-2882)
+            const float* base = (concat && gp.use_img_uncond) ? img_uncond_out.data() : (use_cfg ? uncond_out.data() : cond_out.data());
             for (size_t k = 0; k < n; ++k) denoised_uncond[k] = base[k] * c_out + x[k] * c_skip;
         }
         if (spectrum) {  // SpectrumState::update in front of the mask blend (stable-diffusion.cpp:2885-2887)
@@ -2198,7 +2396,7 @@ static inline void noise_scaling(float* x, const float* noise, const float* late
     }
 }
 static bool sample_group(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, int nb, float* out) {
-    const int W = p->width / 8, H = p->height / 8, C = ctx->in_channels();
+    const int W = p->width / 8, H = p->height / 8, C = ctx->latent_channels();
     const size_t per = (size_t)W * H * C;
     const sdm_sample_params_t& sp = p->sample_params;
     int method, scheduler;
@@ -2221,7 +2419,7 @@ static bool sample_group(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, 
             noise_scaling(&x[b * per], noise.data(), p->init_latent, per, sigmas[0], ctx->is_dit);
         }
     }, 2);
-    HostDenoise denoise(ctx, p, W, H, C, nb);
+    HostDenoise denoise(ctx, p, W, H, C, nb, b0);
     denoise.n_sigmas = (int)sigmas.size();
     denoise.b0       = b0;
     ctx->step_cache_begin_trajectory(sigmas, method);  // init_sample_cache_runtime per sample() call, stable-diffusion.cpp:2578
@@ -2417,11 +2615,12 @@ struct StepCacheDevice {
 // only — and then the PREDICTED-STEP graph, the tail of the step graph from `denoised` on.  Calls from the stop call on feed nothing any more: plain step graph.
 static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, int b0, int nb, float* out, bool* handled) {
     *handled = false;
-    const int W = p->width / 8, H = p->height / 8, C = ctx->in_channels();
+    const int W = p->width / 8, H = p->height / 8, C = ctx->latent_channels();
     const sdm_sample_params_t& sp = p->sample_params;
-    const bool use_cfg = sp.txt_cfg != 1.0f && p->uncond.c_crossattn != nullptr;
+    const GuidancePlan gp = resolve_guidance_plan(ctx, p);  // (a plain context: use_uncond = txt_cfg != 1 with an uncond conditioning, no third branch)
+    const bool use_cfg = gp.use_uncond;
     const bool has_y   = p->cond.c_vector != nullptr;
-    if (use_cfg && (p->cond.ctx_dim != p->uncond.ctx_dim || p->cond.n_tokens != p->uncond.n_tokens || has_y != (p->uncond.c_vector != nullptr))) return true;
+    if (gp.branches() > 1 && (p->cond.ctx_dim != p->uncond.ctx_dim || p->cond.n_tokens != p->uncond.n_tokens || has_y != (p->uncond.c_vector != nullptr))) return true;
     if (ctx->out_channels() != C) return true;  // learned-sigma heads are not sampled this way
     int method, scheduler;
     float eta;
@@ -2484,18 +2683,56 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
     // same latents (same Philox streams), so nothing else is exchanged.
     const bool pair = ctx->pair_fn != nullptr && use_cfg;
     // conditioning of the (cond, uncond) pair, tiled over the images by the model graph's own ggml_repeat
-    const bool both   = use_cfg && !pair;
-    const int n_model = both ? 2 * nb : nb;
-    const int ctx_n   = both ? 2 : 1;
+    // K evaluations per image in the step graph: cond [, uncond] [, img_uncond — uncond's text with the img_uncond concat]; two of them combine as
+    // second + s * (cond - second) whichever the second is (guidance.cpp:171, 175), three as the three-term form (:166-168)
+    const int K       = pair ? 1 : gp.branches();
+    const bool both   = K == 2;
+    const bool three  = K == 3;
+    const int n_model = K * nb;
+    const int ctx_n   = K;
     const size_t cn   = (size_t)p->cond.ctx_dim * p->cond.n_tokens;
     const sd_condition_t& first = (pair && ctx->pair_branch == 1) ? p->uncond : p->cond;
     std::vector<float> c2(cn * ctx_n), y2;
     memcpy(&c2[0], first.c_crossattn, cn * sizeof(float));
-    if (both) memcpy(&c2[cn], p->uncond.c_crossattn, cn * sizeof(float));
+    for (int j = 1; j < K; ++j) memcpy(&c2[cn * j], p->uncond.c_crossattn, cn * sizeof(float));
     if (has_y) {
         y2.resize((size_t)p->cond.vector_dim * ctx_n);
         memcpy(&y2[0], first.c_vector, p->cond.vector_dim * sizeof(float));
-        if (both) memcpy(&y2[p->cond.vector_dim], p->uncond.c_vector, p->cond.vector_dim * sizeof(float));
+        for (int j = 1; j < K; ++j) memcpy(&y2[(size_t)p->cond.vector_dim * j], p->uncond.c_vector, p->cond.vector_dim * sizeof(float));
+    }
+    // c_concat (inpaint / pix2pix UNets): resident for the trajectory, uploaded once — [W,H,cc,K] when the batch shares it (row j is branch j's: `concat` for cond and
+    // uncond, `img_uncond_concat` on the img_uncond seat; the model graph's REPEAT tiles it over the images) or [W,H,cc,K*nb] per image, in the order of the model batch
+    const float *cat_host = nullptr, *cat_img_host = nullptr;
+    int cat_cc = 0, cat_n = 0;
+    group_concat(ctx, b0, nb, cat_host, cat_img_host, cat_cc, cat_n);
+    std::vector<float> cat_stage;
+    ggml_tensor* cat_dev = nullptr;
+    if (cat_host) {
+        const int rows     = cat_n == 1 ? 1 : nb;
+        const size_t ccper = (size_t)W * H * cat_cc;
+        const int img_seat = (gp.use_img_uncond && !pair) ? K - 1 : -1;
+        if (!st.concat || st.concat->t->ne[2] != cat_cc || st.concat->t->ne[3] != (int64_t)K * rows) {
+            st.concat.reset(new sdm_ctx_t::SamplerState::Concat());
+            auto& sc_ = *st.concat;
+            ggml_init_params ip{0, nullptr, true};
+            sc_.cctx = ggml_init(ip);
+            sc_.t    = ggml_new_tensor_4d(sc_.cctx, GGML_TYPE_F32, W, H, cat_cc, (int64_t)K * rows);
+            ggml_set_name(sc_.t, "sampler.concat");
+            sc_.buf = ggml_backend_alloc_ctx_tensors(sc_.cctx, ctx->backend);
+            if (!sc_.buf) {
+                st.concat.reset();
+                set_error("sampler concat state allocation failed");
+                return false;
+            }
+            static std::atomic<uint64_t> g_concat_serial{0};
+            sc_.serial = ++g_concat_serial;
+        }
+        cat_stage.resize((size_t)K * rows * ccper);
+        for (int b = 0; b < rows; ++b)
+            for (int j = 0; j < K; ++j)
+                memcpy(&cat_stage[((size_t)b * K + j) * ccper], (j == img_seat ? cat_img_host : cat_host) + (size_t)b * ccper, ccper * sizeof(float));
+        cat_dev = st.concat->t;
+        ggml_backend_tensor_set_async(ctx->backend, cat_dev, cat_stage.data(), 0, cat_stage.size() * sizeof(float));
     }
     void* pair_stream = nullptr;
     if (pair) {
@@ -2608,9 +2845,12 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
     if (!prepare_side_inputs(ctx, W, H, n_model, p->cond.n_tokens, has_y, si)) return false;
     std::vector<float> ts(n_model);
     Runner& r = ctx->unet_runner;
-    char step_sig[200];  // every step of the trajectory replays ONE cached graph: only the 8 scalars, the timesteps and the conditioning are re-uploaded
-    snprintf(step_sig, sizeof(step_sig), "step %d %d %d %d cfg%d ea%d %lld %lld y%lld %p pair%d", W, H, C, nb, (int)use_cfg, (int)euler_a + 2 * (int)flow, (long long)p->cond.ctx_dim,
-             (long long)p->cond.n_tokens, (long long)(has_y ? p->cond.vector_dim : -1), (void*)st.x, (int)pair);
+    char step_sig[280];  // every step of the trajectory replays ONE cached graph: only the 8 scalars, the timesteps and the conditioning are re-uploaded
+    int sig_n = snprintf(step_sig, sizeof(step_sig), "step %d %d %d %d cfg%d ea%d %lld %lld y%lld %p pair%d", W, H, C, nb, (int)use_cfg, (int)euler_a + 2 * (int)flow,
+                         (long long)p->cond.ctx_dim, (long long)p->cond.n_tokens, (long long)(has_y ? p->cond.vector_dim : -1), (void*)st.x, (int)pair);
+    if (cat_dev)  // graphs with a concat input: its width, the branches per image, whether the last seat is img_uncond's, and the resident tensor they name
+        snprintf(step_sig + sig_n, sizeof(step_sig) - (size_t)sig_n, " cc%d K%d iu%d pi%d concat%llu", cat_cc, K, (int)gp.use_img_uncond, (int)(cat_n != 1),
+                 (unsigned long long)st.concat->serial);
     const std::string update_sig = std::string("update ") + step_sig;
     const std::string cache_tag  = cc ? " cache" + std::to_string(cc->serial) : std::string();
     const std::string record_sig = std::string("record ") + step_sig + cache_tag;  // the recording variant and the skip-step graph: plans of their own
@@ -2627,7 +2867,9 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
         std::fill(ts.begin(), ts.end(), t_model);
         // scalars of this step: {c_in, cfg scale, c_out, c_skip, a, b, noise gain, alpha}; Euler-A: x' = (a*x + b*denoised) [* alpha on flow models] + gain*noise;
         // Euler: x' = x + ((x - denoised) / a) * b with a = sigma, b = sigma_to - sigma
-        float sc[8] = {c_in, pair ? (ctx->pair_branch == 0 ? sp.txt_cfg : 1.0f - sp.txt_cfg) : sp.txt_cfg, c_out, c_skip, 0.f, 0.f, 0.f, 1.f};
+        // (a ninth scalar, img_cfg, exists only on graphs with a third branch: every other graph keeps its 8 scalars and its signature)
+        float sc[9] = {c_in, pair ? (ctx->pair_branch == 0 ? sp.txt_cfg : 1.0f - sp.txt_cfg) : sp.txt_cfg, c_out, c_skip, 0.f, 0.f, 0.f, 1.f, gp.img_cfg};
+        const int n_sc = three ? 9 : 8;
         bool fresh_noise = false;
         if (euler_a) {
             if (sigma_to == 0.f) {
@@ -2692,9 +2934,9 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
         auto build_variant = [&](int variant) {
           return [&, variant](GraphCtx& g, std::vector<HostInput>& in) {
             ggml_context* c  = g.ctx;
-            ggml_tensor* tsc = ggml_new_tensor_1d(c, GGML_TYPE_F32, 8);
+            ggml_tensor* tsc = ggml_new_tensor_1d(c, GGML_TYPE_F32, n_sc);
             ggml_set_input(tsc);
-            in.push_back({tsc, sc, sizeof(sc)});
+            in.push_back({tsc, sc, (size_t)n_sc * sizeof(float)});
             auto S = [&](int k) { return ggml_view_1d(c, tsc, 1, (size_t)k * sizeof(float)); };
             ggml_tensor* xs     = st.x;
             ggml_tensor* noised = variant == 4 ? nullptr : ggml_mul(c, xs, S(0));
@@ -2711,16 +2953,18 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
                 }
             } else {
                 ggml_tensor* xin = noised;
-                if (both) {  // every image twice, (cond, uncond) adjacent: [per, 1, nb] -> [per, 2, nb]
+                if (K > 1) {  // every image K times, its branches adjacent: [per, 1, nb] -> [per, K, nb]
                     ggml_tensor* flat = ggml_reshape_3d(c, noised, (int64_t)per, 1, nb);
-                    ggml_tensor* rep  = ggml_repeat(c, flat, ggml_new_tensor_3d(c, GGML_TYPE_F32, (int64_t)per, 2, nb));
-                    xin               = ggml_reshape_4d(c, rep, W, H, C, 2 * nb);
+                    ggml_tensor* rep  = ggml_repeat(c, flat, ggml_new_tensor_3d(c, GGML_TYPE_F32, (int64_t)per, K, nb));
+                    xin               = ggml_reshape_4d(c, rep, W, H, C, K * nb);
                 }
+                // (cat_dev: the model's own graph appends it — [REPEAT over the images,] CONCAT along the channels, unet.hpp:554-559; with the chain above that is
+                // the pattern the MI355X backend runs as one launch of k_model_input)
                 eps = build_model_call(ctx, g, in, xin, n_model, ts.data(), c2.data(), p->cond.ctx_dim, p->cond.n_tokens, ctx_n,
-                                       has_y ? y2.data() : nullptr, p->cond.vector_dim, ctx_n, si);
+                                       has_y ? y2.data() : nullptr, p->cond.vector_dim, ctx_n, si, cat_dev);
                 if (pair) return ggml_cpy(c, ggml_mul(c, eps, S(1)), st.eps);  // weight * eps of this rank's branch; the update follows the exchange
-                if (both) {
-                    e3 = ggml_reshape_3d(c, ggml_cont(c, eps), (int64_t)per, 2, nb);
+                if (K > 1) {
+                    e3 = ggml_reshape_3d(c, ggml_cont(c, eps), (int64_t)per, K, nb);
                     if (variant == 1) e3 = ggml_cpy(c, e3, cc->out);
                 } else if (variant == 1) {
                     eps = ggml_cpy(c, eps, cc->out);
@@ -2732,6 +2976,13 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
                 ggml_tensor* eu = ggml_view_3d(c, e3, (int64_t)per, 1, nb, e3->nb[1], e3->nb[2], e3->nb[1]);
                 ggml_tensor* d  = ggml_mul(c, ggml_sub(c, ec, eu), S(1));
                 guided          = ggml_reshape_4d(c, ggml_add(c, eu, d), W, H, C, nb);
+            } else if (three && variant != 4) {  // iu + img * (u - iu) + txt * (c - u), guidance.cpp:166-168: six nodes, left to right (one launch of k_guidance3 on the MI355X backend)
+                ggml_tensor* ec = ggml_view_3d(c, e3, (int64_t)per, 1, nb, e3->nb[1], e3->nb[2], 0);
+                ggml_tensor* eu = ggml_view_3d(c, e3, (int64_t)per, 1, nb, e3->nb[1], e3->nb[2], e3->nb[1]);
+                ggml_tensor* ei = ggml_view_3d(c, e3, (int64_t)per, 1, nb, e3->nb[1], e3->nb[2], 2 * e3->nb[1]);
+                ggml_tensor* a1 = ggml_add(c, ei, ggml_mul(c, ggml_sub(c, eu, ei), S(8)));
+                ggml_tensor* s2 = ggml_mul(c, ggml_sub(c, ec, eu), S(1));
+                guided          = ggml_reshape_4d(c, ggml_add(c, a1, s2), W, H, C, nb);
             }
             ggml_tensor* den = variant == 4 ? ss->denoised : ggml_add(c, ggml_mul(c, guided, S(2)), ggml_mul(c, xs, S(3)));  // stable-diffusion.cpp:2876
             if (variant == 3) den = ggml_cpy(c, den, ss->denoised);
@@ -2803,7 +3054,7 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
                 ggml_context* c  = g.ctx;
                 ggml_tensor* tsc = ggml_new_tensor_1d(c, GGML_TYPE_F32, 8);
                 ggml_set_input(tsc);
-                in.push_back({tsc, sc, sizeof(sc)});
+                in.push_back({tsc, sc, 8 * sizeof(float)});
                 auto S = [&](int k) { return ggml_view_1d(c, tsc, 1, (size_t)k * sizeof(float)); };
                 ggml_tensor* xs  = st.x;
                 ggml_tensor* den = ggml_add(c, ggml_mul(c, st.eps, S(2)), ggml_mul(c, xs, S(3)));
@@ -3119,7 +3370,7 @@ bool sdm_planar_to_u8(sdm_ctx_t* ctx, const float* chw, int w, int h, int n, uin
 }
 
 bool sd_sample_latents(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, float* out_latents) {
-    const int W = p->width / 8, H = p->height / 8, C = ctx->in_channels();
+    const int W = p->width / 8, H = p->height / 8, C = ctx->latent_channels();
     const size_t per = (size_t)W * H * C;
     const int group  = p->device_batch > 0 ? p->device_batch : p->batch_count;
     const double t0  = now_ms();
@@ -3134,6 +3385,38 @@ bool sd_sample_latents(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, float* out
         if (ctx->pair_fn != nullptr && p->device_sampler) {
             set_error("step cache: not available with a CFG-pair exchange (the anchor condition lives on one rank only)");
             return false;
+        }
+    }
+    if (ctx->variant != SDM_UNET_PLAIN) {  // inpaint / pix2pix UNets: the model input needs its extra channels
+        const sdm_ctx_t::ConcatCondition& cs = ctx->concat_cond;
+        if (!cs.set()) {
+            set_error("model needs c_concat: no concat condition is set (sd_set_concat_condition)");
+            return false;
+        }
+        if (cs.w != W || cs.h != H || (cs.n != 1 && cs.n != p->batch_count)) {
+            set_error("concat condition is [" + std::to_string(cs.w) + "," + std::to_string(cs.h) + "," + std::to_string(cs.cc) + "," + std::to_string(cs.n) + "], the request needs [" +
+                      std::to_string(W) + "," + std::to_string(H) + "," + std::to_string(cs.cc) + ", 1 or " + std::to_string(p->batch_count) + "]");
+            return false;
+        }
+        const GuidancePlan gp = resolve_guidance_plan(ctx, p);
+        if (gp.img_cfg != 1.0f && !p->uncond.c_crossattn) {
+            set_error("image guidance (img_cfg != 1) needs the uncond conditioning: its text is the third condition's text");
+            return false;
+        }
+        if (gp.use_img_uncond) {  // the third branch
+            const sdm_sample_params_t& sp = p->sample_params;
+            if (ApgParams{sp.apg_eta, sp.apg_momentum, sp.apg_norm_threshold, sp.apg_norm_threshold_smoothing}.enabled()) {
+                set_error("image guidance: a third branch is not available together with adaptive projected guidance");
+                return false;
+            }
+            if (ctx->step_cache_would_arm(resolve_sample_method(ctx, sp.sample_method))) {
+                set_error("image guidance: a third branch is not available together with a step cache");
+                return false;
+            }
+            if (ctx->pair_fn != nullptr) {
+                set_error("image guidance: a third branch is not available with a CFG-pair exchange");
+                return false;
+            }
         }
     }
     if (ctx->preview.on() && ctx->pair_fn != nullptr && p->device_sampler) {
@@ -3177,7 +3460,7 @@ static void planar_rgb_to_u8(const float* f, size_t pix, uint8_t* d) {
 void sd_planar_rgb_to_u8(const float* chw, int width, int height, uint8_t* out) { planar_rgb_to_u8(chw, (size_t)width * height, out); }
 
 bool sdm_generate_image(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, sdm_image_t** images_out, int* num_images_out) {
-    const int W = p->width / 8, H = p->height / 8, C = ctx->in_channels();
+    const int W = p->width / 8, H = p->height / 8, C = ctx->latent_channels();
     const size_t per = (size_t)W * H * C;
     std::vector<float> latents(per * p->batch_count);
     if (!sd_sample_latents(ctx, p, latents.data())) return false;
@@ -3377,6 +3660,210 @@ void sd_apg_sequence(const float* cond, const float* uncond, int64_t n, int step
 }
 void sd_cfg_combine(const float* cond, const float* uncond, int64_t n, float scale, float* out) {
     for (int64_t k = 0; k < n; ++k) out[k] = cfg_guided(cond[k], uncond[k], scale);
+}
+// ---- inpaint / pix2pix UNets: image guidance, the concat condition and how it is made from pixels ----------------------------------------------
+// ClassifierFreeGuidance::forward's three forms (guidance.cpp:162-176) by which predictions exist: uncond or img_uncond may be NULL
+void sd_cfg_combine3(const float* cond, const float* uncond, const float* img_uncond, int64_t n, float txt_cfg, float img_cfg, float* out) {
+    for (int64_t k = 0; k < n; ++k)
+        out[k] = (uncond && img_uncond) ? cfg_guided3(cond[k], uncond[k], img_uncond[k], txt_cfg, img_cfg)
+                 : uncond               ? cfg_guided(cond[k], uncond[k], txt_cfg)
+                 : img_uncond           ? cfg_guided(cond[k], img_uncond[k], txt_cfg)
+                                        : cond[k];
+}
+bool sd_set_img_cfg(sdm_ctx_t* ctx, float img_cfg) {
+    if (std::isnan(img_cfg)) {
+        set_error("sd_set_img_cfg: NaN");
+        return false;
+    }
+    ctx->img_cfg = img_cfg;
+    ctx->guidance_status.clear();
+    if (ctx->variant == SDM_UNET_PLAIN && std::isfinite(img_cfg) && img_cfg != 1.0f) {
+        // resolve_guidance's warning (stable-diffusion.cpp:4242-4247): accepted and ignored
+        ctx->guidance_status = "3-conditioning CFG is not supported with this model, disabling it for better performance";
+        set_error(ctx->guidance_status);
+    }
+    return true;
+}
+bool sd_set_concat_condition(sdm_ctx_t* ctx, const float* concat, const float* img_uncond_concat, int w, int h, int cc, int n) {
+    sdm_ctx_t::ConcatCondition& s = ctx->concat_cond;
+    if (!concat) {
+        s = sdm_ctx_t::ConcatCondition();
+        return true;
+    }
+    if (ctx->variant == SDM_UNET_PLAIN) {
+        set_error("sd_set_concat_condition: the model takes no c_concat (a plain context)");
+        return false;
+    }
+    if (cc != ctx->concat_channels() || w < 1 || h < 1 || n < 1) {
+        set_error("sd_set_concat_condition: the model takes a [w,h," + std::to_string(ctx->concat_channels()) + ",n] concat, got cc = " + std::to_string(cc));
+        return false;
+    }
+    const size_t plane = (size_t)w * h, one = plane * cc, total = one * n;
+    s.concat.assign(concat, concat + total);
+    if (img_uncond_concat) {
+        s.img_uncond.assign(img_uncond_concat, img_uncond_concat + total);
+    } else {
+        // the reference's default (stable-diffusion.cpp:5145, 5168, 5173): inpaint keeps the mask channel and zeroes the masked latent, pix2pix is all zeros
+        s.img_uncond.assign(total, 0.0f);
+        if (ctx->variant == SDM_UNET_INPAINT)
+            for (int b = 0; b < n; ++b) memcpy(&s.img_uncond[(size_t)b * one], concat + (size_t)b * one, plane * sizeof(float));
+    }
+    s.w = w, s.h = h, s.cc = cc, s.n = n;
+    return true;
+}
+// sd::ops::round (tensor.hpp:1089-1092: std::round, halves away from zero — 0.5 becomes 1) followed by interpolate(..., NearestMax) to w/8 x h/8 (:1346-1360: the max over
+// the source block [o * in / out, ceil((o + 1) * in / out)) per axis): stable-diffusion.cpp:4986-5010
+bool sd_latent_mask(const float* mask, int w, int h, float* out) {
+    if (!mask || !out || w < 8 || h < 8 || w % 8 || h % 8) {
+        set_error("sd_latent_mask: width and height must be positive multiples of 8");
+        return false;
+    }
+    const int64_t lw = w / 8, lh = h / 8;
+    for (int64_t oy = 0; oy < lh; ++oy)
+        for (int64_t ox = 0; ox < lw; ++ox) {
+            const int64_t x0 = ox * w / lw, x1 = std::min<int64_t>(w, ((ox + 1) * w + lw - 1) / lw), y0 = oy * h / lh, y1 = std::min<int64_t>(h, ((oy + 1) * h + lh - 1) / lh);
+            float v = std::numeric_limits<float>::lowest();
+            for (int64_t y = y0; y < y1; ++y)
+                for (int64_t x = x0; x < x1; ++x) v = std::max(v, static_cast<float>(std::round(static_cast<double>(mask[y * w + x]))));
+            out[oy * lw + ox] = v;
+        }
+    return true;
+}
+// sd::ops::max_pool_2d(latent_mask, {3, 3}, {1, 1}, {1, 1}) (tensor.hpp:1473-1544; stable-diffusion.cpp:5197-5203): cells outside the map do not take part
+bool sd_mask_max_pool3(const float* in, int w, int h, float* out) {
+    if (!in || !out || w < 1 || h < 1 || in == out) {
+        set_error("sd_mask_max_pool3: bad arguments");
+        return false;
+    }
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            float v = std::numeric_limits<float>::lowest();
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int yy = y + dy, xx = x + dx;
+                    if (yy >= 0 && yy < h && xx >= 0 && xx < w) v = std::max(v, in[(size_t)yy * w + xx]);
+                }
+            out[(size_t)y * w + x] = v;
+        }
+    return true;
+}
+// prepare_image_generation_latents for the UNet inpaint and edit models (stable-diffusion.cpp:4986-5010, 5127-5173, 5197-5203).  Both encodes draw from Philox(seed)
+// at offset 0 (sd_vae_encode's convention; the reference continues one stream from the init image to the masked image)
+bool sd_make_inpaint_condition(sdm_ctx_t* ctx, const float* rgb, const float* mask, int w, int h, uint64_t seed, float* concat_out, float* img_uncond_concat_out,
+                               float* denoise_mask_out, float* init_latent_out) {
+    if (ctx->variant == SDM_UNET_PLAIN) {
+        set_error("sd_make_inpaint_condition: the model takes no c_concat (a plain context)");
+        return false;
+    }
+    if (!rgb || !concat_out || w < 8 || h < 8 || w % 8 || h % 8 || (ctx->variant == SDM_UNET_INPAINT && !mask)) {
+        set_error("sd_make_inpaint_condition: bad arguments (an image, sizes that are multiples of 8, and on an inpaint model a mask)");
+        return false;
+    }
+    const int lw = w / 8, lh = h / 8, zc = ctx->latent_channels();
+    const size_t plane = (size_t)lw * lh, pix = (size_t)w * h;
+    if (ctx->variant == SDM_UNET_PIX2PIX) {  // the encoded image; the third condition sees zeros; no denoise mask
+        if (!sd_vae_encode(ctx, rgb, w, h, 1, seed, concat_out, nullptr)) return false;
+        if (img_uncond_concat_out) std::fill(img_uncond_concat_out, img_uncond_concat_out + plane * zc, 0.0f);
+        if (init_latent_out) memcpy(init_latent_out, concat_out, plane * zc * sizeof(float));
+        return true;
+    }
+    std::vector<float> m(pix), masked(pix * 3);
+    for (size_t i = 0; i < pix; ++i) m[i] = static_cast<float>(std::round(static_cast<double>(mask[i])));
+    for (int c = 0; c < 3; ++c)
+        for (size_t i = 0; i < pix; ++i) masked[c * pix + i] = ((1.0f - m[i]) * (rgb[c * pix + i] - 0.5f)) + 0.5f;  // stable-diffusion.cpp:5132
+    if (!sd_latent_mask(mask, w, h, concat_out)) return false;                                                   // concat = latent mask | masked-image latent
+    if (!sd_vae_encode(ctx, masked.data(), w, h, 1, seed, concat_out + plane, nullptr)) return false;
+    if (img_uncond_concat_out) {
+        memcpy(img_uncond_concat_out, concat_out, plane * sizeof(float));
+        std::fill(img_uncond_concat_out + plane, img_uncond_concat_out + plane * (1 + zc), 0.0f);
+    }
+    if (denoise_mask_out && !sd_mask_max_pool3(concat_out, lw, lh, denoise_mask_out)) return false;
+    if (init_latent_out && !sd_vae_encode(ctx, rgb, w, h, 1, seed, init_latent_out, nullptr)) return false;
+    return true;
+}
+// the device-resident sampler's two glue stages on caller memory: the node chains sample_group_device emits (the model-input chain as it stands in front of
+// UNetModel::forward's concat, the three-term combine as in the step graph's tail), computed as graphs on the context's backend — one launch each on the MI355X
+// backend (plan_model_input / plan_guidance3), the plain nodes on any other
+bool sd_guidance_kernels(sdm_ctx_t* ctx, const float* x, float c_in, const float* concat, int w, int h, int c, int cc, int k, int nb, bool concat_per_image, float* xin_out,
+                         const float* e3, float txt_cfg, float img_cfg, float* guided_out) {
+    if (w < 1 || h < 1 || c < 1 || nb < 1 || (xin_out && (!x || !concat || cc < 1 || k < 1)) || (guided_out && !e3)) {
+        set_error("sd_guidance_kernels: bad arguments");
+        return false;
+    }
+    const int64_t per = (int64_t)w * h * c;
+    const float sc[9] = {c_in, txt_cfg, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, img_cfg};  // the step graph's scalar tensor: [0] c_in, [1] txt_cfg, [8] img_cfg
+    if (xin_out) {
+        Runner r;
+        r.backend    = ctx->backend;
+        r.graph_size = 256;
+        const int rows = concat_per_image ? k * nb : k;
+        auto build = [&](GraphCtx& g, std::vector<HostInput>& in) {
+            ggml_context* gc = g.ctx;
+            ggml_tensor* tsc = ggml_new_tensor_1d(gc, GGML_TYPE_F32, 9);
+            ggml_set_input(tsc);
+            in.push_back({tsc, sc, sizeof(sc)});
+            ggml_tensor* tx = ggml_new_tensor_4d(gc, GGML_TYPE_F32, w, h, c, nb);
+            ggml_set_input(tx);
+            in.push_back({tx, x, ggml_nbytes(tx)});
+            ggml_tensor* tcat = ggml_new_tensor_4d(gc, GGML_TYPE_F32, w, h, cc, rows);
+            ggml_set_input(tcat);
+            in.push_back({tcat, concat, ggml_nbytes(tcat)});
+            ggml_tensor* xin = ggml_mul(gc, tx, ggml_view_1d(gc, tsc, 1, 0));
+            if (k > 1) {
+                ggml_tensor* flat = ggml_reshape_3d(gc, xin, per, 1, nb);
+                ggml_tensor* rep  = ggml_repeat(gc, flat, ggml_new_tensor_3d(gc, GGML_TYPE_F32, per, k, nb));
+                xin               = ggml_reshape_4d(gc, rep, w, h, c, (int64_t)k * nb);
+            }
+            ggml_tensor* cat = tcat;
+            if (cat->ne[3] != xin->ne[3]) cat = ggml_repeat(gc, cat, ggml_new_tensor_4d(gc, GGML_TYPE_F32, w, h, cc, xin->ne[3]));
+            return ggml_concat(gc, xin, cat, 2);
+        };
+        if (!r.compute(build, xin_out, (size_t)w * h * (c + cc) * k * nb * sizeof(float))) return false;
+    }
+    if (guided_out) {
+        Runner r;
+        r.backend    = ctx->backend;
+        r.graph_size = 256;
+        auto build = [&](GraphCtx& g, std::vector<HostInput>& in) {
+            ggml_context* gc = g.ctx;
+            ggml_tensor* tsc = ggml_new_tensor_1d(gc, GGML_TYPE_F32, 9);
+            ggml_set_input(tsc);
+            in.push_back({tsc, sc, sizeof(sc)});
+            ggml_tensor* t3 = ggml_new_tensor_3d(gc, GGML_TYPE_F32, per, 3, nb);
+            ggml_set_input(t3);
+            in.push_back({t3, e3, ggml_nbytes(t3)});
+            auto S = [&](int j) { return ggml_view_1d(gc, tsc, 1, (size_t)j * sizeof(float)); };
+            ggml_tensor* ec = ggml_view_3d(gc, t3, per, 1, nb, t3->nb[1], t3->nb[2], 0);
+            ggml_tensor* eu = ggml_view_3d(gc, t3, per, 1, nb, t3->nb[1], t3->nb[2], t3->nb[1]);
+            ggml_tensor* ei = ggml_view_3d(gc, t3, per, 1, nb, t3->nb[1], t3->nb[2], 2 * t3->nb[1]);
+            ggml_tensor* a1 = ggml_add(gc, ei, ggml_mul(gc, ggml_sub(gc, eu, ei), S(8)));
+            ggml_tensor* s2 = ggml_mul(gc, ggml_sub(gc, ec, eu), S(1));
+            return ggml_add(gc, a1, s2);
+        };
+        if (!r.compute(build, guided_out, (size_t)per * nb * sizeof(float))) return false;
+    }
+    return true;
+}
+int sd_probe_unet_variant(const char* path) {
+    ModelFile mf;
+    if (!path || !read_model_file(path, mf)) {
+        set_error(path ? mf.error : std::string("sd_probe_unet_variant: NULL path"));
+        return -1;
+    }
+    const NameDialect dialect;  // (the first conv's name does not depend on the family's block layout)
+    const std::string want = "model.diffusion_model.input_blocks.0.0.weight";
+    for (const FileTensor& t : mf.tensors)
+        for (const char* prefix : {"", "unet."}) {  // diffusers keeps one file per sub-model whose names carry no component prefix
+            if (canonical_tensor_name(std::string(prefix) + t.name, dialect) != want) continue;
+            const int64_t ic = t.n_dims >= 3 ? t.ne[2] : 0;
+            if (ic == 4) return SDM_UNET_PLAIN;
+            if (ic == 9) return SDM_UNET_INPAINT;
+            if (ic == 8) return SDM_UNET_PIX2PIX;
+            set_error("sd_probe_unet_variant: input_blocks.0.0.weight has " + std::to_string(ic) + " input channels (4, 9 or 8 expected)");
+            return -1;
+        }
+    set_error("sd_probe_unet_variant: the file holds no model.diffusion_model.input_blocks.0.0.weight");
+    return -1;
 }
 bool sd_set_vae_conv2d_scale(sdm_ctx_t* ctx, float scale) {
     if (!ctx || !(scale > 0.f) || !std::isfinite(scale)) {

@@ -162,11 +162,20 @@ struct UNetModel {
         out_conv.init(ps, prefix + "out.2.", mc, cfg.out_channels, 3, 1, 1);
     }
 
-    // forward — unet.hpp:526-745.  x [W,H,C,N]; timesteps [N]; context [ctx_dim,77,N|1]; y [adm,N|1]
-    ggml_tensor* forward(GraphCtx& g, ggml_tensor* x, ggml_tensor* timesteps, ggml_tensor* context, ggml_tensor* y) const {
+    // forward — unet.hpp:526-745.  x [W,H,C,N]; timesteps [N]; context [ctx_dim,77,N|1]; y [adm,N|1]; c_concat [W,H,cc,N|1] (inpaint / pix2pix UNets) or NULL
+    ggml_tensor* forward(GraphCtx& g, ggml_tensor* x, ggml_tensor* timesteps, ggml_tensor* context, ggml_tensor* y, ggml_tensor* c_concat = nullptr) const {
         ggml_context* c = g.ctx;
         if (context != nullptr && context->ne[2] != x->ne[3]) {
             context = ggml_repeat(c, context, ggml_new_tensor_3d(c, GGML_TYPE_F32, context->ne[0], context->ne[1], x->ne[3]));
+        }
+        if (c_concat != nullptr) {  // unet.hpp:554-559
+            // The reference writes ggml_repeat(c_concat, x) here.  That cannot be copied: ggml_repeat asserts that every dimension of the target is a multiple of
+            // the source's, so it aborts whenever the concat width does not divide the latent channels (5 against 4 on an inpaint UNet), and the reference only
+            // ever reaches this line with equal batch.  The target here has the concat's own width and x's batch.
+            if (c_concat->ne[3] != x->ne[3]) {
+                c_concat = ggml_repeat(c, c_concat, ggml_new_tensor_4d(c, GGML_TYPE_F32, c_concat->ne[0], c_concat->ne[1], c_concat->ne[2], x->ne[3]));
+            }
+            x = ggml_concat(c, x, c_concat, 2);
         }
         if (y != nullptr && y->ne[1] != x->ne[3]) {
             y = ggml_repeat(c, y, ggml_new_tensor_2d(c, GGML_TYPE_F32, y->ne[0], x->ne[3]));

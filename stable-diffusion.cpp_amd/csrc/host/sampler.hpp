@@ -1210,6 +1210,18 @@ inline float cfg_guided(float cond, float uncond, float scale) {
     return uncond + s;
 }
 
+// the three-conditioning form of the same function (guidance.cpp:164-168): pred_img_uncond + image_guidance_scale * (pred_uncond - pred_img_uncond) +
+// guidance_scale * (pred_cond - pred_uncond) — SIX separately rounded f32 operations, evaluated left to right as the sd::Tensor operators do:
+// ((iu + img * (u - iu)) + txt * (c - u)).  With the img_uncond prediction alone the reference computes iu + txt * (c - iu): cfg_guided(c, iu, txt).
+inline float cfg_guided3(float cond, float uncond, float img_uncond, float txt_cfg, float img_cfg) {
+    volatile float d1 = uncond - img_uncond;
+    volatile float s1 = img_cfg * d1;
+    volatile float a1 = img_uncond + s1;
+    volatile float d2 = cond - uncond;
+    volatile float s2 = txt_cfg * d2;
+    return a1 + s2;
+}
+
 // AdaptiveProjectedGuidance::forward for the (cond, uncond) pair of ONE image of n floats — src/runtime/guidance.cpp:209-294: the guidance delta cond - uncond with momentum
 // (the buffer is carried by the caller from step to step), rescaled to a norm threshold (norm measured at SDXL's standard resolution), its component parallel to cond
 // scaled by eta; pred = cond + (scale - 1) * delta.  sd::Tensor<float>::sum accumulates in double and rounds once (tensor.hpp:340-347).  scale == 1: the reference returns cond.

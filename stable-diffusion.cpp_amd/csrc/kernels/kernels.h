@@ -50,6 +50,14 @@ struct TileMergeArgs {
     int store;                        // 1: canvas = value (both overlaps 0: the last covering tile wins, like successive copies); 0: canvas += value
 };
 void launch_tile_merge(hipStream_t s, float* canvas, const float* tiles, const float* wx, const float* wy, const TileMergeArgs& a);
+// ---- guidance.hip: the device-resident sampler's glue around an inpaint / pix2pix UNet (planner: plan_model_input, plan_guidance3) -------------------------
+// out [plane, C + cc, K * nb] f32: plane p < C of model image b * K + j = x[b] plane p times *scale (a DEVICE scalar; NULL = copied), plane p >= C = plane p - C
+// of concat row (b * K + j) % rows.  The bits of MUL -> RESHAPE -> REPEAT -> RESHAPE, [REPEAT,] CONCAT(dim 2).  Route 0: float4 (plane % 4 == 0, bases 16-byte
+// aligned), route 1: scalar.
+void launch_model_input(hipStream_t s, float* out, const float* x, const float* scale, const float* cat, int64_t plane, int C, int cc, int K, int64_t nb, int64_t rows);
+int64_t model_input_route_launches(int route);
+// out [per, nb] = iu + *img * (u - iu) + *txt * (c - u) from e3 [per, 3, nb] = (c, u, iu) per image, six separately rounded operations left to right
+void launch_guidance3(hipStream_t s, float* out, const float* e3, const float* txt, const float* img, int64_t per, int64_t nb);
 void launch_unary(hipStream_t s, UnOp op, float* dst, const float* src, int64_t n);
 void launch_scale(hipStream_t s, float* dst, const float* src, int64_t n, float scale, float bias);
 // generic strided copy with conversion between f32/f16/bf16 (logical element order preserved)
