@@ -145,6 +145,39 @@ struct ggml_backend_mi355x_stats {
     int64_t fused_guidance3;     /* the six nodes of the three-conditioning CFG combine over views of one [per, 3, nb] tensor run as ONE launch of k_guidance3 (option fuse_guidance3) */
     int64_t ew_model_input_v4;   /* launch_model_input: k_model_input<4> (plane a multiple of 4 floats, bases 16-byte aligned); per launch call, as the ew_* fields above */
     int64_t ew_model_input_v1;   /* ... k_model_input<1> */
+    /* gemm16.hip / qgemm.hip: Linear (weight MUL_MAT) launches per kernel route, counted where each launcher chooses (per launch call, as the g16_conv_* fields are) */
+    int64_t lin_t128;            /* launch_gemm16_linear / _multi / _geglu: k_gemm16<128, 128> */
+    int64_t lin_t128n64;         /* ... k_gemm16<128, 64> (narrow outputs, small grids, every in-launch K combine of such a shape) */
+    int64_t lin_t256;            /* ... 256 x 128, eight waves */
+    int64_t lin_t256w;           /* ... 256 x 128, four waves (option gemm16_tile only) */
+    int64_t lin_t160;            /* ... 256 x 160, four waves */
+    int64_t lin_t160n;           /* ... 256 x 160, eight waves */
+    int64_t lin_t320;            /* ... 256 x 320, pipelined */
+    int64_t lin_t256p;           /* ... 256 x 256, pipelined (f16 weight image) */
+    int64_t lin_t192p;           /* ... 256 x 192, pipelined (f16 weight image) */
+    int64_t lin_t256p_q8;        /* ... 256 x 256, raw q8_0 rows dequantised in the main loop */
+    int64_t lin_t256p_q4;        /* ... 256 x 256, raw q4_0 rows */
+    int64_t lin_t192p_q8;        /* ... 256 x 192, raw q8_0 rows */
+    int64_t lin_t192p_q4;        /* ... 256 x 192, raw q4_0 rows */
+    int64_t lin_streamk;         /* ... the stream-K instantiation of the 256 x 256 tile (option streamk) */
+    int64_t lin_rowsplit_main;   /* ... the whole-rounds launch of a row split (option tail_split); its tail counts under the tile it takes */
+    int64_t lin_multi;           /* launch_gemm16_linear_multi calls (the launch's tile is counted too) */
+    int64_t lin_splitk_reduce;   /* k_splitk_reduce behind a slab-split Linear */
+    int64_t lin_splitk_reduce_ln; /* k_splitk_reduce_ln behind one (fused_ln_reduce) */
+    int64_t lin_geglu_pair;      /* launch_gemm16_linear_geglu on the 128-column value / gate pairing (the launch's tile is counted too) */
+    int64_t lin_geglu16;         /* ... on the 16-column interleave */
+    int64_t lin_qgemv;           /* launch_qgemv: k_qgemv (one or two activation rows) */
+    int64_t lin_qgemv_rows4;     /* ... k_qgemv_rows<QT, 4> (3 .. 4 rows) */
+    int64_t lin_qgemv_rows8;     /* ... k_qgemv_rows<QT, 8> (5 .. 8 rows, option qgemv_max_rows) */
+    int64_t lin_qgemv_rows16;    /* ... k_qgemv_rows<QT, 16> (9 .. 16 rows) */
+    int64_t lin_qgemv_group;     /* launch_qgemv_group */
+    int64_t lin_qgemm16_rb1;     /* launch_qgemm16: k_qgemm16<QT, 1> (32-row tiles) */
+    int64_t lin_qgemm16_rb2;     /* ... k_qgemm16<QT, 2> */
+    int64_t lin_qgemm16_rb4;     /* ... k_qgemm16<QT, 4> */
+    int64_t lin_qgemm16_reduce;  /* the slab reduce behind a split launch_qgemm16 */
+    int64_t lin_fgemv_f16;       /* launch_fgemv: k_fgemv<f16 weights> */
+    int64_t lin_fgemv_f32;       /* ... k_fgemv<f32 weights> */
+    int64_t lin_wswz_q;          /* launch_wswz_q: just-in-time f16 weight image (option jit_qimages) */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and

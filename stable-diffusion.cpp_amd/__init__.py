@@ -418,7 +418,11 @@ _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned 
                         "c3w_tw16_bn256 c3w_tw16_bn320 c3w_tw32_bn256 c3w_tw32_bn320 c3w_tw64_bn256 c3w_tw64_bn320 c3w_tw128_bn256 c3w_tw128_bn320 "
                         "g16_conv_t128 g16_conv_t128n64 g16_conv_t256 g16_conv_t256w g16_conv_t160 g16_conv_t160n g16_conv_t320 g16_conv_t256p "
                         "g16_conv_splitk_reduce g16_conv_wmajor "
-                        "fused_model_input fused_guidance3 ew_model_input_v4 ew_model_input_v1").split()
+                        "fused_model_input fused_guidance3 ew_model_input_v4 ew_model_input_v1 "
+                        "lin_t128 lin_t128n64 lin_t256 lin_t256w lin_t160 lin_t160n lin_t320 lin_t256p lin_t192p lin_t256p_q8 lin_t256p_q4 lin_t192p_q8 lin_t192p_q4 "
+                        "lin_streamk lin_rowsplit_main lin_multi lin_splitk_reduce lin_splitk_reduce_ln lin_geglu_pair lin_geglu16 "
+                        "lin_qgemv lin_qgemv_rows4 lin_qgemv_rows8 lin_qgemv_rows16 lin_qgemv_group lin_qgemm16_rb1 lin_qgemm16_rb2 lin_qgemm16_rb4 lin_qgemm16_reduce "
+                        "lin_fgemv_f16 lin_fgemv_f32 lin_wswz_q").split()
 
 
 class BackendStats(C.Structure):

@@ -4364,6 +4364,10 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     for (int r = 0; r < CONV_ROUTE_COUNT; ++r) (&o->c3w_tw16_bn256)[r] = conv_route_launches(r);
     o->ew_model_input_v4 = model_input_route_launches(0);
     o->ew_model_input_v1 = model_input_route_launches(1);
+    // ... and where the Linear launchers choose theirs: the lin_* fields lie in the order of LinearRoute
+    static_assert(offsetof(ggml_backend_mi355x_stats, lin_wswz_q) - offsetof(ggml_backend_mi355x_stats, lin_t128) == (LIN_ROUTE_COUNT - 1) * sizeof(int64_t),
+                  "ggml_backend_mi355x_stats: one lin_* field per LinearRoute, in its order");
+    for (int r = 0; r < LIN_ROUTE_COUNT; ++r) (&o->lin_t128)[r] = linear_route_launches(r);
 }
 
 namespace {

@@ -1259,6 +1259,10 @@ static bool g16_trace();
 static std::atomic<int64_t> g_conv_route_launches[CONV_ROUTE_COUNT];
 void conv_route_taken(ConvRoute r) { g_conv_route_launches[r].fetch_add(1, std::memory_order_relaxed); }
 int64_t conv_route_launches(int route) { return route >= 0 && route < CONV_ROUTE_COUNT ? g_conv_route_launches[route].load(std::memory_order_relaxed) : 0; }
+// ... and Linear launches per route (kernels.h LinearRoute; qgemm.hip counts its own launchers here too)
+static std::atomic<int64_t> g_linear_route_launches[LIN_ROUTE_COUNT];
+void linear_route_taken(LinearRoute r) { g_linear_route_launches[r].fetch_add(1, std::memory_order_relaxed); }
+int64_t linear_route_launches(int route) { return route >= 0 && route < LIN_ROUTE_COUNT ? g_linear_route_launches[route].load(std::memory_order_relaxed) : 0; }
 // conv launches whose epilogue fills a GroupNorm side band (Epilogue::gn_rec, epi_conv_gn): unsplit, a 256-row tile with four wave rows of two row blocks
 // or eight wave rows of one (256 x 160 with four or eight waves, 256 x 320, 256 x 256 pipelined; not the 256 x 128 tiles), whole column tiles, whole GN_REC_CHUNK-position tiles per image
 static bool g16_gn_rec_tile_ok(int tile, int64_t C, int64_t ohow, int ny) {
@@ -1290,6 +1294,7 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
             if (g.sk_grid > 0) {  // stream-K: one persistent workgroup per CU (the planner asked g16_streamk_grid, which made the same tile choice)
                 KScope ks_(s, KF_LINEAR, flops, bytes);
                 if (tile == G16_T256P) {
+                    linear_route_taken(LIN_STREAMK);
                     g.ncol_tiles = (int)((g.C + 255) / 256);
                     k_gemm16<256, 256, false, 32, 4, 4, 2, 1, true><<<dim3((unsigned)g.sk_grid, 1), 512, 0, s>>>(g);
                 } else {
@@ -1308,6 +1313,7 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                 t.row_base      = g.row_base + (int64_t)rtm * 256;
                 {
                     KScope ks_(s, KF_LINEAR, flops * fm, bytes * fm);
+                    linear_route_taken(LIN_ROWSPLIT_MAIN);
                     g.ncol_tiles = (int)((g.C + 255) / 256);
                     if (g.C % 256 != 0) g.wblk_lim = (int)(rup64(g.C, 128) / 32);
                     k_gemm16<256, 256, false, 32, 4, 4, 2, 1><<<dim3((unsigned)(rtm * g.ncol_tiles), 1), 512, 0, s>>>(g);
@@ -1328,6 +1334,10 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
                 g.worder     = gemm16_worder_rows(t, (unsigned)(rt256 * t.ncol_tiles * mul), ny);
                 if (g.worder > 0) conv_route_taken(CONV_WMAJOR);
                 conv_route_taken(tile == G16_T320 ? CONV_G16_T320 : tile == G16_T256P ? CONV_G16_T256P : tile == G16_T160 ? CONV_G16_T160 : tile == G16_T160N ? CONV_G16_T160N : tile == G16_T256W ? CONV_G16_T256W : CONV_G16_T256);
+            } else {
+                const int q = g.qt == 8 ? 1 : g.qt ? 2 : 0;  // in-loop dequantisation: the pipelined 256 x 256 / 256 x 192 tiles only (checked above)
+                linear_route_taken(tile == G16_T320 ? LIN_T320 : tile == G16_T256P ? (LinearRoute)(q ? LIN_T256P_Q8 + q - 1 : LIN_T256P) : tile == G16_T192P ? (LinearRoute)(q ? LIN_T192P_Q8 + q - 1 : LIN_T192P)
+                                   : tile == G16_T160 ? LIN_T160 : tile == G16_T160N ? LIN_T160N : tile == G16_T256W ? LIN_T256W : LIN_T256);
             }
             if (tile == G16_T320) {
                 g.ncol_tiles = (int)((g.C + 319) / 320);
@@ -1406,6 +1416,7 @@ static void g16_launch(hipStream_t s, G16Args& g, int64_t rows, double flops, do
     }
     if (CONV_ && g.ep.gn_rec) g16_gn_rec_contract_violation();  // 128-row tiles do not fill a side band
     if (CONV_) conv_route_taken(BN_ == 64 ? CONV_G16_T128N64 : CONV_G16_T128);
+    else linear_route_taken(BN_ == 64 ? LIN_T128N64 : LIN_T128);
     const dim3 grid((unsigned)(((rows + 127) / 128) * g.ncol_tiles * mul), ny);
     KScope ks_(s, CONV_ ? KF_CONV_T128 : KF_LINEAR, flops, bytes);
     // (measured and rejected: the hand-pipelined loop of the 256x320 tile instantiated for a 128x128 tile — 2 waves of 64x128, 4 stages, two
@@ -1939,6 +1950,7 @@ void launch_gemm16_linear(hipStream_t s, float* dst, void* dst16, int64_t ldd16,
         abort();
     }
     if (S > 1 && !inker) {
+        linear_route_taken(e.ln_dst16 ? LIN_SPLITK_REDUCE_LN : LIN_SPLITK_REDUCE);
         if (e.ln_dst16)
             launch_splitk_reduce_ln(s, dst, splitk_ws, S, rows, M, e);
         else
@@ -1984,6 +1996,7 @@ void launch_gemm16_linear_multi(hipStream_t s, int n, float* const* dst, void* c
     for (int i = 0; i < n; ++i) out_b += (double)rows * M * (dst16[i] ? 2.0 : 4.0);
     const double bytes = (double)rows * Kp * 2.0 + (double)n * Kp * rup64(M, 128) * 2.0 + out_b;
     if (g16_trace()) fprintf(stderr, "G16 linear x%d rows=%lld K=%lld M=%lld hm=%d\n", n, (long long)rows, (long long)K, (long long)M, hm_d);
+    linear_route_taken(LIN_MULTI);
     if (g16_use_bn64(rows, M, n)) {
         g.ncol_tiles = (int)((M + 63) / 64);
         g16_launch<64, false>(s, g, rows, 2.0 * n * rows * K * M, bytes);
@@ -2026,6 +2039,7 @@ void launch_gemm16_linear_geglu(hipStream_t s, void* dst16, const void* a16, int
         g.sk_cnt   = splitk_cnt;
     }
     if (g16_trace()) fprintf(stderr, "G16 linear rows=%lld K=%lld M=%lld res=0 hm=0 f16out=1 geglu=1\n", (long long)rows, (long long)K, (long long)M);
+    linear_route_taken(g.geglu16 ? LIN_GEGLU16 : LIN_GEGLU_PAIR);
     g16_launch<128, false>(s, g, rows, 2.0 * rows * K * M, (double)rows * rup64(K, 64) * 2.0 + (double)rup64(K, 64) * rup64(M, 128) * 2.0 + (double)rows * (M / 2) * 2.0);
 }
 

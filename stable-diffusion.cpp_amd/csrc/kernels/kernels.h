@@ -262,6 +262,29 @@ enum ConvRoute {
 };
 void conv_route_taken(ConvRoute r);
 int64_t conv_route_launches(int route);
+// Which kernel a Linear (weight MUL_MAT) launcher chose, counted per launch call where the choice is made (as ConvRoute is).  LIN_T*: the non-conv branch of
+// g16_launch (a GEGLU, grouped or head-major launch counts its tile here too; the tail of a row split counts under its own tile); the *_Q8 / *_Q4 forms are the
+// in-loop dequantising instantiations k_gemm16<..., QT>.  The experiment-only instantiations (MI355X_EXPERIMENTS, gemm16_variant 0 / 2) are not counted.
+enum LinearRoute {
+    LIN_T128 = 0, LIN_T128N64, LIN_T256, LIN_T256W, LIN_T160, LIN_T160N, LIN_T320, LIN_T256P, LIN_T192P,
+    LIN_T256P_Q8, LIN_T256P_Q4, LIN_T192P_Q8, LIN_T192P_Q4,
+    LIN_STREAMK,           // k_gemm16<256, 256, ..., SK>: one persistent workgroup per CU
+    LIN_ROWSPLIT_MAIN,     // the whole-rounds launch of a row split (g16_tail_rows)
+    LIN_MULTI,             // launch_gemm16_linear_multi, once per sibling launch
+    LIN_SPLITK_REDUCE,     // k_splitk_reduce behind a slab-split launch_gemm16_linear
+    LIN_SPLITK_REDUCE_LN,  // k_splitk_reduce_ln (the reduce pass that also writes the next LayerNorm's operand image)
+    LIN_GEGLU_PAIR, LIN_GEGLU16,  // launch_gemm16_linear_geglu on the 128-column pairing / the 16-column interleave
+    LIN_QGEMV,             // launch_qgemv: k_qgemv (one or two rows)
+    LIN_QGEMV_ROWS4, LIN_QGEMV_ROWS8, LIN_QGEMV_ROWS16,  // launch_qgemv: k_qgemv_rows<QT, R> for 3 .. 4 / 5 .. 8 / 9 .. 16 rows
+    LIN_QGEMV_GROUP,       // launch_qgemv_group
+    LIN_QGEMM16_RB1, LIN_QGEMM16_RB2, LIN_QGEMM16_RB4,  // launch_qgemm16: k_qgemm16<QT, RB>
+    LIN_QGEMM16_REDUCE,    // the slab reduce behind a split launch_qgemm16
+    LIN_FGEMV_F16, LIN_FGEMV_F32,  // launch_fgemv: k_fgemv<W16>
+    LIN_WSWZ_Q,            // launch_wswz_q: the just-in-time f16 image of a q8_0 / q4_0 weight
+    LIN_ROUTE_COUNT
+};
+void linear_route_taken(LinearRoute r);
+int64_t linear_route_launches(int route);
 // ---- conv3w.hip: 3x3 / stride-1 conv with the input window resident in LDS (weights in the kblk = 32 image)
 // K slices the window kernel would run this shape with (>= 1), or 0: the shape stays on launch_gemm16_conv
 int conv3w_plan(int64_t W, int64_t H, int64_t IC, int64_t N, int64_t OC, int ksize, int stride, bool upscale2x, int* bn_out = nullptr);

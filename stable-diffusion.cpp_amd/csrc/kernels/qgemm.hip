@@ -430,6 +430,7 @@ void launch_qgemv(hipStream_t s, float* dst, int64_t ldd, const float* x, int64_
         const unsigned grid2 = (unsigned)((M + 4 * CPW2 - 1) / (4 * CPW2));
         const int r          = rows <= 4 ? 4 : rows <= 8 ? 8 : 16;
         const size_t lds     = (size_t)r * K * 2;
+        linear_route_taken(r == 4 ? LIN_QGEMV_ROWS4 : r == 8 ? LIN_QGEMV_ROWS8 : LIN_QGEMV_ROWS16);
 #define QGR_LAUNCH(QT_, R_)                                                                                                         \
     do {                                                                                                                            \
         static bool attr_dev_[64] = {false};                                                                                        \
@@ -455,6 +456,7 @@ void launch_qgemv(hipStream_t s, float* dst, int64_t ldd, const float* x, int64_
     }
     constexpr int CPW = 4;
     const unsigned grid = (unsigned)((M + 4 * CPW - 1) / (4 * CPW));
+    linear_route_taken(LIN_QGEMV);
 #define QG_LAUNCH(QT_, R_) k_qgemv<QT_, R_, CPW><<<grid, 256, (size_t)(R_) * K * 2, s>>>(g)
     if (wtype == 8) {
         if (rows == 1) QG_LAUNCH(8, 1);
@@ -486,6 +488,7 @@ void launch_qgemv_group(hipStream_t s, float* dst, int64_t Mtot, const float* x,
     g.K = (int)K; g.M = (int)Mtot; g.rows = (int)rows; g.pre_silu = pre_silu ? 1 : 0;
     constexpr int CPW = 4;
     const unsigned grid = (unsigned)((Mtot + 4 * CPW - 1) / (4 * CPW));
+    linear_route_taken(LIN_QGEMV_GROUP);
 #define QG_LAUNCH(QT_, R_) k_qgemv<QT_, R_, CPW><<<grid, 256, (size_t)(R_) * K * 2, s>>>(g)
     if (wtype == 8) {
         if (rows == 1) QG_LAUNCH(8, 1);
@@ -799,6 +802,7 @@ void launch_wswz_q(hipStream_t s, void* dst, const void* wraw, int wtype, int64_
     const int64_t Rp = (R + 127) / 128 * 128, nblk = K / 32;
     KScope ks_(s, KF_PACK_F16, 0.0, (double)R * nblk * (wtype == 8 ? 34 : 18) + (double)Rp * K * 2.0);
     const dim3 grid((unsigned)(Rp / 128), (unsigned)(K / 256));
+    linear_route_taken(LIN_WSWZ_Q);
     if (wtype == 8)
         k_wswz_q<8><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, nblk * 34, R, K / 16);
     else
@@ -865,6 +869,7 @@ void launch_qgemm16(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const
     if (g_qg16_rb == 1 || g_qg16_rb == 2 || g_qg16_rb == 4) rb = rows <= 32 ? 1 : (rows <= 64 && g_qg16_rb > 2) ? 2 : g_qg16_rb;
     else if (g_qg16_rb == 3 && rb == 4 && ((rows + 127) / 128) * ((M + 127) / 128) * S < 512) rb = 2;  // 3 = auto: 64-row tiles while the grid stays under two workgroups per CU
     const dim3 grid((unsigned)((rows + rb * 32 - 1) / (rb * 32)), (unsigned)((M + 127) / 128), (unsigned)S);
+    linear_route_taken(rb == 1 ? LIN_QGEMM16_RB1 : rb == 2 ? LIN_QGEMM16_RB2 : LIN_QGEMM16_RB4);
 #define QG16_LAUNCH(QT_, RB_) k_qgemm16<QT_, RB_><<<grid, 256, 0, s>>>(g)
     if (wtype == 8) {
         if (rb == 1) QG16_LAUNCH(8, 1);
@@ -876,7 +881,10 @@ void launch_qgemm16(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const
         else QG16_LAUNCH(4, 4);
     }
 #undef QG16_LAUNCH
-    if (S > 1) splitk_reduce_rows(s, dst, splitk_ws, S, rows * M, ep.bias, M, ep.residual);
+    if (S > 1) {
+        linear_route_taken(LIN_QGEMM16_REDUCE);
+        splitk_reduce_rows(s, dst, splitk_ws, S, rows * M, ep.bias, M, ep.residual);
+    }
 }
 
 
@@ -1035,6 +1043,7 @@ void launch_fgemv(hipStream_t s, float* dst, int64_t ldd, const float* x, int64_
     static bool attr_dev_[64][2] = {};
     int dev_ = 0;
     (void)hipGetDevice(&dev_);
+    linear_route_taken(wtype == 1 ? LIN_FGEMV_F16 : LIN_FGEMV_F32);
     if (wtype == 1) {
         if (!attr_dev_[dev_ & 63][0]) {
             (void)hipFuncSetAttribute((const void*)k_fgemv<true, CPW, NIT>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
