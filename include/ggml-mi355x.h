@@ -178,6 +178,9 @@ struct ggml_backend_mi355x_stats {
     int64_t lin_fgemv_f16;       /* launch_fgemv: k_fgemv<f16 weights> */
     int64_t lin_fgemv_f32;       /* ... k_fgemv<f32 weights> */
     int64_t lin_wswz_q;          /* launch_wswz_q: just-in-time f16 weight image (option jit_qimages) */
+    /* IP-Adapter cross-attention (option fuse_ip_attn) */
+    int64_t fused_ip_attn;           /* attn2 pairs FLASH_ATTN_EXT(q,k,v) / FLASH_ATTN_EXT(q,k_ip,v_ip) -> SCALE -> ADD planned as ONE launch of k_flash_short_ip (per plan; a pair refused for the placement of its operands counts in flash_out_alias) */
+    int64_t flash_short_ip_launches; /* launch_flash_attn_ip calls (per launch call, as flash_short_launches) */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and
@@ -239,6 +242,8 @@ GGML_MI355X_API int ggml_backend_mi355x_get_kernel_timings(struct ggml_backend_m
  * round 6: "qinloop_min_rows" (513: q8_0 / q4_0 Linears with at least that many activation rows whose launch takes the pipelined 256 x 256 tile read the RAW GGUF blocks and
  * dequantise them inside the GEMM's main loop — no f16 weight image, cached or rebuilt; 0 = off: cached image, or "jit_qimages" rebuild),
  * "fuse_flash_slices" (1: the proj Linears of an MMDiT / FLUX double block read their token slices out of the flash kernel's f16 image), "gemm16_t192p" (1: the pipelined 256 x 192 Linear tile where it quantises better on 256 CUs), "hoist_mod" (1), "plan_cache_cap" (512), "gn_split_min" (65536);
+ * "fuse_ip_attn" (1: the two attentions of an IP-Adapter attn2 — text keys and 1 .. 32 image keys of the same q — with their SCALE and ADD as one launch of
+ * k_flash_short_ip; 0 = plain nodes on k_flash_short and the elementwise launches);
  * "fuse_ln_reduce" (1: the slab reduce of a split-K Linear also writes the f16 operand image of the LayerNorm that reads its result);
  * "fuse_gn_epilogue" (1: an unsplit LDS-window conv read by a GroupNorm, or by a skip CONCAT a GroupNorm reads, writes per-channel (mean, M2) records of the values it
  * stores; the GroupNorm's statistics pass over the tensor becomes one small finalize launch over the records; 0 = the plan without it);

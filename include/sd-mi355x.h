@@ -237,6 +237,36 @@ SD_API bool sd_unet_forward(sdm_ctx_t* ctx, const float* x, int w, int h, int c,
  * context is an error ("model needs c_concat"), never a silent zero-fill; so is a wrong cc */
 SD_API bool sd_unet_forward_concat(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim, int64_t n_tokens,
                                    int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const float* c_concat, int cc, int concat_n, float* out);
+/* ---- IP-Adapter (src/model/adapter/ip_adapter.hpp, CrossAttention::to_k_ip / to_v_ip, block.hpp:307-393); UNet families only.
+ * In scope: the plain adapters (ImageProjModel: Linear + LayerNorm).  Out of scope: the Resampler of the "plus" adapters (it needs GELU_ERF, which neither the ggml
+ * front-end, the backend nor the CPU oracle implement) and the CLIP vision tower — the API takes CLIP image embeddings like the text side takes token ids; a caller
+ * with plus tokens from elsewhere passes them as ip_context directly.
+ * sd_ip_adapter_init adds "...attn2.to_k_ip.weight" / "...attn2.to_v_ip.weight" [ip_dim -> inner, no bias] to every attn2 and "ip_adapter.image_proj.{proj,norm}.*", in a
+ * weight buffer of their own with synthetic values from the seeded initialiser (sd_set_tensor_f32 binds real ones); the resident weights stay untouched.  A second
+ * call with the same dimensions is a no-op, with other dimensions an error. */
+SD_API bool sd_ip_adapter_init(sdm_ctx_t* ctx, int64_t ip_dim, int64_t clip_dim, int64_t num_tokens, uint64_t weight_seed);
+/* an adapter file (safetensors / the formats sd_load_weights reads): names converted by the reference's rule (name_conversion.cpp:1307-1344; "ip_adapter.<idx>.to_k_ip.weight" ->
+ * "model.diffusion_model.<block>.attn2.to_k_ip.weight", "image_proj.*" -> "ip_adapter.image_proj.*"), the adapter initialised from the file's shapes if it is not yet, its
+ * parameters (and only they) bound.  Returns the number loaded or -1; n_missing counts adapter parameters the file lacks, n_unused file tensors nothing took */
+SD_API int64_t sd_load_ip_adapter(sdm_ctx_t* ctx, const char* path, int64_t* n_missing, int64_t* n_unused);
+SD_API bool sd_ip_adapter_info(sdm_ctx_t* ctx, int64_t* ip_dim, int64_t* clip_dim, int64_t* num_tokens); /* false: no adapter initialised */
+/* ImageProjModel: CLIP image embeddings [clip_dim, n] -> image tokens tokens_out [ip_dim, num_tokens, n] */
+SD_API bool sd_ip_adapter_project(sdm_ctx_t* ctx, const float* embeds, int n, float* tokens_out);
+/* Token state for the sampling entries (context state like sd_set_vae_tiling): sdm_generate_image and sd_sample_latents — the host loop, its fused branches, the
+ * device-resident sampler, inpaint / pix2pix variants, the CFG-pair exchange — hand `tokens` [ip_dim, n_tokens] to the cond branch and `uncond_tokens` to every other
+ * branch (uncond, img_uncond; stable-diffusion.cpp:2829-2843), scaled by `strength` (0: the graphs of a context without the adapter).  In a graph of K branches per image
+ * they form one [ip_dim, n_tokens, K] input, assembled once per trajectory.  tokens NULL clears.  uncond_tokens NULL: the projection of an all-zero embedding
+ * (stable-diffusion.cpp:2206-2207; not zero when the projection's LayerNorm has a bias) — n_tokens must then be the projection's token count.  Every device group
+ * (device_batch images of the request at a time) of a call uses the same tokens. */
+SD_API bool sd_set_ip_adapter(sdm_ctx_t* ctx, const float* tokens, const float* uncond_tokens, int64_t n_tokens, float strength);
+/* sd_ip_adapter_project of one CLIP image embedding [clip_dim] + sd_set_ip_adapter with the default uncond tokens, as the reference does; NULL clears */
+SD_API bool sd_set_ip_adapter_embeds(sdm_ctx_t* ctx, const float* embeds, float strength);
+/* sd_unet_forward_concat's arguments (c_concat NULL on a plain context) plus the image tokens ip_context [ip_dim, n_ip, ip_n] (ip_n 1 or a divisor of n) and ip_scale.
+ * Every attn2 emits, behind its text attention, what block.hpp:382-389 emits: to_k_ip, to_v_ip, the attention of the same q onto them, SCALE, ADD.  ip_context NULL or
+ * ip_scale 0: the graph of a context without the adapter */
+SD_API bool sd_unet_forward_ip(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim, int64_t n_tokens,
+                               int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const float* c_concat, int cc, int concat_n, const float* ip_context, int64_t n_ip,
+                               int ip_n, float ip_scale, float* out);
 /* the same forward WITHOUT the listed joint blocks — MMDiT::forward's skip_layers (mmdit.hpp:854-866), the extra evaluation of skip-layer guidance; MMDiT family only */
 SD_API bool sd_unet_forward_skip_layers(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim,
                                         int64_t n_tokens, int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const int* skip_layers, int n_skip, float* out);

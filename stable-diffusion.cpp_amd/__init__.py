@@ -422,7 +422,8 @@ _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned 
                         "lin_t128 lin_t128n64 lin_t256 lin_t256w lin_t160 lin_t160n lin_t320 lin_t256p lin_t192p lin_t256p_q8 lin_t256p_q4 lin_t192p_q8 lin_t192p_q4 "
                         "lin_streamk lin_rowsplit_main lin_multi lin_splitk_reduce lin_splitk_reduce_ln lin_geglu_pair lin_geglu16 "
                         "lin_qgemv lin_qgemv_rows4 lin_qgemv_rows8 lin_qgemv_rows16 lin_qgemv_group lin_qgemm16_rb1 lin_qgemm16_rb2 lin_qgemm16_rb4 lin_qgemm16_reduce "
-                        "lin_fgemv_f16 lin_fgemv_f32 lin_wswz_q").split()
+                        "lin_fgemv_f16 lin_fgemv_f32 lin_wswz_q "
+                        "fused_ip_attn flash_short_ip_launches").split()
 
 
 class BackendStats(C.Structure):
@@ -708,14 +709,35 @@ class Engine:
             raise EngineError(f"sd_set_tensor_f32({name}) failed")
 
     # ---- hot path ----
-    def unet_forward(self, x: np.ndarray, timesteps: np.ndarray, context: np.ndarray, y: np.ndarray | None = None, c_concat: np.ndarray | None = None) -> np.ndarray:
-        """x [N,C,H,W]; timesteps [N]; context [Nc,77,ctx_dim] (Nc in {1,N}); y [Ny,adm] or None; c_concat [1 or N, cc, H, W] on an inpaint / pix2pix engine."""
+    def unet_forward(self, x: np.ndarray, timesteps: np.ndarray, context: np.ndarray, y: np.ndarray | None = None, c_concat: np.ndarray | None = None,
+                     ip_context: np.ndarray | None = None, ip_scale: float = 1.0) -> np.ndarray:
+        """x [N,C,H,W]; timesteps [N]; context [Nc,77,ctx_dim] (Nc in {1,N}); y [Ny,adm] or None; c_concat [1 or N, cc, H, W] on an inpaint / pix2pix engine;
+        ip_context [1 or N, n_ip, ip_dim] image tokens of an initialised IP-Adapter (ip_adapter_init), added to every attn2 with weight ip_scale."""
         x = _f32(x)
         t = _f32(timesteps)
         ctxt = _f32(context)
         n, c, h, w = x.shape
         out = np.empty_like(x)
         yy = None if y is None else _f32(y)
+        if ip_context is not None:
+            ip = _f32(ip_context)
+            info = self.ip_adapter_info()
+            if info is None:
+                raise EngineError("ip_context given, but no IP-Adapter is initialised on this engine (ip_adapter_init)")
+            if ip.ndim != 3 or ip.shape[2] != info[0]:
+                raise EngineError(f"ip_context is [1 or N, n_ip, ip_dim = {info[0]}], got {ip.shape}")
+            cat = None if c_concat is None else _f32(c_concat)
+            if cat is not None:
+                assert cat.ndim == 4 and cat.shape[2:] == (h, w), "c_concat is [1 or N, cc, H, W]"
+            L = lib()
+            L.sd_unet_forward_ip.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                             C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p]
+            L.sd_unet_forward_ip.restype = C.c_bool
+            if not L.sd_unet_forward_ip(self._ctx, _fptr(x), w, h, c, n, _fptr(t), _fptr(ctxt), ctxt.shape[2], ctxt.shape[1], ctxt.shape[0], _fptr(yy),
+                                        0 if yy is None else yy.shape[1], 0 if yy is None else yy.shape[0], _fptr(cat), 0 if cat is None else cat.shape[1],
+                                        0 if cat is None else cat.shape[0], _fptr(ip), ip.shape[1], ip.shape[0], float(ip_scale), _fptr(out)):
+                raise EngineError("sd_unet_forward_ip failed: " + L.sd_last_error().decode())
+            return out
         if c_concat is not None:
             cat = _f32(c_concat)
             L = lib()
@@ -747,6 +769,90 @@ class Engine:
         if not L.sd_unet_forward_skip_layers(self._ctx, _fptr(x), w, h, c, n, _fptr(t), _fptr(ctxt), ctxt.shape[2], ctxt.shape[1], ctxt.shape[0], _fptr(yy),
                                              0 if yy is None else yy.shape[1], 0 if yy is None else yy.shape[0], sk.ctypes.data_as(C.c_void_p), sk.size, _fptr(out)):
             raise EngineError("sd_unet_forward_skip_layers failed: " + L.sd_last_error().decode())
+        return out
+
+    # ---- IP-Adapter: image tokens in every attn2 (plain adapters: ImageProjModel; the Resampler and the CLIP vision tower are out of scope) ----
+    def ip_adapter_init(self, ip_dim: int, clip_dim: int, num_tokens: int = 4, weight_seed: int = 0) -> None:
+        """sd_ip_adapter_init: to_k_ip / to_v_ip on every attn2 plus the image projection, synthetic weights (set_tensor binds real ones).  UNet families only."""
+        L = lib()
+        L.sd_ip_adapter_init.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64]
+        L.sd_ip_adapter_init.restype = C.c_bool
+        if not L.sd_ip_adapter_init(self._ctx, int(ip_dim), int(clip_dim), int(num_tokens), int(weight_seed)):
+            raise EngineError("sd_ip_adapter_init failed: " + L.sd_last_error().decode())
+
+    def load_ip_adapter(self, path) -> dict:
+        """sd_load_ip_adapter: an adapter file (`ip_adapter.<idx>.to_{k,v}_ip.weight`, `image_proj.{proj,norm}.*`); initialises the adapter from the file's shapes if needed."""
+        miss, unused = C.c_int64(0), C.c_int64(0)
+        L = lib()
+        L.sd_load_ip_adapter.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.sd_load_ip_adapter.restype = C.c_int64
+        n = L.sd_load_ip_adapter(self._ctx, str(path).encode(), C.byref(miss), C.byref(unused))
+        if n < 0:
+            raise EngineError("sd_load_ip_adapter failed: " + L.sd_last_error().decode())
+        return {"loaded": int(n), "missing": int(miss.value), "unused": int(unused.value)}
+
+    def set_ip_adapter(self, tokens: np.ndarray | None = None, uncond_tokens: np.ndarray | None = None, embeds: np.ndarray | None = None, strength: float = 1.0) -> None:
+        """sd_set_ip_adapter / sd_set_ip_adapter_embeds: the image tokens the sampling entries use — `tokens` [n_tokens, ip_dim] on the cond branch, `uncond_tokens` (default:
+        the projection of an all-zero embedding) on every other branch — or `embeds` [clip_dim], projected first.  Neither given: cleared."""
+        L = lib()
+        L.sd_set_ip_adapter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
+        L.sd_set_ip_adapter.restype = C.c_bool
+        L.sd_set_ip_adapter_embeds.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
+        L.sd_set_ip_adapter_embeds.restype = C.c_bool
+        if tokens is not None and embeds is not None:
+            raise EngineError("set_ip_adapter: give tokens or embeds, not both")
+        if tokens is None and embeds is None:
+            if uncond_tokens is not None:
+                raise EngineError("set_ip_adapter: uncond_tokens without tokens")
+            L.sd_set_ip_adapter(self._ctx, None, None, 0, 0.0)
+            return
+        info = self.ip_adapter_info()
+        if info is None:
+            raise EngineError("set_ip_adapter: no IP-Adapter is initialised on this engine (ip_adapter_init / load_ip_adapter)")
+        if embeds is not None:
+            e = _f32(embeds).reshape(-1)
+            if e.size != info[1]:
+                raise EngineError(f"set_ip_adapter: embeds are [clip_dim = {info[1]}], got {e.size} values")
+            ok = L.sd_set_ip_adapter_embeds(self._ctx, _fptr(e), float(strength))
+        else:
+            t = _f32(tokens)
+            t = t[0] if t.ndim == 3 and t.shape[0] == 1 else t
+            if t.ndim != 2 or t.shape[1] != info[0]:
+                raise EngineError(f"set_ip_adapter: tokens are [n_tokens, ip_dim = {info[0]}], got {t.shape}")
+            u = None
+            if uncond_tokens is not None:
+                u = _f32(uncond_tokens)
+                u = u[0] if u.ndim == 3 and u.shape[0] == 1 else u
+                if u.shape != t.shape:
+                    raise EngineError(f"set_ip_adapter: uncond_tokens are {u.shape}, tokens {t.shape}: the two token sets must have one shape (n_tokens mismatch)")
+            ok = L.sd_set_ip_adapter(self._ctx, _fptr(np.ascontiguousarray(t)), None if u is None else _fptr(np.ascontiguousarray(u)), t.shape[0], float(strength))
+        if not ok:
+            raise EngineError("sd_set_ip_adapter failed: " + L.sd_last_error().decode())
+
+    def ip_adapter_info(self):
+        """(ip_dim, clip_dim, num_tokens) of the initialised adapter, or None."""
+        L = lib()
+        L.sd_ip_adapter_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sd_ip_adapter_info.restype = C.c_bool
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        if not L.sd_ip_adapter_info(self._ctx, C.byref(a), C.byref(b), C.byref(c)):
+            return None
+        return int(a.value), int(b.value), int(c.value)
+
+    def ip_adapter_project(self, embeds: np.ndarray) -> np.ndarray:
+        """sd_ip_adapter_project: CLIP image embeddings [n, clip_dim] -> image tokens [n, num_tokens, ip_dim]."""
+        info = self.ip_adapter_info()
+        if info is None:
+            raise EngineError("ip_adapter_project: no IP-Adapter is initialised on this engine (ip_adapter_init)")
+        e = _f32(embeds)
+        if e.ndim != 2 or e.shape[1] != info[1]:
+            raise EngineError(f"ip_adapter_project: embeds are [n, clip_dim = {info[1]}], got {e.shape}")
+        out = np.empty((e.shape[0], info[2], info[0]), dtype=np.float32)
+        L = lib()
+        L.sd_ip_adapter_project.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.sd_ip_adapter_project.restype = C.c_bool
+        if not L.sd_ip_adapter_project(self._ctx, _fptr(e), e.shape[0], _fptr(out)):
+            raise EngineError("sd_ip_adapter_project failed: " + L.sd_last_error().decode())
         return out
 
     # ---- inpaint / pix2pix UNets: c_concat state, image guidance, the condition from pixels ----

@@ -168,7 +168,7 @@ std::atomic<int64_t> g_stat_counters[N_STATS];
 #define STAT(field) g_stat_counters[offsetof(ggml_backend_mi355x_stats, field) / sizeof(int64_t)]
 
 struct Options {
-    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1}, fuse_gn_epilogue{1}, fuse_tile_merge{1}, fuse_model_input{1}, fuse_guidance3{1};
+    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1}, fuse_gn_epilogue{1}, fuse_tile_merge{1}, fuse_model_input{1}, fuse_guidance3{1}, fuse_ip_attn{1};
 } g_opt;
 
 using Step = std::function<void(hipStream_t)>;  // one launch (or a few) of a plan
@@ -505,6 +505,9 @@ struct Builder {
     size_t arena_off = 0;
     std::unordered_map<const ggml_tensor*, Packed> packed;           // graph tensor -> f16 operand image
     std::unordered_map<const ggml_tensor*, size_t> q16;              // flash Q operand (the RESHAPE the node reads) -> f16 head-major image in the arena
+    // IP-Adapter attn2: the second attention's own head-major copy of q (q_twin_of) -> the first attention's, when the projection GEMM wrote ONE f16 image for both
+    // (plan_linear; the second copy's nodes are not executed)
+    std::unordered_map<const ggml_tensor*, const ggml_tensor*> q_alias;
     std::unordered_map<const ggml_tensor*, const ggml_tensor*> ups;  // deferred nearest-x2 UPSCALE node -> its source
     std::unordered_map<const ggml_tensor*, const ggml_tensor*> presilu;  // deferred SiLU node in front of a few-row Linear -> its source (applied by k_fgemv / k_qgemv on load)
     std::map<int, std::vector<Step>> deferred;                       // steps to run once the walk reaches graph node <key>
@@ -824,6 +827,131 @@ bool all_consumers_gemm16(const GInfo& gi, int i, bool want_conv, float* mul_out
     return n_real > 0;
 }
 
+// FLASH_ATTN_EXT (node i) -> VIEW [d,H,Lq,N] -> CONT [C,Lq,N] as ggml_ext_attention_ext ends it (ggml_extend.hpp:1446-1455, 1481-1482): the VIEW and the CONT
+static bool flash_view_cont(const GInfo& gi, int i, int& j1, int& j2) {
+    const ggml_tensor* n = gi.node(i);
+    j1 = gi.sole(i);
+    j2 = (j1 >= 0 && xop(gi.node(j1)) == GGML_OP_VIEW) ? gi.sole(j1) : -1;
+    if (j2 < 0 || xop(gi.node(j2)) != GGML_OP_CONT || gi.node(j2)->src[0] != gi.node(j1) || !is_f32(gi.node(j2)) || !contig(gi.node(j2))) return false;
+    const ggml_tensor* vw = gi.node(j1);
+    const int64_t d = vw->ne[0], H = vw->ne[1], Lq = vw->ne[2], Nimg = vw->ne[3];
+    return d == n->ne[0] && H * Nimg == n->ne[1] && Lq == n->ne[2] && (const char*)vw->data == (const char*)n->data && (int64_t)vw->nb[1] == (int64_t)n->nb[1] &&
+           (int64_t)vw->nb[2] == (int64_t)n->nb[2] && (int64_t)vw->nb[3] == (int64_t)n->nb[1] * H;
+}
+
+// The decoupled cross-attention of an IP-Adapter attn2 (block.hpp:380-389):
+//   A = FLASH_ATTN_EXT(q, k, v)       -> VIEW -> CONT -> RESHAPE
+//   B = FLASH_ATTN_EXT(q, k_ip, v_ip) -> VIEW -> CONT -> RESHAPE -> SCALE(ip_scale)
+//   ADD(A, B)
+// matched from A's flash node: the same q node, no masks, every link of both chains read by the next one only and none of them a graph output, nothing but
+// views between the nodes of each chain, and the shapes k_flash_short_ip takes.  (Where the operands lie is the caller's concern.)
+struct IpAttnMatch {
+    int fa = -1, va = -1, ca = -1, ra = -1;  // A: flash, VIEW, CONT, RESHAPE
+    int fb = -1, vb = -1, cb = -1, rb = -1;  // B
+    int sc = -1, add = -1;
+    int qtwin[4] = {-1, -1, -1, -1};  // B's own head-major copy of the same projection (RESHAPE, PERMUTE, CONT, RESHAPE), when it has one
+    std::vector<int> chain() const {
+        std::vector<int> c{fa, va, ca, ra, fb, vb, cb, rb, sc, add};
+        for (int t : qtwin)
+            if (t >= 0) c.push_back(t);
+        return c;
+    }
+};
+// ggml_ext_attention_ext splits the heads of its q argument itself (ggml_extend.hpp:1373-1376), so the second attention of an IP-Adapter attn2 reads its OWN
+// RESHAPE [d,H,L,N] -> PERMUTE(0,2,1,3) -> CONT -> RESHAPE [d,L,H*N] of the one to_q output: the same values as the first attention's q, in a second buffer.
+// qa / qb: the tensors the two flash nodes read.  True when both are such copies of one tensor and B's copy feeds nothing but its flash node; tw = B's four nodes
+static bool q_twin_of(const GInfo& gi, const ggml_tensor* qa, const ggml_tensor* qb, int fb, int tw[4]) {
+    const ggml_tensor* t[2][4];
+    const ggml_tensor* q2[2] = {qa, qb};
+    for (int s = 0; s < 2; ++s) {
+        const ggml_tensor* r2 = q2[s];
+        if (!r2 || xop(r2) != GGML_OP_RESHAPE) return false;
+        const ggml_tensor* ct = r2->src[0];
+        if (!ct || xop(ct) != GGML_OP_CONT || !is_f32(ct) || !contig(ct)) return false;
+        const ggml_tensor* pm = ct->src[0];
+        if (!pm || xop(pm) != GGML_OP_PERMUTE) return false;
+        const ggml_tensor* r1 = pm->src[0];
+        if (!r1 || xop(r1) != GGML_OP_RESHAPE || !r1->src[0]) return false;
+        t[s][0] = r1;
+        t[s][1] = pm;
+        t[s][2] = ct;
+        t[s][3] = r2;
+    }
+    if (t[0][0]->src[0] != t[1][0]->src[0]) return false;
+    for (int k = 0; k < 4; ++k) {
+        for (int a = 0; a < 4; ++a)
+            if (t[0][k]->ne[a] != t[1][k]->ne[a] || t[0][k]->nb[a] != t[1][k]->nb[a]) return false;
+        tw[k] = gi.idx(t[1][k]);
+        if (tw[k] < 0) return false;
+    }
+    for (int a = 0; a < 4; ++a)
+        if (t[0][1]->op_params[a] != t[1][1]->op_params[a]) return false;
+    return gi.sole(tw[0]) == tw[1] && gi.sole(tw[1]) == tw[2] && gi.sole(tw[2]) == tw[3] && gi.sole(tw[3]) == fb;
+}
+static bool match_ip_attn(const GInfo& gi, int fa, IpAttnMatch& m) {
+    if (!g_opt.fusion || !g_opt.fuse_ip_attn) return false;
+    const ggml_tensor* a = gi.node(fa);
+    if (xop(a) != GGML_OP_FLASH_ATTN_EXT || a->src[3]) return false;
+    m.fa = fa;
+    if (!flash_view_cont(gi, fa, m.va, m.ca)) return false;
+    m.ra = gi.sole(m.ca);
+    if (m.ra < 0 || xop(gi.node(m.ra)) != GGML_OP_RESHAPE) return false;
+    m.add = gi.sole(m.ra);
+    if (m.add < 0 || xop(gi.node(m.add)) != GGML_OP_ADD || gi.node(m.add)->src[0] != gi.node(m.ra)) return false;  // ADD(A, B), not ADD(B, A)
+    const ggml_tensor* add = gi.node(m.add);
+    m.sc = gi.idx(add->src[1]);
+    if (m.sc < 0 || xop(gi.node(m.sc)) != GGML_OP_SCALE || gi.sole(m.sc) != m.add) return false;
+    m.rb = gi.idx(gi.node(m.sc)->src[0]);
+    if (m.rb < 0 || xop(gi.node(m.rb)) != GGML_OP_RESHAPE || gi.sole(m.rb) != m.sc) return false;
+    m.cb = gi.idx(gi.node(m.rb)->src[0]);
+    if (m.cb < 0 || xop(gi.node(m.cb)) != GGML_OP_CONT || gi.sole(m.cb) != m.rb) return false;
+    m.vb = gi.idx(gi.node(m.cb)->src[0]);
+    if (m.vb < 0 || xop(gi.node(m.vb)) != GGML_OP_VIEW) return false;
+    m.fb = gi.idx(gi.node(m.vb)->src[0]);
+    if (m.fb < 0 || m.fb <= m.ra || xop(gi.node(m.fb)) != GGML_OP_FLASH_ATTN_EXT) return false;
+    const ggml_tensor* b = gi.node(m.fb);
+    int vb = -1, cb = -1;
+    if (b->src[3] || !flash_view_cont(gi, m.fb, vb, cb) || vb != m.vb || cb != m.cb) return false;
+    if (b->src[0] != a->src[0] && !q_twin_of(gi, a->src[0], b->src[0], m.fb, m.qtwin)) return false;  // the same q: one node, or two head-major copies of one projection
+    const std::vector<int> ch = m.chain();
+    if (!gi.only_noops_between(m.fa, m.ra, ch) || !gi.only_noops_between(m.fb, m.add, ch)) return false;
+    const ggml_tensor *q = a->src[0], *k = a->src[1], *v = a->src[2], *ki = b->src[1], *vi = b->src[2];
+    if (!flash_attn_ip_shape_ok(q->ne[0], v->ne[0], q->ne[1], k->ne[1], ki->ne[1])) return false;
+    if (ggml_abi_op_param_f32(a, 0) != ggml_abi_op_param_f32(b, 0)) return false;  // one softmax scale (it sits in both K images)
+    // all operands as the reference builds them: f32 d-contiguous Q rows, f16 d-contiguous K / V of the same head count, 16-byte aligned rows
+    auto kv_ok = [&](const ggml_tensor* t, int64_t L) {
+        return t->type == GGML_TYPE_F16 && t->nb[0] == 2 && t->ne[0] == q->ne[0] && t->ne[1] == L && t->ne[2] == q->ne[2] && t->ne[3] == 1 && t->nb[1] % 16 == 0 && t->nb[2] % 16 == 0 &&
+               aligned16(t->data);
+    };
+    if (!is_f32(q) || !contig(q) || q->ne[3] != 1 || !aligned16(q->data) || !kv_ok(k, k->ne[1]) || !kv_ok(v, k->ne[1]) || !kv_ok(ki, ki->ne[1]) || !kv_ok(vi, ki->ne[1])) return false;
+    const ggml_tensor* ct = gi.node(m.ca);
+    auto same_shape = [](const ggml_tensor* x, const ggml_tensor* y) { return x->ne[0] == y->ne[0] && x->ne[1] == y->ne[1] && x->ne[2] == y->ne[2] && x->ne[3] == y->ne[3]; };
+    if (!is_f32(add) || !contig(add) || !same_shape(add, gi.node(m.ra)) || !same_shape(add, gi.node(m.sc)) || ggml_abi_nelements(ct) != ggml_abi_nelements(add)) return false;
+    return (int64_t)q->ne[1] * std::max<int64_t>((int64_t)q->nb[1], (int64_t)add->nb[1]) < (int64_t)0x7ff00000;
+}
+
+// The f32 head-major CONT `cont` (head dim hd) is the Q operand of a FLASH_ATTN_EXT node and nothing else reads it (ggml_extend.hpp:1373-1376, 1437): the projection
+// GEMM may store it as an f16 image in the arena instead (option fuse_q16).  Returns that flash node (the first of the two of an IP-Adapter pair that read one Q
+// node), *qview = the RESHAPE it reads; -1 otherwise.  ONE predicate for the decision to store the image and for the twin handling that depends on it.
+static int q16_flash_reader(const GInfo& gi, int cont, int64_t hd, int* qview) {
+    if (!g_opt.fuse_q16 || hd % 8 != 0) return -1;
+    const int c1 = gi.sole(cont);
+    if (c1 < 0 || xop(gi.node(c1)) != GGML_OP_RESHAPE) return -1;
+    int c2 = gi.sole(c1);
+    if (c2 < 0 && gi.consumers[c1].size() == 2 && !(gi.node(c1)->flags & GGML_TENSOR_FLAG_OUTPUT)) {
+        // an IP-Adapter attn2 on one Q node: the two flash nodes of the pair read it and nothing else does.  One launch reads it when the pair fuses; if the
+        // operands' placement refuses that later, each node finds the image on its own (Builder::q16 is keyed by the tensor they both read)
+        const int f0 = std::min(gi.consumers[c1][0], gi.consumers[c1][1]), f1 = std::max(gi.consumers[c1][0], gi.consumers[c1][1]);
+        IpAttnMatch im;
+        if (match_ip_attn(gi, f0, im) && im.fb == f1) c2 = f0;
+    }
+    if (c2 < 0 || xop(gi.node(c2)) != GGML_OP_FLASH_ATTN_EXT || gi.node(c2)->src[0] != gi.node(c1) || gi.node(c2)->src[3] || !contig(gi.node(c1)) || gi.node(c1)->ne[0] != hd ||
+        !flash_attn_supported(hd, gi.node(c2)->src[2]->ne[0]))
+        return -1;
+    if (qview) *qview = c1;
+    return c2;
+}
+
 bool linear_fast_ok(const ggml_tensor* n) {
     const ggml_tensor* w = n->src[0];
     const ggml_tensor* x = n->src[1];
@@ -941,8 +1069,21 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     // the projection GEMM stores straight into the CONT (f32) or CPY (f16) buffer in head-major order
     int hm_d = 0, hm_H = 0, hm_L = 0;
     bool hm_f16 = false;
+    IpAttnMatch q_ip;  // to_q of an IP-Adapter attn2 whose two attentions fuse: both head-major copies of this output are served by ONE f16 image
+    bool q_ip_twin = false;
     if (g_opt.fusion) {
-        const int j1 = gi.sole(i);
+        int j1 = gi.sole(i);
+        if (j1 < 0 && g_opt.fuse_q16 && gi.consumers[i].size() == 2 && !(n->flags & GGML_TENSOR_FLAG_OUTPUT)) {
+            const int r0 = std::min(gi.consumers[i][0], gi.consumers[i][1]);
+            int f = r0;  // RESHAPE -> PERMUTE -> CONT -> RESHAPE -> FLASH_ATTN_EXT
+            for (int hop = 0; hop < 4 && f >= 0; ++hop) f = gi.sole(f);
+            const int p0 = gi.sole(r0), ct0 = p0 >= 0 ? gi.sole(p0) : -1;  // the first copy's CONT: what the head-major GEMM writes
+            if (f >= 0 && ct0 >= 0 && xop(gi.node(ct0)) == GGML_OP_CONT && is_f32(gi.node(ct0)) && match_ip_attn(gi, f, q_ip) &&
+                q_ip.qtwin[0] == std::max(gi.consumers[i][0], gi.consumers[i][1]) && q16_flash_reader(gi, ct0, gi.node(r0)->ne[0], nullptr) == f) {
+                j1        = r0;
+                q_ip_twin = true;
+            }
+        }
         const int j2 = (j1 >= 0 && xop(gi.node(j1)) == GGML_OP_RESHAPE) ? gi.sole(j1) : -1;
         const int j3 = (j2 >= 0 && xop(gi.node(j2)) == GGML_OP_PERMUTE) ? gi.sole(j2) : -1;
         if (j3 >= 0 && xop(gi.node(j3)) == GGML_OP_CONT && is_f32(gi.node(j3)) && contig(gi.node(j3))) {
@@ -971,6 +1112,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
             }
         }
     }
+    if (hm_d == 0) q_ip_twin = false;  // not stored head-major: both copies run as the nodes they are
     if (g_opt.fusion && hm_d == 0) {
         // [RESHAPE] -> ADD bias
         int j = gi.sole(last);
@@ -1288,17 +1430,13 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         const int hd = hm_d, hH = hm_H, hL = hm_L;
         // the f32 CONT is the Q operand of a FLASH_ATTN_EXT node and nothing else reads it (ggml_extend.hpp:1373-1376, 1437): store it as an
         // f16 head-major image in the arena instead — the kernel rounds Q to f16 anyway; half the bytes written here and read there
-        int qflash = -1, qview = -1;
-        if (!f16o && g_opt.fuse_q16 && hd % 8 == 0) {
-            const int c1 = gi.sole(last);
-            const int c2 = (c1 >= 0 && xop(gi.node(c1)) == GGML_OP_RESHAPE) ? gi.sole(c1) : -1;
-            if (c2 >= 0 && xop(gi.node(c2)) == GGML_OP_FLASH_ATTN_EXT && gi.node(c2)->src[0] == gi.node(c1) && !gi.node(c2)->src[3] && contig(gi.node(c1)) &&
-                gi.node(c1)->ne[0] == hd && flash_attn_supported(hd, gi.node(c2)->src[2]->ne[0])) {
-                qflash = c2;
-                qview  = c1;
-            }
-        }
+        int qview        = -1;
+        const int qflash = f16o ? -1 : q16_flash_reader(gi, last, hd, &qview);
         const bool groupable = B.hm_grouping && !ep.residual && !ep.gate && !ep.gelu && !ep.chan_add;
+        if (q_ip_twin) {  // (taken only where q16_flash_reader said yes for this very CONT: qflash >= 0)
+            B.q_alias[gi.node(q_ip.qtwin[3])] = gi.node(qview);
+            for (int t : q_ip.qtwin) gi.done[t] = 1;
+        }
         if (qflash >= 0) {
             const size_t qoff        = B.alloc((size_t)tokens * M * 2);
             B.q16[gi.node(qview)]    = qoff;
@@ -1563,6 +1701,9 @@ void plan_hoisted_kv(Builder& B, hipStream_t s) {
         if (!((f->src[1] == gi.node(j5)) != (f->src[2] == gi.node(j5))) || f->src[0] == gi.node(j5)) continue;  // exactly one of K, V
         const ggml_tensor* r4 = gi.node(j1);
         const ggml_tensor* w  = n->src[0];
+        // plan_linear stores a projection head-major (and so lets it be captured below) from 32 tokens per image on: the 4 .. 16 image tokens of an IP-Adapter
+        // (to_k_ip / to_v_ip read a graph input like to_k / to_v do) stay at their graph position, on the launches such a short projection had before
+        if (r4->ne[2] < 32) continue;
         groups[Key{x, (int)w->type, w->ne[0], w->ne[1], r4->ne[0], r4->ne[1], r4->ne[2]}].push_back(j);
     }
     for (auto& kv : groups) {
@@ -2977,10 +3118,12 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
             return true;
         }
         case GGML_OP_FLASH_ATTN_EXT: {
-            View4 q = view_of(n->src[0]), k = view_of(n->src[1]), v = view_of(n->src[2]);
+            const auto qal         = B.q_alias.find(n->src[0]);
+            const ggml_tensor* qsrc = qal != B.q_alias.end() ? qal->second : n->src[0];
+            View4 q = view_of(qsrc), k = view_of(n->src[1]), v = view_of(n->src[2]);
             float* dst       = (float*)n->data;
             const float sc   = ggml_abi_op_param_f32(n, 0);
-            const auto q16it = B.q16.find(n->src[0]);
+            const auto q16it = B.q16.find(qsrc);
             const bool q16   = q16it != B.q16.end();
             const size_t q16off = q16 ? q16it->second : 0;
             if (q16) {  // same [d, L, H*N] shape, f16 elements; the address is resolved at launch (the arena may still grow while planning)
@@ -3013,6 +3156,86 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
             fo.dst  = dst;
             fo.nb_q = nbq;
             fo.nb_h = nbh;
+            // IP-Adapter attn2 (match_ip_attn): this node, the attention of the same q onto the image keys, the SCALE and the ADD as ONE launch that writes the ADD's
+            // result.  It runs at the SECOND flash node's position (its K / V are projected between the two chains), so whatever this node reads from the graph buffer
+            // has to survive until there, and the ADD's block — written ahead of its position — must not be one of the five operands' (the allocator recycles
+            // the block of a tensor whose last reader is a flash node for the next allocation of its size).  Either refusal is counted in flash_out_alias and the
+            // nodes run plain, on the launches they had before.
+            if (IpAttnMatch im; match_ip_attn(gi, i, im)) {
+                const ggml_tensor* fb  = gi.node(im.fb);
+                const ggml_tensor* add = gi.node(im.add);
+                View4 ki = view_of(fb->src[1]), vi = view_of(fb->src[2]);
+                const auto kimv = B.moved.find(fb->src[1]), vimv = B.moved.find(fb->src[2]);
+                const bool kimoved = kimv != B.moved.end(), vimoved = vimv != B.moved.end();
+                const size_t kioff = kimoved ? kimv->second : 0, vioff = vimoved ? vimv->second : 0;
+                if (kimoved) ki.data = nullptr;
+                if (vimoved) vi.data = nullptr;
+                auto kifix = [=](View4 kk) {
+                    if (kimoved) kk.data = PP->arena + kioff;
+                    return kk;
+                };
+                auto vifix = [=](View4 vv) {
+                    if (vimoved) vv.data = PP->arena + vioff;
+                    return vv;
+                };
+                const std::vector<int> ch = im.chain();
+                const bool to16 = all_consumers_gemm16(gi, im.add, false);
+                const ggml_tensor* ops[5] = {n->src[0], n->src[1], n->src[2], fb->src[1], fb->src[2]};
+                const bool in_arena[5]    = {q16, kmoved, vmoved, kimoved, vimoved};
+                bool refused = false;
+                for (int a = 0; a < 3 && !refused; ++a)  // the first chain's operands, read (im.fb - i) nodes later than the graph says
+                    if (!in_arena[a]) {
+                        const ggml_tensor* root = ops[a]->view_src ? ops[a]->view_src : ops[a];
+                        refused = B.clobbered_between(i, im.fb, root->data, ggml_abi_nbytes(root), ch) || B.clobbered_between(i, im.fb, ops[a]->data, ggml_abi_nbytes(ops[a]), ch);
+                    }
+                if (!to16)
+                    for (int a = 0; a < 5 && !refused; ++a)
+                        if (!in_arena[a]) {
+                            const ggml_tensor* root = ops[a]->view_src ? ops[a]->view_src : ops[a];
+                            refused = overlaps(add->data, ggml_abi_nbytes(add), root->data, ggml_abi_nbytes(root)) || overlaps(add->data, ggml_abi_nbytes(add), ops[a]->data, ggml_abi_nbytes(ops[a]));
+                        }
+                const ggml_tensor* vw = gi.node(im.va);
+                const int64_t d = vw->ne[0], H = vw->ne[1], Lq = vw->ne[2], Nimg = vw->ne[3], C = d * H;
+                const float ipsc = ggml_abi_op_param_f32(gi.node(im.sc), 0);
+                if (getenv("GGML_MI355X_PLAN_TRACE"))
+                    fprintf(stderr, "[plan flash ip] nodes %d + %d of %d (view %d): d %lld H %lld Lq %lld N %lld Lk %lld Lk_ip %lld ip_scale %g -> %s; q16 %d moved k %d v %d k_ip %d v_ip %d\n", i,
+                            im.fb, gi.g->n_nodes, (int)gi.is_view, (long long)d, (long long)H, (long long)Lq, (long long)Nimg, (long long)k.ne[1], (long long)ki.ne[1], (double)ipsc,
+                            refused ? "refused (operand placement): plain nodes" : to16 ? "f16 operand image" : "f32 final layout", (int)q16, (int)kmoved, (int)vmoved, (int)kimoved,
+                            (int)vimoved);
+                if (refused) {
+                    STAT(flash_out_alias)++;
+                } else {
+                    Planner* P = B.P;
+                    if (to16) {
+                        const int64_t ld = rup64(C);
+                        const size_t off = B.alloc((size_t)Nimg * Lq * ld * 2);
+                        if (ld != C) B.emit_at(im.fb, i, [=](hipStream_t st) { (void)hipMemsetAsync(P->arena + off, 0, (size_t)Nimg * Lq * ld * 2, st); });
+                        B.emit_at(im.fb, i, [=](hipStream_t st) {
+                            FlashOut f2;
+                            f2.H     = (int)H;
+                            f2.dst16 = P->arena + off;
+                            f2.ld16  = ld;
+                            launch_flash_attn_ip(st, f2, qfix(q), kfix(k), vfix(v), kifix(ki), vifix(vi), sc, ipsc);
+                        });
+                        B.packed[add] = Packed{off, ld, false};
+                    } else {
+                        float* adst = (float*)add->data;
+                        B.emit_at(im.fb, i, [=](hipStream_t st) {
+                            FlashOut f2;
+                            f2.dst  = adst;
+                            f2.H    = (int)H;
+                            f2.nb_q = C * 4;
+                            f2.nb_h = d * 4;
+                            f2.nb_n = Lq * C * 4;
+                            launch_flash_attn_ip(st, f2, qfix(q), kfix(k), vfix(v), kifix(ki), vifix(vi), sc, ipsc);
+                        });
+                    }
+                    for (int c : ch) gi.done[c] = 1;
+                    STAT(fused_attention)++;
+                    STAT(fused_ip_attn)++;
+                    return true;
+                }
+            }
             // -> VIEW [d,H,Lq,N] -> CONT [C,Lq,N] (ggml_extend.hpp:1446-1455, 1481-1482): write the final layout directly
             if (g_opt.fusion) {
                 const int j1 = gi.sole(i);
@@ -4354,6 +4577,7 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     o->flash_qb2_launches     = flash_attn_variant_launches(FLASH_VAR_QB2);
     o->flash_mslot_launches   = flash_attn_variant_launches(FLASH_VAR_MSLOT);
     o->flash_generic_launches = flash_attn_variant_launches(FLASH_VAR_GENERIC);
+    o->flash_short_ip_launches = flash_attn_variant_launches(FLASH_VAR_SHORT_IP);
     // ... and where the elementwise launchers choose theirs: the ew_* fields lie in the order of EwRoute
     static_assert(offsetof(ggml_backend_mi355x_stats, ew_tile_merge_v1) - offsetof(ggml_backend_mi355x_stats, ew_bin_same) == (EW_ROUTE_COUNT - 1) * sizeof(int64_t),
                   "ggml_backend_mi355x_stats: one ew_* field per EwRoute, in its order");
@@ -4407,6 +4631,7 @@ const OptionRow g_option_table[] = {
     OPT(fuse_tile_merge),  // MUL -> MUL -> { ADD in place | CPY } x k of a VAE tile batch's overlap merge as one gather launch (k_tile_merge)
     OPT(fuse_model_input),  // [MUL ->] [RESHAPE -> REPEAT -> RESHAPE ->] CONCAT(dim 2) with the [REPEATed] concat latent of an inpaint / pix2pix UNet as one launch (k_model_input)
     OPT(fuse_guidance3),  // the six nodes of the three-conditioning CFG combine as one launch (k_guidance3)
+    OPT(fuse_ip_attn),  // the two attentions of an IP-Adapter attn2 (text keys, image keys) + SCALE + ADD as one launch of k_flash_short_ip
     OPT(fuse_joint_qkv),
     OPT(fuse_ln_reduce),
     OPT(jit_qimages),

@@ -683,8 +683,34 @@ struct sdm_ctx_t {
         }
     };
     std::unique_ptr<TileState> tstate[3];  // decode, encode, sd_tiling_blend
+    // IP-Adapter (sd_ip_adapter_init): to_k_ip / to_v_ip of every attn2 and the image projection, in a weight buffer of their own — the resident weights stay untouched
+    Runner ip_runner;
+    ImageProjModel ip_proj;
+    bool ip_ready = false;
+    int64_t ip_dim = 0, ip_clip_dim = 0, ip_num_tokens = 0;
+    // sd_set_ip_adapter: the image tokens of the sampling entries, [ip_dim, ip_set_n] each — `ip_tokens` for the cond branch, `ip_uncond` for every other branch
+    // (uncond, img_uncond: stable-diffusion.cpp:2829-2843); empty = no adapter in the samplers
+    std::vector<float> ip_tokens, ip_uncond;
+    int64_t ip_set_n  = 0;
+    float ip_strength = 0.f;
+    bool ip_active() const { return ip_ready && ip_set_n > 0 && ip_strength != 0.f; }
+    // K rows for a model batch whose K branches per image are adjacent (cond first, or `first_uncond` on the uncond rank of a CFG-pair exchange): [ip_dim, ip_set_n, K]
+    std::vector<float> ip_rows(int K, bool first_uncond = false) const {
+        std::vector<float> r;
+        for (int j = 0; j < K; ++j) {
+            const std::vector<float>& t = (j == 0 && !first_uncond) ? ip_tokens : ip_uncond;
+            r.insert(r.end(), t.begin(), t.end());
+        }
+        return r;
+    }
+    // the tokens of the forward the host loop is about to run (HostDenoise sets it around its calls; sd_unet_forward / _concat carry no token arguments)
+    struct IpCall {
+        const float* data = nullptr;
+        int ip_n          = 0;
+    } ip_call;
     std::vector<Runner*> runners() {
         std::vector<Runner*> v{&unet_runner, &vae_runner};
+        if (ip_ready) v.push_back(&ip_runner);
         if (tae_ready) v.push_back(&tae_runner);
         if (vae_enc_ready) v.push_back(&vae_enc_runner);
         if (te) {
@@ -912,6 +938,7 @@ static NameDialect name_dialect(const sdm_ctx_t* ctx) {
         const UNetConfig& c = ctx->unet.cfg;
         d.unet_levels       = (int)c.channel_mult.size();
         d.unet_res_blocks   = c.num_res_blocks;
+        d.sdxl              = c.sdxl;
         d.unet_attn_levels.clear();
         int ds = 1;
         for (int l = 0; l < d.unet_levels; ++l, ds *= 2)
@@ -930,7 +957,12 @@ bool sd_convert_tensor_name(sdm_ctx_t* ctx, const char* name, char* out, size_t 
 
 int64_t sd_load_weights(sdm_ctx_t* ctx, const char* path, int64_t* n_missing, int64_t* n_unused) { return sd_load_weights_prefixed(ctx, path, nullptr, n_missing, n_unused); }
 
+// scope: when given, only the parameters it names take part (the others are neither loaded nor counted as missing): sd_load_ip_adapter
+static int64_t load_weights_scoped(sdm_ctx_t* ctx, const char* path, const char* prefix, int64_t* n_missing, int64_t* n_unused, const std::map<std::string, ggml_tensor*>* scope);
 int64_t sd_load_weights_prefixed(sdm_ctx_t* ctx, const char* path, const char* prefix, int64_t* n_missing, int64_t* n_unused) {
+    return load_weights_scoped(ctx, path, prefix, n_missing, n_unused, nullptr);
+}
+static int64_t load_weights_scoped(sdm_ctx_t* ctx, const char* path, const char* prefix, int64_t* n_missing, int64_t* n_unused, const std::map<std::string, ggml_tensor*>* scope) {
     ModelFile mf;
     if (!read_model_file(path, mf)) {
         set_error(mf.error);
@@ -982,6 +1014,7 @@ int64_t sd_load_weights_prefixed(sdm_ctx_t* ctx, const char* path, const char* p
     std::vector<float> f32;
     std::map<std::string, bool> used;
     for (auto& nt : ctx->all_tensors) {
+        if (scope && !scope->count(nt.first)) continue;
         auto it = dir.find(nt.first);
         if (it == dir.end()) {
             auto ud = undecodable.find(nt.first);
@@ -1369,7 +1402,7 @@ static bool prepare_side_inputs(sdm_ctx_t* ctx, int w, int h, int n, int64_t n_t
 // the denoiser network on an existing latent tensor tx [w,h,c,n]: declares the remaining graph inputs and calls the family's forward
 static ggml_tensor* build_model_call(sdm_ctx_t* ctx, GraphCtx& g, std::vector<HostInput>& in, ggml_tensor* tx, int n, const float* timesteps, const float* context,
                                      int64_t ctx_dim, int64_t n_tokens, int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const ModelSideInputs& si,
-                                     ggml_tensor* c_concat = nullptr) {
+                                     ggml_tensor* c_concat = nullptr, const float* ip_data = nullptr, int64_t n_ip = 0, int ip_n = 0, float ip_scale = 0.f) {
     g.flash_attn    = ctx->params.diffusion_flash_attn;
     g.conv_direct   = ctx->params.diffusion_conv_direct;
     ggml_tensor* tt = ggml_new_tensor_1d(g.ctx, GGML_TYPE_F32, n);
@@ -1384,6 +1417,12 @@ static ggml_tensor* build_model_call(sdm_ctx_t* ctx, GraphCtx& g, std::vector<Ho
         ggml_set_input(ty);
         in.push_back({ty, y, ggml_nbytes(ty)});
     }
+    ggml_tensor* ip_context = nullptr;
+    if (ip_data) {  // image tokens [ip_dim, n_ip, ip_n] (UNet families with an initialised adapter; the callers checked)
+        ip_context = ggml_new_tensor_3d(g.ctx, GGML_TYPE_F32, ctx->ip_dim, n_ip, ip_n);
+        ggml_set_input(ip_context);
+        in.push_back({ip_context, ip_data, ggml_nbytes(ip_context)});
+    }
     if (ctx->is_flux) {
         // guidance [N] and the rotary table are host-built inputs of every call (flux.hpp:1457-1500: pe_vec generated on the CPU and uploaded)
         ggml_tensor* tg = ggml_new_tensor_1d(g.ctx, GGML_TYPE_F32, n);
@@ -1395,14 +1434,32 @@ static ggml_tensor* build_model_call(sdm_ctx_t* ctx, GraphCtx& g, std::vector<Ho
         in.push_back({tp, si.pe().data(), ggml_nbytes(tp)});
         return ctx->flux.forward(g, tx, tt, tc, ty, tg, tp);
     }
-    return ctx->is_dit ? ctx->mmdit.forward(g, tx, tt, tc, ty) : ctx->unet.forward(g, tx, tt, tc, ty, c_concat);
+    return ctx->is_dit ? ctx->mmdit.forward(g, tx, tt, tc, ty) : ctx->unet.forward(g, tx, tt, tc, ty, c_concat, ip_context, ip_scale);
 }
 
 // skip: the joint blocks a skip-layer-guidance forward leaves out (MMDiT only; NULL / empty = the whole model)
 static bool unet_forward_skip(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim, int64_t n_tokens,
                               int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, float* out, const std::vector<int>* skip, const float* c_concat = nullptr,
-                              int cc = 0, int concat_n = 0) {
+                              int cc = 0, int concat_n = 0, const float* ip_context = nullptr, int64_t n_ip = 0, int ip_n = 0, float ip_scale = 0.f) {
     Runner& r = ctx->unet_runner;
+    if (!ip_context && ctx->ip_call.data) {  // a sampling forward of the host loop with the context's token state
+        ip_context = ctx->ip_call.data;
+        n_ip       = ctx->ip_set_n;
+        ip_n       = ctx->ip_call.ip_n;
+        ip_scale   = ctx->ip_strength;
+    }
+    if (ip_context && ip_scale != 0.f) {
+        if (!ctx->ip_ready) {
+            set_error("ip_context given, but no IP-Adapter is initialised on this context (sd_ip_adapter_init / sd_load_ip_adapter)");
+            return false;
+        }
+        if (n_ip < 1 || ip_n < 1 || n % ip_n != 0) {
+            set_error("ip_context must hold at least one token, and its batch must be 1 or divide the batch of x");
+            return false;
+        }
+    } else {
+        ip_context = nullptr;  // block.hpp:382: no tokens or a zero scale emit nothing
+    }
     if (ctx->variant != SDM_UNET_PLAIN && !c_concat) {  // never a silent zero-fill of the extra input channels
         set_error("model needs c_concat (an inpaint / pix2pix UNet: sd_unet_forward_concat)");
         return false;
@@ -1429,7 +1486,7 @@ static bool unet_forward_skip(sdm_ctx_t* ctx, const float* x, int w, int h, int 
             in.push_back({tcc, c_concat, ggml_nbytes(tcc)});
         }
         g.skip_layers = skip;
-        return build_model_call(ctx, g, in, tx, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, si, tcc);
+        return build_model_call(ctx, g, in, tx, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, si, tcc, ip_context, n_ip, ip_n, ip_scale);
     };
     char sig[256];
     int so = snprintf(sig, sizeof(sig), "fwd %d %d %d %d %lld %lld %lld %lld %lld %d", w, h, c, n, (long long)ctx_dim, (long long)n_tokens, (long long)ctx_n,
@@ -1438,11 +1495,13 @@ static bool unet_forward_skip(sdm_ctx_t* ctx, const float* x, int w, int h, int 
         for (int l : *skip)
             if (so < (int)sizeof(sig) - 8) so += snprintf(sig + so, sizeof(sig) - so, " s%d", l);
     if (c_concat && so < (int)sizeof(sig) - 24) so += snprintf(sig + so, sizeof(sig) - so, " cc%d n%d", cc, concat_n);
+    if (ip_context && so < (int)sizeof(sig) - 48) so += snprintf(sig + so, sizeof(sig) - so, " ip%lld n%d s%a", (long long)n_ip, ip_n, (double)ip_scale);  // the scale is a node parameter
     std::vector<const void*> ptrs{x};
     if (c_concat) ptrs.push_back(c_concat);  // (the order the builder declares its inputs in)
     ptrs.push_back(timesteps);
     ptrs.push_back(context);
     if (y) ptrs.push_back(y);
+    if (ip_context) ptrs.push_back(ip_context);
     if (ctx->is_flux) {
         ptrs.push_back(si.guidance.data());
         ptrs.push_back(si.pe().data());
@@ -1469,6 +1528,171 @@ bool sd_unet_forward_concat(sdm_ctx_t* ctx, const float* x, int w, int h, int c,
         return false;
     }
     return unet_forward_skip(ctx, x, w, h, c, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, out, nullptr, c_concat, cc, concat_n);
+}
+// ---- IP-Adapter (src/model/adapter/ip_adapter.hpp, block.hpp:307-393) -----------------------------------------------
+// to_k_ip / to_v_ip of every attn2 plus the ImageProjModel, synthetic weights from the seeded initialiser (a file's values are bound afterwards by name like any other parameter)
+bool sd_ip_adapter_init(sdm_ctx_t* ctx, int64_t ip_dim, int64_t clip_dim, int64_t num_tokens, uint64_t weight_seed) {
+    if (ctx->is_dit) {
+        set_error("sd_ip_adapter_init: the IP-Adapter exists for the UNet families (SD15, SDXL and their tiny forms) only");
+        return false;
+    }
+    if (ip_dim < 1 || clip_dim < 1 || num_tokens < 1) {
+        set_error("sd_ip_adapter_init: ip_dim, clip_dim and num_tokens must be positive");
+        return false;
+    }
+    if (ctx->ip_ready) {
+        if (ip_dim == ctx->ip_dim && clip_dim == ctx->ip_clip_dim && num_tokens == ctx->ip_num_tokens) return true;
+        set_error("sd_ip_adapter_init: an adapter with other dimensions (ip_dim " + std::to_string(ctx->ip_dim) + ", clip_dim " + std::to_string(ctx->ip_clip_dim) + ", " +
+                  std::to_string(ctx->ip_num_tokens) + " tokens) is initialised on this context already");
+        return false;
+    }
+    Runner& r        = ctx->ip_runner;
+    r.backend        = ctx->backend;
+    r.ps.linear_type = (ggml_type)ctx->params.wtype;
+    r.graph_size     = 256;
+    ctx->unet.init_ip_adapter(r.ps, ip_dim);
+    ctx->ip_proj.init(r.ps, "ip_adapter.image_proj.", clip_dim, ip_dim, num_tokens);
+    if (!r.alloc_weights(weight_seed)) {
+        ctx->unet.drop_ip_adapter();  // no attn2 may claim projections that have no buffer
+        set_error("IP-Adapter weight buffer allocation failed");
+        return false;
+    }
+    for (auto& sp : r.ps.specs) ctx->all_tensors.push_back({sp.name, sp.tensor});
+    ctx->stats.weight_bytes += ggml_backend_buffer_get_size(r.weights);
+    ctx->ip_dim        = ip_dim;
+    ctx->ip_clip_dim   = clip_dim;
+    ctx->ip_num_tokens = num_tokens;
+    ctx->ip_ready      = true;
+    ctx->unet_runner.drop_cache();  // a cached forward graph was built without the adapter's nodes
+    return true;
+}
+// An adapter file ("ip_adapter.<idx>.to_{k,v}_ip.weight", "image_proj.{proj,norm}.*"; names converted by ip_adapter_to_ldm): the dimensions are read from its shapes as
+// IPAdapterRunner reads them (ip_adapter.hpp:159-175) — ip_dim = to_k_ip's input width, clip_dim = proj's, num_tokens = proj's rows / norm's width — the adapter is
+// initialised from them if it is not yet, and the file's tensors are bound to the adapter's parameters only.  Returns the number loaded, -1 on error.
+int64_t sd_load_ip_adapter(sdm_ctx_t* ctx, const char* path, int64_t* n_missing, int64_t* n_unused) {
+    if (ctx->is_dit) {
+        set_error("sd_load_ip_adapter: the IP-Adapter exists for the UNet families (SD15, SDXL and their tiny forms) only");
+        return -1;
+    }
+    ModelFile mf;
+    if (!path || !read_model_file(path, mf)) {
+        set_error(path ? mf.error : std::string("sd_load_ip_adapter: NULL path"));
+        return -1;
+    }
+    const NameDialect dialect = name_dialect(ctx);
+    int64_t ip_dim = 0, clip_dim = 0, proj_rows = 0, norm_dim = 0;
+    for (const FileTensor& t : mf.tensors) {
+        const std::string c = canonical_tensor_name(t.name, dialect);
+        const std::string tail = "attn2.to_k_ip.weight";
+        if (c.size() > tail.size() && c.compare(c.size() - tail.size(), tail.size(), tail) == 0 && c.rfind("model.diffusion_model.", 0) == 0) ip_dim = t.ne[0];
+        if (c == "ip_adapter.image_proj.proj.weight") {
+            clip_dim  = t.ne[0];
+            proj_rows = t.ne[1];
+        }
+        if (c == "ip_adapter.image_proj.norm.weight") norm_dim = t.ne[0];
+    }
+    if (ip_dim < 1 || clip_dim < 1 || norm_dim < 1 || proj_rows % norm_dim != 0) {
+        set_error("sd_load_ip_adapter: the file holds no to_k_ip weight of this family's cross-attentions, or no image_proj.proj / image_proj.norm (the Resampler of the \"plus\" adapters is not supported)");
+        return -1;
+    }
+    if (norm_dim != ip_dim) {
+        set_error("sd_load_ip_adapter: image_proj.norm is " + std::to_string(norm_dim) + " wide, to_k_ip reads " + std::to_string(ip_dim));
+        return -1;
+    }
+    if (!sd_ip_adapter_init(ctx, ip_dim, clip_dim, proj_rows / norm_dim, ctx->params.weight_seed)) return -1;
+    return load_weights_scoped(ctx, path, nullptr, n_missing, n_unused, &ctx->ip_runner.ps.by_name);
+}
+bool sd_ip_adapter_info(sdm_ctx_t* ctx, int64_t* ip_dim, int64_t* clip_dim, int64_t* num_tokens) {
+    if (!ctx->ip_ready) return false;
+    if (ip_dim) *ip_dim = ctx->ip_dim;
+    if (clip_dim) *clip_dim = ctx->ip_clip_dim;
+    if (num_tokens) *num_tokens = ctx->ip_num_tokens;
+    return true;
+}
+// CLIP image embeddings [clip_dim, n] -> image tokens [ip_dim, num_tokens, n]: a small graph of its own on the context's backend
+bool sd_ip_adapter_project(sdm_ctx_t* ctx, const float* embeds, int n, float* tokens_out) {
+    if (!ctx->ip_ready) {
+        set_error("sd_ip_adapter_project: no IP-Adapter is initialised on this context (sd_ip_adapter_init)");
+        return false;
+    }
+    if (!embeds || !tokens_out || n < 1) {
+        set_error("sd_ip_adapter_project: bad arguments");
+        return false;
+    }
+    auto build = [&](GraphCtx& g, std::vector<HostInput>& in) {
+        ggml_tensor* te = ggml_new_tensor_2d(g.ctx, GGML_TYPE_F32, ctx->ip_clip_dim, n);
+        ggml_set_input(te);
+        in.push_back({te, embeds, ggml_nbytes(te)});
+        return ctx->ip_proj.forward(g, te);
+    };
+    return ctx->ip_runner.compute(build, tokens_out, (size_t)ctx->ip_dim * ctx->ip_num_tokens * n * sizeof(float));
+}
+// Token state of the sampling entries (sdm_generate_image, sd_sample_latents: host loop, fused branches, device-resident sampler, CFG-pair exchange).  tokens /
+// uncond_tokens [ip_dim, n_tokens]; tokens NULL clears; uncond_tokens NULL = the projection of an all-zero embedding (stable-diffusion.cpp:2206-2207 — not zero when
+// the projection's LayerNorm has a bias), which has the projection's own token count
+bool sd_set_ip_adapter(sdm_ctx_t* ctx, const float* tokens, const float* uncond_tokens, int64_t n_tokens, float strength) {
+    if (!tokens) {
+        ctx->ip_tokens.clear();
+        ctx->ip_uncond.clear();
+        ctx->ip_set_n    = 0;
+        ctx->ip_strength = 0.f;
+        return true;
+    }
+    if (!ctx->ip_ready) {
+        set_error("sd_set_ip_adapter: no IP-Adapter is initialised on this context (sd_ip_adapter_init / sd_load_ip_adapter)");
+        return false;
+    }
+    if (n_tokens < 1 || std::isnan(strength)) {
+        set_error("sd_set_ip_adapter: n_tokens must be positive and the strength a number");
+        return false;
+    }
+    const size_t cnt = (size_t)ctx->ip_dim * (size_t)n_tokens;
+    std::vector<float> un(cnt);
+    if (uncond_tokens) {
+        std::copy(uncond_tokens, uncond_tokens + cnt, un.begin());
+    } else {
+        if (n_tokens != ctx->ip_num_tokens) {
+            set_error("sd_set_ip_adapter: the default uncond tokens are the projection of zeros, " + std::to_string(ctx->ip_num_tokens) + " tokens; with " + std::to_string(n_tokens) +
+                      " cond tokens uncond_tokens must be given");
+            return false;
+        }
+        const std::vector<float> zero((size_t)ctx->ip_clip_dim, 0.f);
+        if (!sd_ip_adapter_project(ctx, zero.data(), 1, un.data())) return false;
+    }
+    ctx->ip_tokens.assign(tokens, tokens + cnt);
+    ctx->ip_uncond   = std::move(un);
+    ctx->ip_set_n    = n_tokens;
+    ctx->ip_strength = strength;
+    return true;
+}
+// project + set, as the reference does with the CLIP image embedding (stable-diffusion.cpp:2187-2215); embeds [clip_dim]
+bool sd_set_ip_adapter_embeds(sdm_ctx_t* ctx, const float* embeds, float strength) {
+    if (!embeds) return sd_set_ip_adapter(ctx, nullptr, nullptr, 0, 0.f);
+    if (!ctx->ip_ready) {
+        set_error("sd_set_ip_adapter_embeds: no IP-Adapter is initialised on this context (sd_ip_adapter_init / sd_load_ip_adapter)");
+        return false;
+    }
+    std::vector<float> tok((size_t)ctx->ip_dim * (size_t)ctx->ip_num_tokens);
+    if (!sd_ip_adapter_project(ctx, embeds, 1, tok.data())) return false;
+    return sd_set_ip_adapter(ctx, tok.data(), nullptr, ctx->ip_num_tokens, strength);
+}
+// sd_unet_forward_concat's argument list (c_concat may be NULL on a plain context) plus the image tokens ip_context [ip_dim, n_ip, ip_n] and their scale
+bool sd_unet_forward_ip(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim, int64_t n_tokens,
+                        int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const float* c_concat, int cc, int concat_n, const float* ip_context, int64_t n_ip,
+                        int ip_n, float ip_scale, float* out) {
+    if (ctx->is_dit) {
+        set_error("sd_unet_forward_ip: the IP-Adapter exists for the UNet families only");
+        return false;
+    }
+    if (ip_context && !ctx->ip_ready) {
+        set_error("sd_unet_forward_ip: no IP-Adapter is initialised on this context (sd_ip_adapter_init)");
+        return false;
+    }
+    if (c_concat && ctx->variant == SDM_UNET_PLAIN) {
+        set_error("sd_unet_forward_ip: the model takes no c_concat (a plain context)");
+        return false;
+    }
+    return unet_forward_skip(ctx, x, w, h, c, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, out, nullptr, c_concat, cc, concat_n, ip_context, n_ip, ip_n, ip_scale);
 }
 int sd_unet_variant(sdm_ctx_t* ctx) { return ctx->variant; }
 int sd_concat_channels(sdm_ctx_t* ctx) { return ctx->concat_channels(); }
@@ -2126,6 +2350,7 @@ struct HostDenoise {
     int n_sigmas = 0;  // sigmas.size() of the trajectory (GuidanceInput::schedule_size)
     std::vector<std::vector<float>> apg_momentum;  // adaptive projected guidance: one momentum buffer per image
     std::vector<float> x2, o2, t2, c2, y2;  // staging of the fused (cond, uncond) pair
+    std::vector<float> ip2;                 // ... and its image tokens [ip_dim, n_ip, K] (sd_set_ip_adapter), assembled on first use
     // step cache (csrc/host/step_cache.hpp): every model forward is wrapped like the reference's run_condition (stable-diffusion.cpp:2779-2795), cond = 0 and
     // uncond = 1; the input is `noised` and the output the model output over the whole device group (nb = 1: the reference's tensors; nb > 1: the means run over
     // the group and there is one decision for all its images)
@@ -2170,9 +2395,20 @@ struct HostDenoise {
         if (!preview(step, true, noised.data())) return false;  // stable-diffusion.cpp:2681-2683
         const bool cached = sc && sc->armed();
         if (cached) sc->begin_call(step, sigma);  // SampleStepCacheDispatcher step_cache(cache_runtime, step, sigma), stable-diffusion.cpp:2688
+        // image tokens (sd_set_ip_adapter): the cond branch sees the tokens, every other branch the uncond tokens (stable-diffusion.cpp:2829-2843); a forward of K
+        // adjacent branches per image takes [tokens, uncond (, uncond)], tiled over the images like its context
+        struct IpScope {
+            sdm_ctx_t* c;
+            IpScope(sdm_ctx_t* c_, const std::vector<float>* rows, int ip_n) : c(c_) {
+                if (rows) c->ip_call = {rows->data(), ip_n};
+            }
+            ~IpScope() { c->ip_call = {}; }
+        };
+        const bool ip_on = ctx->ip_active();
         auto run = [&](const sd_condition_t& cd, float* dst, const float* cat = nullptr) {
             const int cond_id = &cd == &p->uncond ? 1 : 0;
             if (cached && sc_store.before_condition(*sc, cond_id, noised.data(), dst, n)) return true;
+            IpScope ips(ctx, ip_on ? (cond_id == 0 ? &ctx->ip_tokens : &ctx->ip_uncond) : nullptr, 1);
             if (cat ? !sd_unet_forward_concat(ctx, noised.data(), W, H, C, nb, ts.data(), cd.c_crossattn, cd.ctx_dim, cd.n_tokens, 1, cd.c_vector, cd.vector_dim, 1, cat, cc, concat_n, dst)
                     : !sd_unet_forward(ctx, noised.data(), W, H, C, nb, ts.data(), cd.c_crossattn, cd.ctx_dim, cd.n_tokens, 1, cd.c_vector, cd.vector_dim, 1, dst))
                 return false;
@@ -2232,6 +2468,8 @@ struct HostDenoise {
             } else {
                 for (int b = 0; b < nb; ++b)
                     for (int j = 0; j < K; ++j) memcpy(&x2[((size_t)K * b + j) * per], &noised[(size_t)b * per], per * sizeof(float));
+                if (ip_on && ip2.empty()) ip2 = ctx->ip_rows(K);
+                IpScope ips(ctx, ip_on ? &ip2 : nullptr, K);
                 if (!sd_unet_forward_concat(ctx, x2.data(), W, H, C, K * nb, t2.data(), c2.data(), p->cond.ctx_dim, p->cond.n_tokens, K, has_y ? y2.data() : nullptr,
                                             p->cond.vector_dim, K, cc2.data(), cc, concat_n == 1 ? K : K * nb, o2.data()))
                     return false;
@@ -2291,6 +2529,8 @@ struct HostDenoise {
                     memcpy(&x2[(2 * b) * per], &noised[b * per], per * sizeof(float));
                     memcpy(&x2[(2 * b + 1) * per], &noised[b * per], per * sizeof(float));
                 }
+                if (ip_on && ip2.empty()) ip2 = ctx->ip_rows(2);
+                IpScope ips(ctx, ip_on ? &ip2 : nullptr, 2);
                 if (!sd_unet_forward(ctx, x2.data(), W, H, C, 2 * nb, t2.data(), c2.data(), p->cond.ctx_dim, p->cond.n_tokens, 2,
                                      has_y ? y2.data() : nullptr, p->cond.vector_dim, 2, o2.data()))
                     return false;
@@ -2702,6 +2942,9 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
     }
     // c_concat (inpaint / pix2pix UNets): resident for the trajectory, uploaded once — [W,H,cc,K] when the batch shares it (row j is branch j's: `concat` for cond and
     // uncond, `img_uncond_concat` on the img_uncond seat; the model graph's REPEAT tiles it over the images) or [W,H,cc,K*nb] per image, in the order of the model batch
+    // image tokens (sd_set_ip_adapter): one [ip_dim, n_ip, K] input, row j is branch j's — assembled once per trajectory, tiled over the images like the context
+    const bool ip_on             = !ctx->is_dit && ctx->ip_active();
+    const std::vector<float> ip2 = ip_on ? ctx->ip_rows(K, pair && ctx->pair_branch == 1) : std::vector<float>();
     const float *cat_host = nullptr, *cat_img_host = nullptr;
     int cat_cc = 0, cat_n = 0;
     group_concat(ctx, b0, nb, cat_host, cat_img_host, cat_cc, cat_n);
@@ -2845,13 +3088,17 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
     if (!prepare_side_inputs(ctx, W, H, n_model, p->cond.n_tokens, has_y, si)) return false;
     std::vector<float> ts(n_model);
     Runner& r = ctx->unet_runner;
-    char step_sig[280];  // every step of the trajectory replays ONE cached graph: only the 8 scalars, the timesteps and the conditioning are re-uploaded
+    char step_sig[360];  // every step of the trajectory replays ONE cached graph: only the 8 scalars, the timesteps and the conditioning are re-uploaded
     int sig_n = snprintf(step_sig, sizeof(step_sig), "step %d %d %d %d cfg%d ea%d %lld %lld y%lld %p pair%d", W, H, C, nb, (int)use_cfg, (int)euler_a + 2 * (int)flow,
                          (long long)p->cond.ctx_dim, (long long)p->cond.n_tokens, (long long)(has_y ? p->cond.vector_dim : -1), (void*)st.x, (int)pair);
     if (cat_dev)  // graphs with a concat input: its width, the branches per image, whether the last seat is img_uncond's, and the resident tensor they name
         snprintf(step_sig + sig_n, sizeof(step_sig) - (size_t)sig_n, " cc%d K%d iu%d pi%d concat%llu", cat_cc, K, (int)gp.use_img_uncond, (int)(cat_n != 1),
                  (unsigned long long)st.concat->serial);
     const std::string update_sig = std::string("update ") + step_sig;
+    if (ip_on) {  // graphs with image tokens: their count and the strength (a node parameter); the tokens themselves are an input
+        const size_t at = strlen(step_sig);
+        snprintf(step_sig + at, sizeof(step_sig) - at, " ip%lld s%a", (long long)ctx->ip_set_n, (double)ctx->ip_strength);
+    }
     const std::string cache_tag  = cc ? " cache" + std::to_string(cc->serial) : std::string();
     const std::string record_sig = std::string("record ") + step_sig + cache_tag;  // the recording variant and the skip-step graph: plans of their own
     const std::string skip_sig   = std::string("skip ") + step_sig + cache_tag;
@@ -2961,7 +3208,7 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
                 // (cat_dev: the model's own graph appends it — [REPEAT over the images,] CONCAT along the channels, unet.hpp:554-559; with the chain above that is
                 // the pattern the MI355X backend runs as one launch of k_model_input)
                 eps = build_model_call(ctx, g, in, xin, n_model, ts.data(), c2.data(), p->cond.ctx_dim, p->cond.n_tokens, ctx_n,
-                                       has_y ? y2.data() : nullptr, p->cond.vector_dim, ctx_n, si, cat_dev);
+                                       has_y ? y2.data() : nullptr, p->cond.vector_dim, ctx_n, si, cat_dev, ip_on ? ip2.data() : nullptr, ctx->ip_set_n, ctx_n, ctx->ip_strength);
                 if (pair) return ggml_cpy(c, ggml_mul(c, eps, S(1)), st.eps);  // weight * eps of this rank's branch; the update follows the exchange
                 if (K > 1) {
                     e3 = ggml_reshape_3d(c, ggml_cont(c, eps), (int64_t)per, K, nb);
@@ -3001,6 +3248,7 @@ static bool sample_group_device(sdm_ctx_t* ctx, const sdm_img_gen_params_t* p, i
         };
         std::vector<const void*> ptrs{sc, ts.data(), c2.data()};
         if (has_y) ptrs.push_back(y2.data());
+        if (ip_on) ptrs.push_back(ip2.data());
         if (ctx->is_flux) {
             ptrs.push_back(si.guidance.data());
             ptrs.push_back(si.pe().data());

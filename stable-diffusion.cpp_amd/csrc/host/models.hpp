@@ -162,9 +162,40 @@ struct UNetModel {
         out_conv.init(ps, prefix + "out.2.", mc, cfg.out_channels, 3, 1, 1);
     }
 
-    // forward — unet.hpp:526-745.  x [W,H,C,N]; timesteps [N]; context [ctx_dim,77,N|1]; y [adm,N|1]; c_concat [W,H,cc,N|1] (inpaint / pix2pix UNets) or NULL
-    ggml_tensor* forward(GraphCtx& g, ggml_tensor* x, ggml_tensor* timesteps, ggml_tensor* context, ggml_tensor* y, ggml_tensor* c_concat = nullptr) const {
+    // IP-Adapter: to_k_ip / to_v_ip on every attn2, in graph order (input, middle, output blocks); the parameters go to the adapter's own store
+    int64_t ip_dim = 0;
+    void init_ip_adapter(ParamStore& ps, int64_t ip_dim_) {
+        ip_dim = ip_dim_;
+        for (auto& lv : input_blocks)
+            if (lv.attn) lv.attn->init_ip(ps, ip_dim);
+        mid1.attn->init_ip(ps, ip_dim);
+        for (auto& lv : output_blocks)
+            if (lv.attn) lv.attn->init_ip(ps, ip_dim);
+    }
+
+    void drop_ip_adapter() {  // the adapter's weight buffer could not be placed: no attn2 keeps projections without storage
+        ip_dim = 0;
+        auto drop = [](SpatialTransformer& st) {
+            for (auto& b : st.blocks) b.attn2.has_ip = false;
+        };
+        for (auto& lv : input_blocks)
+            if (lv.attn) drop(*lv.attn);
+        drop(*mid1.attn);
+        for (auto& lv : output_blocks)
+            if (lv.attn) drop(*lv.attn);
+    }
+
+    // forward — unet.hpp:526-745.  x [W,H,C,N]; timesteps [N]; context [ctx_dim,77,N|1]; y [adm,N|1]; c_concat [W,H,cc,N|1] (inpaint / pix2pix UNets) or NULL;
+    // ip_context [ip_dim, n_ip, N|1] image tokens of an initialised IP-Adapter or NULL, handed to every attn2 through the graph context like the
+    // reference's runner context does (ip_scale == 0 or no tokens: the graph of a context without the adapter)
+    ggml_tensor* forward(GraphCtx& g, ggml_tensor* x, ggml_tensor* timesteps, ggml_tensor* context, ggml_tensor* y, ggml_tensor* c_concat = nullptr,
+                         ggml_tensor* ip_context = nullptr, float ip_scale = 0.f) const {
         ggml_context* c = g.ctx;
+        if (ip_context != nullptr && ip_scale != 0.f && ip_context->ne[2] != x->ne[3]) {
+            ip_context = ggml_repeat(c, ip_context, ggml_new_tensor_3d(c, GGML_TYPE_F32, ip_context->ne[0], ip_context->ne[1], x->ne[3]));
+        }
+        g.ip_context = ip_dim > 0 ? ip_context : nullptr;
+        g.ip_scale   = ip_scale;
         if (context != nullptr && context->ne[2] != x->ne[3]) {
             context = ggml_repeat(c, context, ggml_new_tensor_3d(c, GGML_TYPE_F32, context->ne[0], context->ne[1], x->ne[3]));
         }

@@ -8,6 +8,7 @@
 // are COMPUTED from the architecture (levels, res-blocks per level, which levels carry attention), so the same code serves SD1.x, SDXL and
 // the tiny test widths.  Only the dialects of the engine's model families are handled (no LoRA / ControlNet / video models).
 #pragma once
+#include <cstdlib>
 #include <string>
 #include <utility>
 #include <vector>
@@ -20,6 +21,7 @@ struct NameDialect {
     int unet_levels = 4, unet_res_blocks = 2;
     std::vector<int> unet_attn_levels{0, 1, 2};  // levels (0 = full resolution) whose blocks carry a SpatialTransformer
     int vae_levels = 4;
+    bool sdxl = false;  // IP-Adapter files number the cross-attentions of SD1.x and SDXL differently (ip_adapter_to_ldm)
 };
 
 namespace nameconv {
@@ -281,11 +283,41 @@ inline std::string dit_diffusers_to_original(const std::string& name, bool flux)
     return name;
 }
 
+// ---- IP-Adapter files (name_conversion.cpp:1307-1344) -----------------------------------------------------------------------------
+// "ip_adapter.<idx>.to_k_ip.weight": idx counts the UNet's attention processors in diffusers order, two per transformer block (attn1 even, attn2 odd), so
+// the cross-attention of the n-th transformer block is 2 n + 1.  The blocks in that order: SD1.x has depth 1 everywhere — input_blocks 1 2 4 5 7 8,
+// output_blocks 3 .. 11, the middle block: 16 indices; SDXL — 11 SpatialTransformers of depths 2 2 10 10 | 10 10 10 2 2 2 | 10 (input 4 5 7 8, output 0 .. 5, middle).
+// "image_proj.*" -> "ip_adapter.image_proj.*".  Names with fewer than four parts and indices outside the table pass through unchanged.
+inline std::string ip_adapter_to_ldm(const std::string& name, bool sdxl) {
+    if (starts_with(name, "image_proj.")) return "ip_adapter." + name;
+    if (!starts_with(name, "ip_adapter.")) return name;
+    const std::vector<std::string> p = split_dots(name);
+    if (p.size() < 4) return name;
+    const int idx = atoi(p[1].c_str());  // (the reference's atoi: "7x" is 7, "x" is 0)
+    struct Blk {
+        const char* sect;
+        int first, count, depth;
+    };
+    static const Blk sd1[]  = {{"input_blocks", 1, 2, 1}, {"input_blocks", 4, 2, 1}, {"input_blocks", 7, 2, 1}, {"output_blocks", 3, 9, 1}, {"middle_block", 1, 1, 1}};
+    static const Blk sdxl_[] = {{"input_blocks", 4, 2, 2}, {"input_blocks", 7, 2, 10}, {"output_blocks", 0, 3, 10}, {"output_blocks", 3, 3, 2}, {"middle_block", 1, 1, 10}};
+    int at = 1;
+    for (const Blk& b : sdxl ? sdxl_ : sd1) {
+        const bool mid = b.sect[0] == 'm';
+        for (int c = 0; c < b.count; ++c)
+            for (int m = 0; m < b.depth; ++m, at += 2)
+                if (at == idx)
+                    return std::string("model.diffusion_model.") + b.sect + (mid ? "" : "." + std::to_string(b.first + c)) + ".1.transformer_blocks." + std::to_string(m) + ".attn2." + p[2] +
+                           "." + p[3];
+    }
+    return name;
+}
+
 }  // namespace nameconv
 
 // file name -> canonical engine name (unchanged when already canonical or not recognised)
 inline std::string canonical_tensor_name(const std::string& raw, const NameDialect& d) {
     using namespace nameconv;
+    if (d.unet_family && (starts_with(raw, "ip_adapter.") || starts_with(raw, "image_proj."))) return ip_adapter_to_ldm(raw, d.sdxl);  // name_conversion.cpp:1351-1353
     const std::string MDM = "model.diffusion_model.", FSM = "first_stage_model.";
     const std::string L = d.unet_family ? "cond_stage_model." : "text_encoders.clip_l.";
     const std::string G = d.unet_family ? "cond_stage_model.1." : "text_encoders.clip_g.";

@@ -60,6 +60,9 @@ struct GraphCtx {
     bool flash_attn        = false;  // sdm_ctx_params_t.diffusion_flash_attn
     bool conv_direct       = false;  // sdm_ctx_params_t.diffusion_conv_direct
     const std::vector<int>* skip_layers = nullptr;  // skip-layer guidance: joint blocks the MMDiT forward leaves out (mmdit.hpp:854-866)
+    // IP-Adapter (GGMLRunnerContext::ip_context / ip_scale, read by every attn2 that has to_k_ip / to_v_ip): image tokens [ip_dim, n_ip, N]
+    ggml_tensor* ip_context = nullptr;
+    float ip_scale          = 0.f;
 };
 
 // ---- ggml_ext_* wrappers (node-for-node) --------------------------------------------------------
@@ -306,12 +309,19 @@ struct FeedForward {
 };
 
 // CrossAttention — block.hpp:307-393
+// IP-Adapter (block.hpp:317-327, 382-389): to_k_ip / to_v_ip (ip_dim -> inner, no bias) exist on attn2 only, and only once an adapter has been
+// initialised on the context (init_ip); without them, or with no image tokens / ip_scale == 0 on the graph context, forward emits today's nodes.
 struct CrossAttention {
-    int64_t n_head = 0;
+    int64_t n_head = 0, inner_dim = 0;
+    std::string name;  // parameter prefix ("...attn2.")
     Linear to_q, to_k, to_v, to_out;
+    Linear to_k_ip, to_v_ip;
+    bool has_ip = false;
     void init(ParamStore& ps, const std::string& prefix, int64_t query_dim, int64_t context_dim, int64_t heads, int64_t d_head) {
         n_head              = heads;
         const int64_t inner = heads * d_head;
+        inner_dim           = inner;
+        name                = prefix;
         to_q.init(ps, prefix + "to_q.", query_dim, inner, false);
         to_k.init(ps, prefix + "to_k.", context_dim, inner, false);
         to_v.init(ps, prefix + "to_v.", context_dim, inner, false);
@@ -322,7 +332,19 @@ struct CrossAttention {
         ggml_tensor* k = to_k.forward(g, context);
         ggml_tensor* v = to_v.forward(g, context);
         x              = ext_attention(g, q, k, v, n_head);
+        if (has_ip && g.ip_context != nullptr && g.ip_scale != 0.0f) {  // block.hpp:382-389
+            ggml_tensor* k_ip = to_k_ip.forward(g, g.ip_context);
+            ggml_tensor* v_ip = to_v_ip.forward(g, g.ip_context);
+            ggml_tensor* x_ip = ext_attention(g, q, k_ip, v_ip, n_head);
+            x                 = ggml_add(g.ctx, x, ggml_scale(g.ctx, x_ip, g.ip_scale));
+        }
         return to_out.forward(g, x);
+    }
+    // the adapter's parameters live in a store of their own (the resident weights are placed already and stay untouched)
+    void init_ip(ParamStore& ps, int64_t ip_dim) {
+        to_k_ip.init(ps, name + "to_k_ip.", ip_dim, inner_dim, false);
+        to_v_ip.init(ps, name + "to_v_ip.", ip_dim, inner_dim, false);
+        has_ip = true;
     }
 };
 
@@ -409,6 +431,31 @@ struct SpatialTransformer {
             x = proj_out_c.forward(g, x);
         }
         return ggml_add(c, x, x_in);
+    }
+    void init_ip(ParamStore& ps, int64_t ip_dim) {
+        for (auto& b : blocks) b.attn2.init_ip(ps, ip_dim);
+    }
+};
+
+// ImageProjModel — src/model/adapter/ip_adapter.hpp:10-32: Linear(clip_dim -> num_tokens * ctx_dim) + bias, reshape to [ctx_dim, num_tokens, N],
+// LayerNorm over ctx_dim.  (The Resampler of the "plus" adapters needs GELU_ERF, which neither this front-end nor the backends implement: out of scope,
+// a caller with plus tokens passes them as tokens directly.)
+struct ImageProjModel {
+    int64_t clip_dim = 0, ctx_dim = 0, num_tokens = 0;
+    Linear proj;
+    LayerNorm norm;
+    void init(ParamStore& ps, const std::string& prefix, int64_t clip_dim_, int64_t ctx_dim_, int64_t num_tokens_) {
+        clip_dim   = clip_dim_;
+        ctx_dim    = ctx_dim_;
+        num_tokens = num_tokens_;
+        proj.init(ps, prefix + "proj.", clip_dim, num_tokens * ctx_dim);
+        norm.init(ps, prefix + "norm.", ctx_dim);
+    }
+    // embeds [clip_dim, N] -> [ctx_dim, num_tokens, N]
+    ggml_tensor* forward(GraphCtx& g, ggml_tensor* embeds) const {
+        ggml_tensor* x = proj.forward(g, embeds);
+        x              = ggml_reshape_3d(g.ctx, x, ctx_dim, num_tokens, embeds->ne[1]);
+        return norm.forward(g, x);
     }
 };
 

@@ -19,6 +19,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "device_utils.h"
@@ -949,8 +950,245 @@ __global__ __launch_bounds__(256, 2) void k_flash_short(FAArgs g) {
         } else {
             FS_PUT(q0 + ro + 4 * hi < g.Lq ? ovoff[nb] : OOR)
         }
-#undef FS_PUT
     }
+}
+
+// =====================================================================================================================================
+// k_flash_short_ip — k_flash_short plus a second, decoupled attention of the same queries onto 1 .. 32 IMAGE keys (IP-Adapter, block.hpp:382-389:
+// x = attn(q, k, v) + ip_scale * attn(q, k_ip, v_ip)), one launch, one read of Q, one write.  A sibling, not more template arguments on k_flash_short: that
+// kernel's instantiations compile to what they compiled to before.  Both softmaxes are one-pass and normalised BEFORE P is packed, so the two
+// attentions share one P V accumulator: o = (P_txt / sum_txt) V_txt + (ip_scale * P_ip / sum_ip) V_ip, each factor rounded to f16 like P_txt is.
+// Registers: the text K / V fragments stay in registers as in k_flash_short; the image keys are one more 32-key block that stays in LDS — its
+// KS K fragments and (up to) four V fragments are read per query block, eight ds_reads next to ~40 MFMAs.  The image scores are made, normalised
+// and packed FIRST (16 score registers -> 8 registers of P_ip), so that they are dead before the 48 text score registers become live; the image
+// P V steps end the MFMA chain.  Padded image keys are masked by the accumulator's initial value like the text keys (negc); image key 0 is never
+// masked (Lk_ip >= 1), so the row max is finite and the row sum >= 1.
+struct FAIpArgs {
+    FAArgs g;  // text operands, Q, output: as k_flash_short reads them
+    const char *k_ip, *v_ip;
+    int64_t kip_nb1, kip_nb2, vip_nb1, vip_nb2;
+    int Lk_ip;
+    float ip_scale;
+};
+template <int DKP, bool QF16, bool OUT16>
+__global__ __launch_bounds__(256, 2) void k_flash_short_ip(FAIpArgs a) {
+    const FAArgs& g = a.g;
+    constexpr int NDV  = 2;
+    constexpr int KS   = DKP / 16;
+    constexpr int KROW = DKP + 8;
+    constexpr int DCH  = DKP / 8;
+    constexpr int NKB  = 3;             // text key blocks of 32
+    constexpr int NKT  = 2 * NKB;       // text P V k-steps of 16 keys
+    constexpr int NK   = 32 * NKB;      // text keys held
+    constexpr int NKA  = NK + 32;       // rows staged: text keys, then the image key block
+    constexpr int VRS  = fa_vtr_stride(NDV);
+    constexpr int VCH  = NDV * 4;
+    constexpr uint32_t OOR = 0x7fffff00u;
+    __shared__ __attribute__((aligned(16))) _Float16 Ks[NKA * KROW];
+    __shared__ __attribute__((aligned(16))) _Float16 Vs[NKA * VRS];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int hi   = lane >> 5;
+    const int hn   = blockIdx.y;
+    const char* kbase  = g.k + (int64_t)hn * g.k_nb2;
+    const char* vbase  = g.v + (int64_t)hn * g.v_nb2;
+    const char* kibase = a.k_ip + (int64_t)hn * a.kip_nb2;
+    const char* vibase = a.v_ip + (int64_t)hn * a.vip_nb2;
+    const half8_t z8   = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int e = threadIdx.x; e < NKA * DCH; e += 256) {
+        const int key = e / DCH, ch = e - key * DCH;
+        half8_t kv    = z8;
+        const bool txt = key < NK;
+        const int kk   = txt ? key : key - NK;
+        if (kk < (txt ? g.Lk : a.Lk_ip) && ch * 8 < g.D) {
+            kv = *(const half8_t*)((txt ? kbase + (int64_t)kk * g.k_nb1 : kibase + (int64_t)kk * a.kip_nb1) + ch * 16);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) kv[j] = (_Float16)((float)kv[j] * g.scale_log2e);
+        }
+        *(half8_t*)&Ks[key * KROW + ch * 8] = kv;
+    }
+    for (int e = threadIdx.x; e < NKA * VCH; e += 256) {
+        const int key = e / VCH, ch = e - key * VCH;
+        half8_t vv    = z8;  // rows beyond Lk / Lk_ip and columns beyond D are zeros: their P is 0, their products must stay finite
+        const bool txt = key < NK;
+        const int kk   = txt ? key : key - NK;
+        if (kk < (txt ? g.Lk : a.Lk_ip) && ch * 8 < g.DV) vv = *(const half8_t*)((txt ? vbase + (int64_t)kk * g.v_nb1 : vibase + (int64_t)kk * a.vip_nb1) + ch * 16);
+        *(half8_t*)&Vs[key * VRS + ch * 8] = vv;
+    }
+    __syncthreads();
+    half8_t kf[NKB][KS], vf[NKT][NDV];
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) kf[kb][ks] = *(const half8_t*)&Ks[(kb * 32 + (lane & 31)) * KROW + ks * 16 + hi * 8];
+    const int vtr_lane = (4 * hi + ((lane & 15) >> 2)) * VRS + ((lane >> 4) & 1) * 16 + 4 * (lane & 3);
+#pragma unroll
+    for (int t = 0; t < NKT; ++t)
+#pragma unroll
+        for (int nb = 0; nb < NDV; ++nb) {
+            const _Float16* p = Vs + vtr_lane + t * 16 * VRS + nb * 32;
+            const half4_t x = lds_read_tr16(p), c = lds_read_tr16(p + 8 * VRS);
+            vf[t][nb] = (half8_t){x[0], x[1], x[2], x[3], c[0], c[1], c[2], c[3]};
+        }
+    // the image block's fragments stay in LDS (nothing writes it after the barrier above): per-lane element offsets
+    const int kip_off = (NK + (lane & 31)) * KROW + hi * 8;
+    const int vip_off = NK * VRS + vtr_lane;
+    // this lane holds query (lane & 31) and, of a key block, the keys (r&3) + 8*(r>>2) + 4*hi: -inf as the accumulator's initial value masks the
+    // text keys >= Lk (last text block only) and the image keys >= Lk_ip
+    float16_t negc, negi;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        negc[r] = (64 + (r & 3) + 8 * (r >> 2) + 4 * hi >= g.Lk) ? -INFINITY : 0.f;
+        negi[r] = ((r & 3) + 8 * (r >> 2) + 4 * hi >= a.Lk_ip) ? -INFINITY : 0.f;
+    }
+    const bool ip2 = a.Lk_ip > 16;  // wave-uniform: image keys 16 .. 31 exist (else their P is zero: the second P V step is skipped)
+
+    // ---- loop-invariant addressing (as k_flash_short)
+    constexpr int QES = QF16 ? 2 : 4;
+    const char* qhead = g.q + (int64_t)hn * g.q_nb2;
+    const auto rsQ = __builtin_amdgcn_make_buffer_rsrc((void*)qhead, 0, (int)min((int64_t)(g.Lq - 1) * g.q_nb1 + (int64_t)g.D * QES, (int64_t)0x7ffffff0), 0x00020000);
+    const int hh = g.H > 0 ? hn % g.H : hn, nn = g.H > 0 ? hn / g.H : 0;
+    char* obytes;
+    int64_t ostride;
+    if (OUT16) {
+        obytes  = (char*)(g.dst16 + (int64_t)nn * g.Lq * g.ld16 + (int64_t)hh * g.DV);
+        ostride = g.ld16 * 2;
+    } else {
+        obytes  = (char*)g.dst + (int64_t)hh * g.dst_nb_h + (int64_t)nn * g.dst_nb_n;
+        ostride = g.dst_nb_q;
+    }
+    constexpr int OES = OUT16 ? 2 : 4;
+    const auto rsO = __builtin_amdgcn_make_buffer_rsrc((void*)obytes, 0, (int)min((int64_t)(g.Lq - 1) * ostride + (int64_t)g.DV * OES, (int64_t)0x7ffffff0), 0x00020000);
+    uint32_t ovoff[NDV];
+#pragma unroll
+    for (int nb = 0; nb < NDV; ++nb) {
+        const int d = nb * 32 + (lane & 31);
+        ovoff[nb]   = d < g.DV ? (uint32_t)(4 * hi) * (uint32_t)ostride + (uint32_t)d * OES : OOR;
+    }
+    const int qwg = 128 * g.qi;
+    constexpr int NQR = QF16 ? KS : 2 * KS;
+    fa_u32x4_t qraw[NQR];
+    {
+        const int q00 = blockIdx.x * qwg + wave * 32;
+        if (q00 < g.Lq) FS_LOADQ(q00)
+    }
+    for (int it = 0; it < g.qi; ++it) {
+        const int q0 = blockIdx.x * qwg + (it * 4 + wave) * 32;  // wave-uniform
+        if (q0 >= g.Lq) break;
+        const bool full = q0 + 32 <= g.Lq;
+        half8_t qf[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            if constexpr (QF16) {
+                qf[ks] = __builtin_bit_cast(half8_t, qraw[ks]);
+            } else {
+                const float4 x = __builtin_bit_cast(float4, qraw[2 * ks]), c = __builtin_bit_cast(float4, qraw[2 * ks + 1]);
+                const half2_t h0 = __builtin_convertvector((float2_t){x.x, x.y}, half2_t), h1 = __builtin_convertvector((float2_t){x.z, x.w}, half2_t);
+                const half2_t h2 = __builtin_convertvector((float2_t){c.x, c.y}, half2_t), h3 = __builtin_convertvector((float2_t){c.z, c.w}, half2_t);
+                qf[ks] = (half8_t){h0[0], h0[1], h1[0], h1[1], h2[0], h2[1], h3[0], h3[1]};
+            }
+        }
+        {
+            const int q1 = q0 + 128;
+            if (it + 1 < g.qi && q1 < g.Lq) FS_LOADQ(q1)
+        }
+        // ---- image keys first: S_ip^T = K_ip Q^T, one-pass softmax, P_ip * ip_scale / sum -> f16
+        // (the offsets pass through an empty asm per block: the reads are loop-invariant, and hoisted out of the loop they would hold the 32 registers this
+        // layout exists to save)
+        int kio = kip_off, vio = vip_off;
+        asm volatile("" : "+v"(kio), "+v"(vio));
+        const _Float16* kip_lane = Ks + kio;
+        const _Float16* vip_lane = Vs + vio;
+        half8_t pi[2];
+        {
+            float16_t si = negi;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) si = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8_t*)(kip_lane + ks * 16), qf[ks], si, 0, 0, 0);
+            float mi = si[0];  // image key 0 (r = 0, hi = 0) is never masked; the other half's partial max is merged below
+#pragma unroll
+            for (int r = 1; r < 16; ++r) mi = __builtin_fmaxf(mi, si[r]);
+            mi = fmaxf(mi, __shfl_xor(mi, 32, 64));
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                si[r] = __builtin_amdgcn_exp2f(si[r] - mi);
+                ps += si[r];
+            }
+            const float invi = a.ip_scale / (ps + __shfl_xor(ps, 32, 64));  // >= one term equal to 1
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int j = 0; j < 8; j += 2) {
+                    const half2_t h2 = __builtin_convertvector((float2_t){si[t * 8 + j] * invi, si[t * 8 + j + 1] * invi}, half2_t);
+                    pi[t][j]     = h2[0];
+                    pi[t][j + 1] = h2[1];
+                }
+        }
+        // pin P_ip here, and keep the text MFMAs behind it: scheduled into the image softmax, both score sets are live at once (the d = 64 f16-Q instantiation spilled)
+        asm volatile("" : "+v"(pi[0]), "+v"(pi[1]));
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- text keys: as k_flash_short
+        float16_t sc[NKB];
+        sc[0] = (float16_t){0};
+        sc[1] = (float16_t){0};
+        sc[2] = negc;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb) sc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[kb][ks], qf[ks], sc[kb], 0, 0, 0);
+        float m = sc[0][0];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            m = __builtin_fmaxf(__builtin_fmaxf(m, sc[0][r]), sc[1][r]);
+            m = __builtin_fmaxf(m, sc[2][r]);
+        }
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        float psum = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                sc[kb][r] = __builtin_amdgcn_exp2f(sc[kb][r] - m);
+                psum += sc[kb][r];
+            }
+        const float inv = 1.0f / (psum + __shfl_xor(psum, 32, 64));
+        half8_t pa[NKT];
+#pragma unroll
+        for (int t = 0; t < NKT; ++t) {
+            const int kb = t >> 1, rb = (t & 1) * 8;
+#pragma unroll
+            for (int j = 0; j < 8; j += 2) {
+                const half2_t h2 = __builtin_convertvector((float2_t){sc[kb][rb + j] * inv, sc[kb][rb + j + 1] * inv}, half2_t);
+                pa[t][j]     = h2[0];
+                pa[t][j + 1] = h2[1];
+            }
+        }
+        float16_t o[NDV];
+#pragma unroll
+        for (int nb = 0; nb < NDV; ++nb) o[nb] = (float16_t){0};
+#pragma unroll
+        for (int t = 0; t < NKT; ++t)
+#pragma unroll
+            for (int nb = 0; nb < NDV; ++nb) o[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa[t], vf[t][nb], o[nb], 0, 0, 0);
+        // ---- the same accumulator takes the image keys: o += P_ip V_ip (fragments from LDS)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            if (t == 1 && !ip2) break;
+#pragma unroll
+            for (int nb = 0; nb < NDV; ++nb) {
+                const _Float16* p = vip_lane + t * 16 * VRS + nb * 32;
+                const half4_t x = lds_read_tr16(p), c = lds_read_tr16(p + 8 * VRS);
+                const half8_t vi = {x[0], x[1], x[2], x[3], c[0], c[1], c[2], c[3]};
+                o[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pi[t], vi, o[nb], 0, 0, 0);
+            }
+        }
+        if (full) {  // wave-uniform: every row of the block exists
+            FS_PUT(ovoff[nb])
+        } else {
+            FS_PUT(q0 + ro + 4 * hi < g.Lq ? ovoff[nb] : OOR)
+        }
+    }
+#undef FS_PUT
 #undef FS_LOADQ
 }
 
@@ -1072,6 +1310,80 @@ void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const
     else
         FA_CASE(160, 5);  // one workgroup per CU (80 accumulator + 40 Q + 40 prefetch registers; 86 KB of tiles)
 #undef FA_CASE
+}
+
+bool flash_attn_ip_shape_ok(int64_t D, int64_t DV, int64_t Lq, int64_t Lk, int64_t Lk_ip) {
+    return D == DV && D >= 8 && D <= 64 && D % 8 == 0 && Lk > 64 && Lk <= 96 && Lk_ip >= 1 && Lk_ip <= 32 && Lq >= 1;
+}
+
+void launch_flash_attn_ip(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, const View4& k_ip, const View4& v_ip, float scale, float ip_scale) {
+    const int64_t Lq = q.ne[1], Lk = k.ne[1], Li = k_ip.ne[1], D = q.ne[0];
+    KScope ks_(s, KF_FLASH, 4.0 * (double)Lq * (double)(Lk + Li) * (double)q.ne[2] * (double)D, 0.0);
+    FAIpArgs a;
+    FAArgs& g = a.g;
+    memset(&a, 0, sizeof(a));
+    g.q = (const char*)q.data;
+    g.k = (const char*)k.data;
+    g.v = (const char*)v.data;
+    g.dst      = out.dst;
+    g.dst16    = (_Float16*)out.dst16;
+    g.ld16     = out.ld16;
+    g.H        = out.H;
+    g.dst_nb_n = out.nb_n;
+    g.dst_nb_q = out.nb_q;
+    g.dst_nb_h = out.nb_h;
+    g.q_nb1 = q.nb[1];
+    g.q_nb2 = q.nb[2];
+    g.k_nb1 = k.nb[1];
+    g.k_nb2 = k.nb[2];
+    g.v_nb0 = v.nb[0];
+    g.v_nb1 = v.nb[1];
+    g.v_nb2 = v.nb[2];
+    g.Lq = (int)Lq;
+    g.Lk = (int)Lk;
+    g.D  = (int)D;
+    g.DV = (int)v.ne[0];
+    g.kv_f16      = 1;
+    g.scale_log2e = scale * 1.44269504088896340736f;
+    g.q_f16       = q.type == 1;
+    a.k_ip     = (const char*)k_ip.data;
+    a.v_ip     = (const char*)v_ip.data;
+    a.kip_nb1  = k_ip.nb[1];
+    a.kip_nb2  = k_ip.nb[2];
+    a.vip_nb1  = v_ip.nb[1];
+    a.vip_nb2  = v_ip.nb[2];
+    a.Lk_ip    = (int)Li;
+    a.ip_scale = ip_scale;
+    auto al16 = [](const void* p, int64_t x, int64_t y) { return ((((uintptr_t)p) | (uintptr_t)x | (uintptr_t)y) & 15) == 0; };
+    auto kv_ok = [&](const View4& t, int64_t L) { return t.type == 1 && t.nb[0] == 2 && t.ne[0] == D && t.ne[1] == L && t.ne[2] == q.ne[2] && al16(t.data, t.nb[1], t.nb[2]); };
+    const bool q_ok = (q.type == 1 && q.nb[0] == 2 && al16(q.data, q.nb[1], q.nb[2])) || (q.type == 0 && q.nb[0] == 4 && al16(q.data, q.nb[1], q.nb[2]));
+    // a missing kernel is an error, never a quiet other route: the planner asked for shapes this launch does not take
+    if (!flash_attn_ip_shape_ok(D, v.ne[0], Lq, Lk, Li) || !kv_ok(k, Lk) || !kv_ok(v, Lk) || !kv_ok(k_ip, Li) || !kv_ok(v_ip, Li) || !q_ok || (g.dst != nullptr) == (g.dst16 != nullptr) ||
+        (int64_t)Lq * std::max<int64_t>(g.q_nb1, g.dst16 ? g.ld16 * 2 : g.dst_nb_q) >= (int64_t)0x7ff00000) {
+        fprintf(stderr, "mi355x: launch_flash_attn_ip: operands outside the kernel's limits (d %lld, Lq %lld, Lk %lld, Lk_ip %lld; f16 d-contiguous 16-byte aligned K / V, one output)\n",
+                (long long)D, (long long)Lq, (long long)Lk, (long long)Li);
+        abort();
+    }
+    const int64_t nblk = (int64_t)((g.Lq + 31) / 32) * q.ne[2];
+    g.qi  = (int)std::max<int64_t>(1, std::min<int64_t>(8, nblk / 4096));
+    dim3 gs((unsigned)((g.Lq + 128 * g.qi - 1) / (128 * g.qi)), (unsigned)q.ne[2]);
+    g_variant_launches[FLASH_VAR_SHORT_IP]++;
+#define FSI_CASE(DKP_)                                                     \
+    do {                                                                   \
+        if (g.q_f16 && g.dst16)                                            \
+            k_flash_short_ip<DKP_, true, true><<<gs, 256, 0, s>>>(a);      \
+        else if (g.q_f16)                                                  \
+            k_flash_short_ip<DKP_, true, false><<<gs, 256, 0, s>>>(a);     \
+        else if (g.dst16)                                                  \
+            k_flash_short_ip<DKP_, false, true><<<gs, 256, 0, s>>>(a);     \
+        else                                                               \
+            k_flash_short_ip<DKP_, false, false><<<gs, 256, 0, s>>>(a);    \
+    } while (0)
+    if (D <= 48)
+        FSI_CASE(48);
+    else
+        FSI_CASE(64);
+#undef FSI_CASE
 }
 
 }  // namespace mi355x

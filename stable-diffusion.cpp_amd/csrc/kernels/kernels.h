@@ -373,7 +373,12 @@ bool gemm16_split_col_supported(int64_t rows, int64_t M, int64_t K);  // a Linea
 void gemm16_set_streamk(int v);    // option "streamk" (0; 1 = launches of two rounds or more, 2 = every candidate): Linears whose tile count leaves the last round of a one-workgroup-per-CU tile mostly empty run as one round of persistent workgroups over equal (tile, K-tile) ranges
 void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale);
 // which instantiation launch_flash_attn chose, counted per call (statistics flash_*_launches; the other FAST tile kernels are not counted)
-enum FlashVariant { FLASH_VAR_SHORT = 0, FLASH_VAR_QB2, FLASH_VAR_MSLOT, FLASH_VAR_GENERIC, FLASH_VAR_COUNT };
+enum FlashVariant { FLASH_VAR_SHORT = 0, FLASH_VAR_QB2, FLASH_VAR_MSLOT, FLASH_VAR_GENERIC, FLASH_VAR_SHORT_IP, FLASH_VAR_COUNT };
+// IP-Adapter cross-attention in one launch (k_flash_short_ip): softmax(scale q k^T) v + ip_scale * softmax(scale q k_ip^T) v_ip into one output.  Text K / V as
+// k_flash_short takes them (64 < Lk <= 96), image K / V [D, Lk_ip, HN] with 1 <= Lk_ip <= 32, all f16, d-contiguous, 16-byte aligned rows; d <= 64, d % 8 == 0; Q f32
+// or an f16 image; exactly one of out.dst / out.dst16.  Anything else aborts: the planner asks flash_attn_ip_shape_ok first and runs other shapes as plain nodes.
+bool flash_attn_ip_shape_ok(int64_t D, int64_t DV, int64_t Lq, int64_t Lk, int64_t Lk_ip);
+void launch_flash_attn_ip(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, const View4& k_ip, const View4& v_ip, float scale, float ip_scale);
 int64_t flash_attn_variant_launches(int variant);
 
 
