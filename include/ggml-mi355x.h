@@ -181,6 +181,9 @@ struct ggml_backend_mi355x_stats {
     /* IP-Adapter cross-attention (option fuse_ip_attn) */
     int64_t fused_ip_attn;           /* attn2 pairs FLASH_ATTN_EXT(q,k,v) / FLASH_ATTN_EXT(q,k_ip,v_ip) -> SCALE -> ADD planned as ONE launch of k_flash_short_ip (per plan; a pair refused for the placement of its operands counts in flash_out_alias) */
     int64_t flash_short_ip_launches; /* launch_flash_attn_ip calls (per launch call, as flash_short_launches) */
+    /* CLIP vision tower (option fuse_patch_embed) */
+    int64_t fused_patch_embed;       /* CLIPVisionEmbeddings chains (REPEAT class, IM2COL .. CONT of the stride = kernel conv, CONCAT, ADD position) planned as ONE launch of k_patch_embed (per plan) */
+    int64_t patch_embed_launches;    /* launch_patch_embed calls (per launch call) */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and
@@ -244,6 +247,8 @@ GGML_MI355X_API int ggml_backend_mi355x_get_kernel_timings(struct ggml_backend_m
  * "fuse_flash_slices" (1: the proj Linears of an MMDiT / FLUX double block read their token slices out of the flash kernel's f16 image), "gemm16_t192p" (1: the pipelined 256 x 192 Linear tile where it quantises better on 256 CUs), "hoist_mod" (1), "plan_cache_cap" (512), "gn_split_min" (65536);
  * "fuse_ip_attn" (1: the two attentions of an IP-Adapter attn2 — text keys and 1 .. 32 image keys of the same q — with their SCALE and ADD as one launch of
  * k_flash_short_ip; 0 = plain nodes on k_flash_short and the elementwise launches);
+ * "fuse_patch_embed" (0 = plain nodes, the default: at batch 1 the one launch measured slower than they are, profiles/clip_vision_probe.txt; 1: the embeddings stage of a CLIP vision tower — REPEAT of the class embedding, the stride = kernel conv without bias (IM2COL .. CONT), the
+ * transposing CONT, CONCAT and the ADD of the position table — as one launch of k_patch_embed);
  * "fuse_ln_reduce" (1: the slab reduce of a split-K Linear also writes the f16 operand image of the LayerNorm that reads its result);
  * "fuse_gn_epilogue" (1: an unsplit LDS-window conv read by a GroupNorm, or by a skip CONCAT a GroupNorm reads, writes per-channel (mean, M2) records of the values it
  * stores; the GroupNorm's statistics pass over the tensor becomes one small finalize launch over the records; 0 = the plan without it);
@@ -305,6 +310,10 @@ GGML_MI355X_API bool ggml_backend_mi355x_spectrum_push(ggml_backend_t backend, c
 GGML_MI355X_API bool ggml_backend_mi355x_latent_preview(ggml_backend_t backend, const float* latents, int64_t plane, int c, int64_t n, float in_scale, const float* proj,
                                                         const float* bias, uint8_t* out_rgb);
 GGML_MI355X_API bool ggml_backend_mi355x_planar_to_u8(ggml_backend_t backend, const float* chw, int64_t plane, int64_t n, float in_mul, float in_add, uint8_t* out_rgb);
+/* CLIP preprocessing (kernels/clip_vision.hip): n u8 HWC RGB pictures [n][h][w][3] -> pixel values [S, S, 3, n] f32 = (clamp(v / 255, 0, 1) - mean[c]) / std[c] of the
+ * pixel (xi[x], yi[y]) — xi / yi: the S source columns / rows of the resize + centre crop (0 <= xi < w, 0 <= yi < h, checked).  images, xi, yi and out are HOST memory;
+ * complete on return.  false: bad arguments or no memory */
+GGML_MI355X_API bool ggml_backend_mi355x_clip_preprocess(ggml_backend_t backend, const uint8_t* images, int w, int h, int64_t n, int S, const int* xi, const int* yi, float* out);
 /* path of the HIP runtime library this plug-in is bound to, and hipSetDevice through it (for companions that must share its streams: RCCL) */
 GGML_MI355X_API const char* ggml_backend_mi355x_hip_library(void);
 GGML_MI355X_API int ggml_backend_mi355x_set_device(int hip_device);

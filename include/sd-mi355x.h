@@ -238,9 +238,9 @@ SD_API bool sd_unet_forward(sdm_ctx_t* ctx, const float* x, int w, int h, int c,
 SD_API bool sd_unet_forward_concat(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int n, const float* timesteps, const float* context, int64_t ctx_dim, int64_t n_tokens,
                                    int64_t ctx_n, const float* y, int64_t y_dim, int64_t y_n, const float* c_concat, int cc, int concat_n, float* out);
 /* ---- IP-Adapter (src/model/adapter/ip_adapter.hpp, CrossAttention::to_k_ip / to_v_ip, block.hpp:307-393); UNet families only.
- * In scope: the plain adapters (ImageProjModel: Linear + LayerNorm).  Out of scope: the Resampler of the "plus" adapters (it needs GELU_ERF, which neither the ggml
- * front-end, the backend nor the CPU oracle implement) and the CLIP vision tower — the API takes CLIP image embeddings like the text side takes token ids; a caller
- * with plus tokens from elsewhere passes them as ip_context directly.
+ * The plain adapters (ImageProjModel: Linear + LayerNorm) here; the Resampler of the "plus" adapters (sd_ip_adapter_init_plus; its feed-forward is GELU_ERF, which the
+ * MI355X backend runs and the CPU oracle of the tests does not) and the CLIP vision tower that makes the embeddings from a picture (sd_clip_vision_init,
+ * sd_set_ip_adapter_image) follow below.  A caller with embeddings or tokens from elsewhere passes them to sd_ip_adapter_project / sd_set_ip_adapter directly.
  * sd_ip_adapter_init adds "...attn2.to_k_ip.weight" / "...attn2.to_v_ip.weight" [ip_dim -> inner, no bias] to every attn2 and "ip_adapter.image_proj.{proj,norm}.*", in a
  * weight buffer of their own with synthetic values from the seeded initialiser (sd_set_tensor_f32 binds real ones); the resident weights stay untouched.  A second
  * call with the same dimensions is a no-op, with other dimensions an error. */
@@ -250,8 +250,46 @@ SD_API bool sd_ip_adapter_init(sdm_ctx_t* ctx, int64_t ip_dim, int64_t clip_dim,
  * parameters (and only they) bound.  Returns the number loaded or -1; n_missing counts adapter parameters the file lacks, n_unused file tensors nothing took */
 SD_API int64_t sd_load_ip_adapter(sdm_ctx_t* ctx, const char* path, int64_t* n_missing, int64_t* n_unused);
 SD_API bool sd_ip_adapter_info(sdm_ctx_t* ctx, int64_t* ip_dim, int64_t* clip_dim, int64_t* num_tokens); /* false: no adapter initialised */
-/* ImageProjModel: CLIP image embeddings [clip_dim, n] -> image tokens tokens_out [ip_dim, num_tokens, n] */
+/* ImageProjModel: CLIP image embeddings [clip_dim, n] -> image tokens tokens_out [ip_dim, num_tokens, n].  On a plus adapter: the tower's hidden states
+ * [embed_dim, n_tok, n] with n_tok the token count of the context's vision tower (257 for 224 / 14); without a tower use sd_ip_adapter_project_tokens */
 SD_API bool sd_ip_adapter_project(sdm_ctx_t* ctx, const float* embeds, int n, float* tokens_out);
+/* the same with the token count stated: embeds [clip_dim, n_tok, n]; n_tok must be 1 on a plain adapter.  A backend without GELU_ERF refuses a plus adapter here */
+SD_API bool sd_ip_adapter_project_tokens(sdm_ctx_t* ctx, const float* embeds, int64_t n_tok, int n, float* tokens_out);
+/* The "plus" adapters: to_k_ip / to_v_ip as sd_ip_adapter_init plus the Resampler (ip_adapter.hpp:34-113) "ip_adapter.image_proj.{latents, proj_in, proj_out, norm_out,
+ * layers.<i>.0.{norm1,norm2,to_q,to_kv,to_out}, layers.<i>.1.{0,1,3}}": `depth` layers of a cross-attention of num_queries latents [dim] onto the hidden states
+ * [embed_dim] and a GELU_ERF feed-forward [ff_inner]; heads = dim / 64; output [ip_dim, num_queries].  A context holds ONE adapter, plain or plus.
+ * sd_load_ip_adapter tells a plus file by "image_proj.latents" and reads the shapes as IPAdapterRunner does (ip_adapter.hpp:128-158) */
+SD_API bool sd_ip_adapter_init_plus(sdm_ctx_t* ctx, int64_t ip_dim, int64_t dim, int64_t depth, int64_t num_queries, int64_t embed_dim, int64_t ff_inner, uint64_t weight_seed);
+/* sd_ip_adapter_info plus is_plus (clip_dim is then the Resampler's embed_dim, num_tokens its num_queries) */
+SD_API bool sd_ip_adapter_info_ex(sdm_ctx_t* ctx, int64_t* ip_dim, int64_t* clip_dim, int64_t* num_tokens, bool* is_plus);
+/* ---- CLIP vision tower (src/model/te/clip.hpp:183-238, 332-464: CLIPVisionModelProjection) — what makes the image embeddings from a picture.
+ * version 0 / 1 / 2 = ViT-L/14, ViT-H/14, ViT-bigG/14 (the reference's hyper-parameters; its MLP activation is tanh-GELU for hidden 1024 / 1280 and quick-GELU
+ * otherwise, so also for bigG's 1664); `tiny` non-NULL overrides it with a test-width configuration (intermediate = 2 hidden).  Parameters "clip_vision.vision_model.*",
+ * "clip_vision.visual_projection.weight" (f16 patch weight, f32 class embedding and position table) in a weight buffer of their own, synthetic values from the seeded
+ * initialiser.  A second call with the same shape is a no-op, with another shape an error. */
+typedef struct {
+    int64_t hidden_size, n_head, n_layer, image_size, patch_size, projection_dim;
+} sd_clip_vision_tiny_t;
+typedef struct {
+    int64_t image_size, patch_size, hidden_size, intermediate_size, n_head, n_layer, projection_dim, num_positions, use_gelu;
+} sd_clip_vision_info_t;
+SD_API bool sd_clip_vision_init(sdm_ctx_t* ctx, int version, const sd_clip_vision_tiny_t* tiny, uint64_t weight_seed);
+SD_API bool sd_clip_vision_info(sdm_ctx_t* ctx, sd_clip_vision_info_t* out); /* false: no tower initialised */
+/* a tower file (HF CLIPVisionModelWithProjection names), loaded under the "clip_vision." prefix by the reference's name rule (name_conversion.cpp:1473, :106-185); the
+ * tower is initialised from the file's shapes if it is not yet.  Returns the number loaded or -1; n_missing / n_unused as sd_load_ip_adapter */
+SD_API int64_t sd_load_clip_vision(sdm_ctx_t* ctx, const char* path, int64_t* n_missing, int64_t* n_unused);
+/* clip_preprocess (src/core/util.cpp:695-758) of n u8 HWC RGB pictures [n][h][w][3]: value / 255, nearest resize by the larger of the two ratios (resized extents
+ * truncated), centre crop, clamp to [0, 1], (v - mean) / std -> out [S, S, 3, n] with S the tower's image size (sd_clip_preprocess_size: S given, no tower needed).
+ * One kernel launch on the MI355X backend; bit-equal to a NumPy restatement */
+SD_API bool sd_clip_preprocess(sdm_ctx_t* ctx, const uint8_t* images, int w, int h, int n, float* out);
+SD_API bool sd_clip_preprocess_size(sdm_ctx_t* ctx, const uint8_t* images, int w, int h, int n, int size, float* out);
+/* pixel_values [S, S, 3, n] -> return_pooled: visual_projection(post_layernorm(x)[token 0]) [projection_dim, n]; else the hidden state BEFORE post_layernorm
+ * [hidden, num_positions, n] (clip.hpp:389).  clip_skip > 0 stops n_layer - clip_skip + 1 layers in, pooled or not (clip.hpp:377) */
+SD_API bool sd_clip_vision_encode(sdm_ctx_t* ctx, const float* pixel_values, int n, bool return_pooled, int clip_skip, float* out);
+/* compute_ip_adapter_tokens (stable-diffusion.cpp:2187-2215) of one u8 HWC RGB picture: preprocess, encode (pooled for a plain adapter, the hidden state at clip_skip 2
+ * for a plus one), project; uncond tokens from an all-zero embedding of the same shape; then sd_set_ip_adapter.  NULL clears.  An error (never a no-op) without a
+ * tower, without an adapter, or when the tower's output width is not what the adapter expects */
+SD_API bool sd_set_ip_adapter_image(sdm_ctx_t* ctx, const uint8_t* image, int w, int h, float strength);
 /* Token state for the sampling entries (context state like sd_set_vae_tiling): sdm_generate_image and sd_sample_latents — the host loop, its fused branches, the
  * device-resident sampler, inpaint / pix2pix variants, the CFG-pair exchange — hand `tokens` [ip_dim, n_tokens] to the cond branch and `uncond_tokens` to every other
  * branch (uncond, img_uncond; stable-diffusion.cpp:2829-2843), scaled by `strength` (0: the graphs of a context without the adapter).  In a graph of K branches per image

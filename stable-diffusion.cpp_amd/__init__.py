@@ -42,6 +42,7 @@ CACHE_DISABLED, CACHE_EASYCACHE, CACHE_UCACHE = 0, 1, 2
 CACHE_DBCACHE, CACHE_TAYLORSEER, CACHE_CACHE_DIT, CACHE_SPECTRUM = 3, 4, 5, 6
 # sdm_preview_t (include/sd-mi355x.h): the reference's preview_t values; sdm_preview_cb_t: (step, frame_count, frames, is_noisy, user)
 PREVIEW_NONE, PREVIEW_PROJ, PREVIEW_TAE, PREVIEW_VAE = 0, 1, 2, 3
+CLIP_VIT_L_14, CLIP_VIT_H_14, CLIP_VIT_BIGG_14 = 0, 1, 2  # clip_vision_init versions
 PREVIEW_CB_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, C.c_bool, C.c_void_p)
 # sdm_unet_variant_t (include/sd-mi355x.h): UNets whose first conv also reads c_concat — inpainting (mask 1 | masked-image latent 4) and instruct-pix2pix (image latent 4)
 UNET_PLAIN, UNET_INPAINT, UNET_PIX2PIX = 0, 1, 2
@@ -209,7 +210,7 @@ ggml_soft_max_inplace ggml_soft_max_ext ggml_im2col ggml_conv_2d ggml_conv_2d_di
 ggml_timestep_embedding ggml_flash_attn_ext ggml_new_graph ggml_new_graph_custom ggml_graph_node ggml_set_name
 ggml_gallocr_new ggml_backend_load ggml_backend_dev_get ggml_backend_dev_by_name ggml_backend_dev_init
 ggml_backend_get_default_buffer_type ggml_backend_alloc_ctx_tensors ggml_backend_dev_buffer_type ggml_unary
-ggml_unary_inplace ggml_get_rows ggml_dup ggml_neg ggml_exp ggml_pad_ext sdm_new_ctx""".split()
+ggml_unary_inplace ggml_get_rows ggml_dup ggml_neg ggml_exp ggml_gelu_erf ggml_gelu_erf_inplace ggml_pad_ext sdm_new_ctx""".split()
 
 
 def lib() -> C.CDLL:
@@ -236,7 +237,7 @@ def lib() -> C.CDLL:
               "ggml_cpy", "ggml_repeat", "ggml_get_rows"):
         getattr(L, n).argtypes = [C.c_void_p] * 3
     for n in ("ggml_silu", "ggml_silu_inplace", "ggml_gelu", "ggml_gelu_inplace", "ggml_gelu_quick", "ggml_sigmoid",
-              "ggml_tanh", "ggml_relu", "ggml_neg", "ggml_exp", "ggml_cont", "ggml_transpose", "ggml_soft_max", "ggml_soft_max_inplace", "ggml_dup"):
+              "ggml_tanh", "ggml_relu", "ggml_neg", "ggml_exp", "ggml_gelu_erf", "ggml_gelu_erf_inplace", "ggml_cont", "ggml_transpose", "ggml_soft_max", "ggml_soft_max_inplace", "ggml_dup"):
         getattr(L, n).argtypes = [C.c_void_p] * 2
     L.ggml_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
     L.ggml_scale_inplace.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
@@ -423,7 +424,8 @@ _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned 
                         "lin_streamk lin_rowsplit_main lin_multi lin_splitk_reduce lin_splitk_reduce_ln lin_geglu_pair lin_geglu16 "
                         "lin_qgemv lin_qgemv_rows4 lin_qgemv_rows8 lin_qgemv_rows16 lin_qgemv_group lin_qgemm16_rb1 lin_qgemm16_rb2 lin_qgemm16_rb4 lin_qgemm16_reduce "
                         "lin_fgemv_f16 lin_fgemv_f32 lin_wswz_q "
-                        "fused_ip_attn flash_short_ip_launches").split()
+                        "fused_ip_attn flash_short_ip_launches "
+                        "fused_patch_embed patch_embed_launches").split()
 
 
 class BackendStats(C.Structure):
@@ -771,7 +773,7 @@ class Engine:
             raise EngineError("sd_unet_forward_skip_layers failed: " + L.sd_last_error().decode())
         return out
 
-    # ---- IP-Adapter: image tokens in every attn2 (plain adapters: ImageProjModel; the Resampler and the CLIP vision tower are out of scope) ----
+    # ---- IP-Adapter: image tokens in every attn2 (plain adapters: ImageProjModel; plus adapters: Resampler), tokens from a picture through the CLIP vision tower ----
     def ip_adapter_init(self, ip_dim: int, clip_dim: int, num_tokens: int = 4, weight_seed: int = 0) -> None:
         """sd_ip_adapter_init: to_k_ip / to_v_ip on every attn2 plus the image projection, synthetic weights (set_tensor binds real ones).  UNet families only."""
         L = lib()
@@ -791,10 +793,23 @@ class Engine:
             raise EngineError("sd_load_ip_adapter failed: " + L.sd_last_error().decode())
         return {"loaded": int(n), "missing": int(miss.value), "unused": int(unused.value)}
 
-    def set_ip_adapter(self, tokens: np.ndarray | None = None, uncond_tokens: np.ndarray | None = None, embeds: np.ndarray | None = None, strength: float = 1.0) -> None:
-        """sd_set_ip_adapter / sd_set_ip_adapter_embeds: the image tokens the sampling entries use — `tokens` [n_tokens, ip_dim] on the cond branch, `uncond_tokens` (default:
-        the projection of an all-zero embedding) on every other branch — or `embeds` [clip_dim], projected first.  Neither given: cleared."""
+    def set_ip_adapter(self, tokens: np.ndarray | None = None, uncond_tokens: np.ndarray | None = None, embeds: np.ndarray | None = None, strength: float = 1.0,
+                       image: np.ndarray | None = None) -> None:
+        """sd_set_ip_adapter / sd_set_ip_adapter_embeds / sd_set_ip_adapter_image: the image tokens the sampling entries use — `tokens` [n_tokens, ip_dim] on the cond branch,
+        `uncond_tokens` (default: the projection of an all-zero embedding) on every other branch — or `embeds` [clip_dim], projected first — or `image` [H, W, 3] uint8,
+        preprocessed, encoded by the context's vision tower and projected (plain or plus adapter).  None given: cleared."""
         L = lib()
+        if image is not None:
+            if tokens is not None or embeds is not None or uncond_tokens is not None:
+                raise EngineError("set_ip_adapter: give an image, tokens or embeds, not several")
+            img = np.ascontiguousarray(image)
+            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+                raise EngineError(f"set_ip_adapter: image is [H, W, 3] uint8, got {img.dtype} {img.shape}")
+            L.sd_set_ip_adapter_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
+            L.sd_set_ip_adapter_image.restype = C.c_bool
+            if not L.sd_set_ip_adapter_image(self._ctx, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0], float(strength)):
+                raise EngineError("sd_set_ip_adapter_image failed: " + L.sd_last_error().decode())
+            return
         L.sd_set_ip_adapter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
         L.sd_set_ip_adapter.restype = C.c_bool
         L.sd_set_ip_adapter_embeds.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
@@ -839,12 +854,111 @@ class Engine:
             return None
         return int(a.value), int(b.value), int(c.value)
 
+    def ip_adapter_init_plus(self, ip_dim: int, dim: int, depth: int, num_queries: int, embed_dim: int, ff_inner: int, weight_seed: int = 0) -> None:
+        """sd_ip_adapter_init_plus: to_k_ip / to_v_ip on every attn2 plus the Resampler of the "plus" adapters, synthetic weights.  UNet families only."""
+        L = lib()
+        L.sd_ip_adapter_init_plus.argtypes = [C.c_void_p] + [C.c_int64] * 6 + [C.c_uint64]
+        L.sd_ip_adapter_init_plus.restype = C.c_bool
+        if not L.sd_ip_adapter_init_plus(self._ctx, int(ip_dim), int(dim), int(depth), int(num_queries), int(embed_dim), int(ff_inner), int(weight_seed)):
+            raise EngineError("sd_ip_adapter_init_plus failed: " + L.sd_last_error().decode())
+
+    def ip_adapter_is_plus(self) -> bool:
+        L = lib()
+        L.sd_ip_adapter_info_ex.argtypes = [C.c_void_p] * 5
+        L.sd_ip_adapter_info_ex.restype = C.c_bool
+        plus = C.c_bool(False)
+        return bool(L.sd_ip_adapter_info_ex(self._ctx, None, None, None, C.byref(plus))) and bool(plus.value)
+
+    # ---- CLIP vision tower: picture -> image embeddings (clip_preprocess, CLIPVisionModelProjection) ----
+    def clip_vision_init(self, version: int | None = None, *, hidden: int = 0, heads: int = 0, layers: int = 0, image_size: int = 224, patch_size: int = 14,
+                         proj: int = 0, weight_seed: int = 0) -> None:
+        """sd_clip_vision_init: version CLIP_VIT_L_14 / _H_14 / _BIGG_14, or (version None) a tiny configuration hidden / heads / layers / image_size / patch_size / proj."""
+        L = lib()
+        L.sd_clip_vision_init.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
+        L.sd_clip_vision_init.restype = C.c_bool
+        tiny = None
+        if version is None:
+            tiny = (C.c_int64 * 6)(int(hidden), int(heads), int(layers), int(image_size), int(patch_size), int(proj))
+        if not L.sd_clip_vision_init(self._ctx, -1 if version is None else int(version), tiny, int(weight_seed)):
+            raise EngineError("sd_clip_vision_init failed: " + L.sd_last_error().decode())
+
+    def clip_vision_info(self):
+        """dict of the initialised tower's shape (image_size, patch_size, hidden_size, intermediate_size, n_head, n_layer, projection_dim, num_positions, use_gelu), or None."""
+        L = lib()
+        L.sd_clip_vision_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.sd_clip_vision_info.restype = C.c_bool
+        v = (C.c_int64 * 9)()
+        if not L.sd_clip_vision_info(self._ctx, v):
+            return None
+        keys = "image_size patch_size hidden_size intermediate_size n_head n_layer projection_dim num_positions use_gelu".split()
+        return {k: int(x) for k, x in zip(keys, v)}
+
+    def load_clip_vision(self, path) -> dict:
+        """sd_load_clip_vision: a tower file (HF CLIPVisionModelWithProjection names); initialises the tower from the file's shapes if needed."""
+        miss, unused = C.c_int64(0), C.c_int64(0)
+        L = lib()
+        L.sd_load_clip_vision.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.sd_load_clip_vision.restype = C.c_int64
+        n = L.sd_load_clip_vision(self._ctx, str(path).encode(), C.byref(miss), C.byref(unused))
+        if n < 0:
+            raise EngineError("sd_load_clip_vision failed: " + L.sd_last_error().decode())
+        return {"loaded": int(n), "missing": int(miss.value), "unused": int(unused.value)}
+
+    def clip_preprocess(self, images: np.ndarray, size: int | None = None) -> np.ndarray:
+        """sd_clip_preprocess: uint8 pictures [H, W, 3] or [n, H, W, 3] -> pixel values [n, 3, S, S] f32; S = the tower's image size, or `size`."""
+        img = np.ascontiguousarray(images)
+        if img.ndim == 3:
+            img = img[None]
+        if img.dtype != np.uint8 or img.ndim != 4 or img.shape[3] != 3:
+            raise EngineError(f"clip_preprocess: images are [n, H, W, 3] uint8, got {img.dtype} {img.shape}")
+        if size is None:
+            info = self.clip_vision_info()
+            if info is None:
+                raise EngineError("clip_preprocess: no vision tower is initialised on this engine (clip_vision_init); pass size=")
+            size = info["image_size"]
+        n, h, w, _ = img.shape
+        out = np.empty((n, 3, int(size), int(size)), dtype=np.float32)
+        L = lib()
+        L.sd_clip_preprocess_size.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.sd_clip_preprocess_size.restype = C.c_bool
+        if not L.sd_clip_preprocess_size(self._ctx, img.ctypes.data_as(C.c_void_p), w, h, n, int(size), _fptr(out)):
+            raise EngineError("sd_clip_preprocess failed: " + L.sd_last_error().decode())
+        return out
+
+    def clip_vision_encode(self, pixel_values: np.ndarray, return_pooled: bool = True, clip_skip: int = -1) -> np.ndarray:
+        """sd_clip_vision_encode: pixel values [n, 3, S, S] -> pooled [n, projection_dim], or the hidden state before post_layernorm [n, num_positions, hidden]."""
+        info = self.clip_vision_info()
+        if info is None:
+            raise EngineError("clip_vision_encode: no vision tower is initialised on this engine (clip_vision_init)")
+        px = _f32(pixel_values)
+        S = info["image_size"]
+        if px.ndim != 4 or px.shape[1:] != (3, S, S):
+            raise EngineError(f"clip_vision_encode: pixel values are [n, 3, {S}, {S}], got {px.shape}")
+        n = px.shape[0]
+        out = np.empty((n, info["projection_dim"]) if return_pooled else (n, info["num_positions"], info["hidden_size"]), dtype=np.float32)
+        L = lib()
+        L.sd_clip_vision_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_bool, C.c_int, C.c_void_p]
+        L.sd_clip_vision_encode.restype = C.c_bool
+        if not L.sd_clip_vision_encode(self._ctx, _fptr(px), n, bool(return_pooled), int(clip_skip), _fptr(out)):
+            raise EngineError("sd_clip_vision_encode failed: " + L.sd_last_error().decode())
+        return out
+
     def ip_adapter_project(self, embeds: np.ndarray) -> np.ndarray:
-        """sd_ip_adapter_project: CLIP image embeddings [n, clip_dim] -> image tokens [n, num_tokens, ip_dim]."""
+        """sd_ip_adapter_project: CLIP image embeddings [n, clip_dim] -> image tokens [n, num_tokens, ip_dim]; on a plus adapter hidden states [n, n_tok, embed_dim]."""
         info = self.ip_adapter_info()
         if info is None:
             raise EngineError("ip_adapter_project: no IP-Adapter is initialised on this engine (ip_adapter_init)")
         e = _f32(embeds)
+        if self.ip_adapter_is_plus():
+            if e.ndim != 3 or e.shape[2] != info[1]:
+                raise EngineError(f"ip_adapter_project: a plus adapter takes hidden states [n, n_tok, embed_dim = {info[1]}], got {e.shape}")
+            out = np.empty((e.shape[0], info[2], info[0]), dtype=np.float32)
+            L = lib()
+            L.sd_ip_adapter_project_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+            L.sd_ip_adapter_project_tokens.restype = C.c_bool
+            if not L.sd_ip_adapter_project_tokens(self._ctx, _fptr(e), e.shape[1], e.shape[0], _fptr(out)):
+                raise EngineError("sd_ip_adapter_project failed: " + L.sd_last_error().decode())
+            return out
         if e.ndim != 2 or e.shape[1] != info[1]:
             raise EngineError(f"ip_adapter_project: embeds are [n, clip_dim = {info[1]}], got {e.shape}")
         out = np.empty((e.shape[0], info[2], info[0]), dtype=np.float32)

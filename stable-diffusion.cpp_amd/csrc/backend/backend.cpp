@@ -294,6 +294,7 @@ static void* reg_get_proc(ggml_backend_reg_t, const char* name) {
     if (strcmp(name, "ggml_backend_mi355x_spectrum_push") == 0) return (void*)ggml_backend_mi355x_spectrum_push;
     if (strcmp(name, "ggml_backend_mi355x_latent_preview") == 0) return (void*)ggml_backend_mi355x_latent_preview;
     if (strcmp(name, "ggml_backend_mi355x_planar_to_u8") == 0) return (void*)ggml_backend_mi355x_planar_to_u8;
+    if (strcmp(name, "ggml_backend_mi355x_clip_preprocess") == 0) return (void*)ggml_backend_mi355x_clip_preprocess;
     if (strcmp(name, "ggml_backend_mi355x_hip_library") == 0) return (void*)ggml_backend_mi355x_hip_library;
     if (strcmp(name, "ggml_backend_mi355x_set_device") == 0) return (void*)ggml_backend_mi355x_set_device;
     if (strcmp(name, "ggml_backend_mi355x_get_device") == 0) return (void*)ggml_backend_mi355x_get_device;
@@ -561,6 +562,27 @@ GGML_MI355X_API bool ggml_backend_mi355x_planar_to_u8(ggml_backend_t backend, co
     uint8_t* dev       = preview_scratch(bc, bytes);
     if (!dev || !mi355x::launch_planar_to_u8(bc->stream, chw, plane, n, in_mul, in_add, dev)) return false;
     return hipMemcpyAsync(out_rgb, dev, bytes, hipMemcpyDeviceToHost, bc->stream) == hipSuccess;
+}
+// CLIP preprocessing (kernels/clip_vision.hip): pictures, index tables and result are HOST memory; the device copies live in the backend's byte buffer
+GGML_MI355X_API bool ggml_backend_mi355x_clip_preprocess(ggml_backend_t backend, const uint8_t* images, int w, int h, int64_t n, int S, const int* xi, const int* yi, float* out) {
+    if (!backend || !images || !xi || !yi || !out || w < 1 || h < 1 || n < 1 || S < 1) return false;
+    for (int i = 0; i < S; ++i)
+        if (xi[i] < 0 || xi[i] >= w || yi[i] < 0 || yi[i] >= h) return false;  // the kernel gathers through them unchecked
+    mi355x::BackendCtx* bc = (mi355x::BackendCtx*)backend->context;
+    if (hipSetDevice(bc->dev->id) != hipSuccess) return false;
+    const size_t out_b = (size_t)S * S * 3 * (size_t)n * sizeof(float), tab_b = (size_t)S * sizeof(int), img_b = (size_t)w * h * 3 * (size_t)n;
+    uint8_t* dev       = preview_scratch(bc, out_b + 2 * tab_b + img_b);
+    if (!dev) return false;
+    float* d_out   = (float*)dev;
+    int* d_xi      = (int*)(dev + out_b);
+    int* d_yi      = (int*)(dev + out_b + tab_b);
+    uint8_t* d_img = dev + out_b + 2 * tab_b;
+    if (hipMemcpyAsync(d_xi, xi, tab_b, hipMemcpyHostToDevice, bc->stream) != hipSuccess || hipMemcpyAsync(d_yi, yi, tab_b, hipMemcpyHostToDevice, bc->stream) != hipSuccess ||
+        hipMemcpyAsync(d_img, images, img_b, hipMemcpyHostToDevice, bc->stream) != hipSuccess)
+        return false;
+    if (!mi355x::launch_clip_preprocess(bc->stream, d_img, d_xi, d_yi, d_out, w, h, S, n)) return false;
+    if (hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, bc->stream) != hipSuccess) return false;
+    return hipStreamSynchronize(bc->stream) == hipSuccess;
 }
 // The HIP runtime THIS plug-in is bound to (a process may hold a second copy, e.g. the one a torch wheel bundles): a companion library that
 // must share streams with the backend — RCCL for the native CFG-pair exchange — is loaded from the same directory.

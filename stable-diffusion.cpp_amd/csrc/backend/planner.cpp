@@ -77,6 +77,7 @@ const NameNum kNeededOps[] = {
 const NameNum kNeededUnary[] = {
     {"NEG", GGML_UNARY_OP_NEG}, {"TANH", GGML_UNARY_OP_TANH}, {"RELU", GGML_UNARY_OP_RELU}, {"SIGMOID", GGML_UNARY_OP_SIGMOID},
     {"GELU", GGML_UNARY_OP_GELU}, {"GELU_QUICK", GGML_UNARY_OP_GELU_QUICK}, {"SILU", GGML_UNARY_OP_SILU}, {"EXP", GGML_UNARY_OP_EXP},
+    {"GELU_ERF", GGML_UNARY_OP_GELU_ERF},
 };
 const NameNum kNeededTypes[] = {
     {"f32", GGML_TYPE_F32}, {"f16", GGML_TYPE_F16}, {"q4_0", GGML_TYPE_Q4_0}, {"q8_0", GGML_TYPE_Q8_0}, {"i32", GGML_TYPE_I32}, {"bf16", GGML_TYPE_BF16},
@@ -136,9 +137,9 @@ bool planner_build_op_maps(const char* (*op_name)(int), const char* (*unary_name
         err_len = sizeof(local);
     }
     static const char* const kOptionalOps[]   = {"CONV_2D"};
-    static const char* const kOptionalUnary[] = {"EXP"};
+    static const char* const kOptionalUnary[] = {"EXP", "GELU_ERF"};  // (a host without GELU_ERF never emits the node; the backend registers all the same)
     if (op_name && !build_map(op_name, kNeededOps, (int)(sizeof(kNeededOps) / sizeof(kNeededOps[0])), 200, GGML_OP_COUNT, ops, err, err_len, "op", kOptionalOps, 1)) return false;
-    if (unary_name && !build_map(unary_name, kNeededUnary, (int)(sizeof(kNeededUnary) / sizeof(kNeededUnary[0])), 64, GGML_UNARY_OP_COUNT, un, err, err_len, "unary op", kOptionalUnary, 1))
+    if (unary_name && !build_map(unary_name, kNeededUnary, (int)(sizeof(kNeededUnary) / sizeof(kNeededUnary[0])), 64, GGML_UNARY_OP_COUNT, un, err, err_len, "unary op", kOptionalUnary, 2))
         return false;
     if (type_name) {
         // type numbers are part of the GGUF file format and cannot drift without breaking every model file: verified, not remapped
@@ -168,7 +169,7 @@ std::atomic<int64_t> g_stat_counters[N_STATS];
 #define STAT(field) g_stat_counters[offsetof(ggml_backend_mi355x_stats, field) / sizeof(int64_t)]
 
 struct Options {
-    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1}, fuse_gn_epilogue{1}, fuse_tile_merge{1}, fuse_model_input{1}, fuse_guidance3{1}, fuse_ip_attn{1};
+    std::atomic<int> fusion{1}, mfma_gemm{1}, hip_graph{1}, flash_pattern{1}, fuse_modulate{1}, fuse_gate{1}, fuse_gelu{1}, fuse_rope{1}, fuse_concat_heads{1}, qgemv{1}, fuse_chan_add{1}, fuse_proj_tokens{1}, fuse_q16{1}, qgemm16{1}, fgemv{1}, fuse_siblings{1}, hoist_kv{1}, hoist_emb{1}, fuse_rows16{0}, fuse_cat_rows16{1}, fuse_joint_qkv{1}, jit_qimages{4096}, fuse_gn_stats{1}, fuse_ln_reduce{1}, relax_res_overlap{1}, fuse_split_gelu{1}, fuse_concat_gn{1}, fuse_gn_tokens{1}, fuse_linear_nchw{1}, fuse_conv_scale{1}, ignore_use_counts{0}, plan_cache_cap{512}, hoist_mod{1}, fuse_flash_slices{1}, fuse_act_pack{1}, fuse_gn_epilogue{1}, fuse_tile_merge{1}, fuse_model_input{1}, fuse_guidance3{1}, fuse_ip_attn{1}, fuse_patch_embed{0};
 } g_opt;
 
 using Step = std::function<void(hipStream_t)>;  // one launch (or a few) of a plan
@@ -2972,6 +2973,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                 case GGML_UNARY_OP_RELU: u = UN_RELU; break;
                 case GGML_UNARY_OP_NEG: u = UN_NEG; break;
                 case GGML_UNARY_OP_EXP: u = UN_EXP; break;
+                case GGML_UNARY_OP_GELU_ERF: u = UN_GELU_ERF; break;
                 default: return false;
             }
             const int64_t nel = ggml_abi_nelements(n);
@@ -4031,6 +4033,115 @@ bool plan_guidance3(Builder& B, int i, std::vector<int>& chain) {
     return true;
 }
 
+// CLIPVisionEmbeddings::forward (src/model/te/clip.hpp:224-235), anchored at the REPEAT of the class embedding (the chain's first node in graph order):
+//   cls4   = RESHAPE [1,E,1,N] of REPEAT(class [E] -> [E,N])
+//   patch4 = RESHAPE [1,E,np,N] of CONT(PERMUTE 1,0,2,3 of RESHAPE [np,E,N] of CONT(PERMUTE 0,1,3,2 of RESHAPE [G,G,N,E] of
+//            MUL_MAT(RESHAPE(IM2COL(w [P,P,3,E] f16, x [S,S,3,N]; stride P, padding 0, dilation 1)), RESHAPE(w)))))          (ggml_ext_conv_2d without a bias)
+//   out    = ADD(RESHAPE [E,np+1,N] of CONCAT(cls4, patch4, dim 2), pos [E,np+1])
+// -> ONE launch of k_patch_embed writing out.  None of the intermediates is written, so the match refuses whenever anything else could read one (a second consumer, an
+// OUTPUT flag, a reader outside a sub-graph view — GInfo::sole sees all three), a non-view node of another chain lies between, the pixel values are produced inside
+// this graph, a tensor has another type or layout, or the result shares memory with an operand.  A bias ADD, another stride, padding or dilation change the chain's
+// shape and run as plain nodes.
+bool plan_patch_embed(Builder& B, int i, std::vector<int>& chain) {
+    if (!g_opt.fusion || !g_opt.fuse_patch_embed || !g_opt.mfma_gemm) return false;
+    GInfo& gi              = B.gi;
+    const ggml_tensor* rep = gi.node(i);
+    const ggml_tensor* cls = rep->src[0];
+    if (!cls || gi.idx(cls) >= 0 || !is_f32(cls) || !contig(cls) || !is_f32(rep) || !contig(rep) || rep->ne[2] != 1 || rep->ne[3] != 1) return false;
+    const int64_t E = rep->ne[0], N = rep->ne[1];
+    if (ggml_abi_nelements(cls) != E || cls->ne[0] != E) return false;
+    const int jc4 = gi.sole(i);
+    if (jc4 < 0 || xop(gi.node(jc4)) != GGML_OP_RESHAPE || gi.node(jc4)->src[0] != rep) return false;
+    const ggml_tensor* cls4 = gi.node(jc4);
+    if (cls4->ne[0] != 1 || cls4->ne[1] != E || cls4->ne[2] != 1 || cls4->ne[3] != N) return false;
+    const int jcat = gi.sole(jc4);
+    if (jcat < 0) return false;
+    const ggml_tensor* cat = gi.node(jcat);
+    if (xop(cat) != GGML_OP_CONCAT || cat->op_params[0] != 2 || cat->src[0] != cls4 || !is_f32(cat) || !contig(cat)) return false;
+    // the patch operand, walked back to the IM2COL: every node read by the next one only
+    auto sole_src = [&](const ggml_tensor* t, enum ggml_op op, int reader) -> int {  // index of t when it is a node with that op whose only reader is `reader`
+        const int j = t ? gi.idx(t) : -1;
+        if (j <= i || gi.done[j] || xop(t) != op || gi.sole(j) != reader) return -1;
+        return j;
+    };
+    const int jp4 = sole_src(cat->src[1], GGML_OP_RESHAPE, jcat);
+    if (jp4 < 0) return false;
+    const ggml_tensor* p4 = gi.node(jp4);
+    const int64_t np      = p4->ne[2];
+    if (p4->ne[0] != 1 || p4->ne[1] != E || p4->ne[3] != N || np < 1) return false;
+    const int jc2 = sole_src(p4->src[0], GGML_OP_CONT, jp4);
+    if (jc2 < 0) return false;
+    const ggml_tensor* c2 = gi.node(jc2);
+    const int jpm2 = sole_src(c2->src[0], GGML_OP_PERMUTE, jc2);
+    if (jpm2 < 0) return false;
+    const ggml_tensor* pm2 = gi.node(jpm2);
+    const int jr3 = sole_src(pm2->src[0], GGML_OP_RESHAPE, jpm2);
+    if (jr3 < 0) return false;
+    const ggml_tensor* r3 = gi.node(jr3);
+    const int jc1 = sole_src(r3->src[0], GGML_OP_CONT, jr3);
+    if (jc1 < 0) return false;
+    const ggml_tensor* c1 = gi.node(jc1);
+    const int jpm1 = sole_src(c1->src[0], GGML_OP_PERMUTE, jc1);
+    if (jpm1 < 0) return false;
+    const ggml_tensor* pm1 = gi.node(jpm1);
+    const int jr4 = sole_src(pm1->src[0], GGML_OP_RESHAPE, jpm1);
+    if (jr4 < 0) return false;
+    const ggml_tensor* r4 = gi.node(jr4);
+    const int jmm = sole_src(r4->src[0], GGML_OP_MUL_MAT, jr4);
+    if (jmm < 0) return false;
+    const ggml_tensor* mm = gi.node(jmm);
+    const int jri = sole_src(mm->src[0], GGML_OP_RESHAPE, jmm);
+    if (jri < 0) return false;
+    const int jim = sole_src(gi.node(jri)->src[0], GGML_OP_IM2COL, jri);
+    if (jim < 0) return false;
+    const ggml_tensor* im = gi.node(jim);
+    const ggml_tensor *w = im->src[0], *x = im->src[1];
+    const ggml_tensor* wr = mm->src[1];  // RESHAPE of the weight
+    if (!w || !x || !wr || xop(wr) != GGML_OP_RESHAPE || wr->src[0] != w || gi.idx(w) >= 0 || gi.idx(x) >= 0) return false;
+    if (w->type != GGML_TYPE_F16 || !contig(w) || !is_f32(x) || !contig(x) || im->type != GGML_TYPE_F16 || !contig(im)) return false;
+    const int64_t Pk = w->ne[0], S = x->ne[0];
+    const int32_t* prm = im->op_params;
+    if (w->ne[1] != Pk || w->ne[2] != 3 || w->ne[3] != E || x->ne[1] != S || x->ne[2] != 3 || x->ne[3] != N) return false;
+    if (prm[0] != Pk || prm[1] != Pk || prm[2] != 0 || prm[3] != 0 || prm[4] != 1 || prm[5] != 1 || prm[6] != 1 || S % Pk != 0) return false;
+    const int64_t G = S / Pk, K = 3 * Pk * Pk;
+    if (np != G * G || im->ne[0] != K || im->ne[1] != G || im->ne[2] != G || im->ne[3] != N) return false;
+    // the layouts in between, by shape and stride (the two PERMUTEs are read off their strides)
+    if (!is_f32(mm) || !contig(mm) || mm->ne[0] != N * np || mm->ne[1] != E || mm->ne[2] != 1 || mm->ne[3] != 1) return false;
+    if (r4->ne[0] != G || r4->ne[1] != G || r4->ne[2] != N || r4->ne[3] != E || !contig(r4)) return false;
+    if (pm1->ne[0] != G || pm1->ne[1] != G || pm1->ne[2] != E || pm1->ne[3] != N || pm1->nb[0] != r4->nb[0] || pm1->nb[1] != r4->nb[1] || pm1->nb[2] != r4->nb[3] ||
+        pm1->nb[3] != r4->nb[2])
+        return false;
+    if (!is_f32(c1) || !contig(c1) || c1->ne[0] != G || c1->ne[1] != G || c1->ne[2] != E || c1->ne[3] != N) return false;
+    if (r3->ne[0] != np || r3->ne[1] != E || r3->ne[2] != N || r3->ne[3] != 1 || !contig(r3)) return false;
+    if (pm2->ne[0] != E || pm2->ne[1] != np || pm2->ne[2] != N || pm2->ne[3] != 1 || pm2->nb[0] != r3->nb[1] || pm2->nb[1] != r3->nb[0] || pm2->nb[2] != r3->nb[2]) return false;
+    if (!is_f32(c2) || !contig(c2) || c2->ne[0] != E || c2->ne[1] != np || c2->ne[2] != N || c2->ne[3] != 1 || !contig(p4)) return false;
+    if (cat->ne[0] != 1 || cat->ne[1] != E || cat->ne[2] != np + 1 || cat->ne[3] != N) return false;
+    // behind the CONCAT: RESHAPE [E, np + 1, N] -> ADD(., pos)
+    const int jr5 = gi.sole(jcat);
+    if (jr5 < 0 || xop(gi.node(jr5)) != GGML_OP_RESHAPE || gi.node(jr5)->src[0] != cat) return false;
+    const ggml_tensor* r5 = gi.node(jr5);
+    if (r5->ne[0] != E || r5->ne[1] != np + 1 || r5->ne[2] != N || r5->ne[3] != 1) return false;
+    const int jadd = gi.sole(jr5);
+    if (jadd < 0) return false;
+    const ggml_tensor* add = gi.node(jadd);
+    const ggml_tensor* pos = add->src[1];
+    if (xop(add) != GGML_OP_ADD || add->src[0] != r5 || !pos || gi.idx(pos) >= 0 || !is_f32(pos) || !contig(pos) || !is_f32(add) || !contig(add)) return false;
+    if (pos->ne[0] != E || pos->ne[1] != np + 1 || pos->ne[2] != 1 || pos->ne[3] != 1 || add->ne[0] != E || add->ne[1] != np + 1 || add->ne[2] != N || add->ne[3] != 1) return false;
+    if (!patch_embed_shape_ok(S, Pk, E, N)) return false;
+    chain = {i, jim, jmm, jc1, jc2, jcat, jadd};
+    if (!gi.only_noops_between(i, jadd, chain)) return false;
+    const size_t ob = ggml_abi_nbytes(add);
+    for (const ggml_tensor* t : {x, w, cls, pos})
+        if (overlaps(add->data, ob, t->data, ggml_abi_nbytes(t)) || B.clobbered_between(i, jadd, t->data, ggml_abi_nbytes(t), chain)) return false;
+    float* out       = (float*)add->data;
+    const float* xp  = (const float*)x->data;
+    const void* wp   = w->data;
+    const float *cp = (const float*)cls->data, *pp = (const float*)pos->data;
+    B.emit_at(jadd, i, [=](hipStream_t st) { launch_patch_embed(st, out, xp, wp, cp, pp, S, Pk, E, N); });
+    STAT(fused_patch_embed)++;
+    return true;
+}
+
 bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, bool no_redirect = false) {
     Builder B(P, plan, g);
     B.no_redirect = no_redirect;
@@ -4084,7 +4195,13 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                     ok = plan_model_input(B, i, chain);
                 }
                 break;
-            case GGML_OP_REPEAT: ok = plan_model_input(B, i, chain); break;
+            case GGML_OP_REPEAT:
+                ok = plan_patch_embed(B, i, chain);
+                if (!ok) {
+                    chain.clear();
+                    ok = plan_model_input(B, i, chain);
+                }
+                break;
             case GGML_OP_SUB: ok = plan_guidance3(B, i, chain); break;
             case GGML_OP_GROUP_NORM: ok = plan_group_norm(B, i, s, chain); break;
             case GGML_OP_NORM:
@@ -4511,6 +4628,7 @@ bool planner_supports_op(const ggml_tensor* n) {
                 case GGML_UNARY_OP_RELU:
                 case GGML_UNARY_OP_NEG:
                 case GGML_UNARY_OP_EXP:
+                case GGML_UNARY_OP_GELU_ERF:
                     return f32c(n) && f32c(n->src[0]) && ggml_abi_is_contiguous(n) && ggml_abi_is_contiguous(n->src[0]);
                 default:
                     return false;
@@ -4586,6 +4704,7 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     static_assert(offsetof(ggml_backend_mi355x_stats, g16_conv_wmajor) - offsetof(ggml_backend_mi355x_stats, c3w_tw16_bn256) == (CONV_ROUTE_COUNT - 1) * sizeof(int64_t),
                   "ggml_backend_mi355x_stats: one c3w_* / g16_conv_* field per ConvRoute, in its order");
     for (int r = 0; r < CONV_ROUTE_COUNT; ++r) (&o->c3w_tw16_bn256)[r] = conv_route_launches(r);
+    o->patch_embed_launches = patch_embed_launches();
     o->ew_model_input_v4 = model_input_route_launches(0);
     o->ew_model_input_v1 = model_input_route_launches(1);
     // ... and where the Linear launchers choose theirs: the lin_* fields lie in the order of LinearRoute
@@ -4631,6 +4750,7 @@ const OptionRow g_option_table[] = {
     OPT(fuse_tile_merge),  // MUL -> MUL -> { ADD in place | CPY } x k of a VAE tile batch's overlap merge as one gather launch (k_tile_merge)
     OPT(fuse_model_input),  // [MUL ->] [RESHAPE -> REPEAT -> RESHAPE ->] CONCAT(dim 2) with the [REPEATed] concat latent of an inpaint / pix2pix UNet as one launch (k_model_input)
     OPT(fuse_guidance3),  // the six nodes of the three-conditioning CFG combine as one launch (k_guidance3)
+    OPT(fuse_patch_embed),  // CLIPVisionEmbeddings (stride = kernel conv, class row, position table) as one launch of k_patch_embed; default 0: slower than the plain nodes at batch 1 (profiles/clip_vision_probe.txt)
     OPT(fuse_ip_attn),  // the two attentions of an IP-Adapter attn2 (text keys, image keys) + SCALE + ADD as one launch of k_flash_short_ip
     OPT(fuse_joint_qkv),
     OPT(fuse_ln_reduce),

@@ -283,6 +283,7 @@ const char* ggml_op_desc(const ggml_tensor* t) {
             case GGML_UNARY_OP_SIGMOID: return "SIGMOID";
             case GGML_UNARY_OP_TANH: return "TANH";
             case GGML_UNARY_OP_RELU: return "RELU";
+            case GGML_UNARY_OP_GELU_ERF: return "GELU_ERF";
             default: return "UNARY?";
         }
     }
@@ -602,6 +603,8 @@ ggml_tensor* ggml_gelu(ggml_context* ctx, ggml_tensor* a) { return unary_impl(ct
 ggml_tensor* ggml_gelu_inplace(ggml_context* ctx, ggml_tensor* a) { return unary_impl(ctx, a, GGML_UNARY_OP_GELU, true); }
 ggml_tensor* ggml_gelu_quick(ggml_context* ctx, ggml_tensor* a) { return unary_impl(ctx, a, GGML_UNARY_OP_GELU_QUICK, false); }
 ggml_tensor* ggml_gelu_quick_inplace(ggml_context* ctx, ggml_tensor* a) { return unary_impl(ctx, a, GGML_UNARY_OP_GELU_QUICK, true); }
+ggml_tensor* ggml_gelu_erf(ggml_context* ctx, ggml_tensor* a) { return unary_impl(ctx, a, GGML_UNARY_OP_GELU_ERF, false); }
+ggml_tensor* ggml_gelu_erf_inplace(ggml_context* ctx, ggml_tensor* a) { return unary_impl(ctx, a, GGML_UNARY_OP_GELU_ERF, true); }
 ggml_tensor* ggml_sigmoid(ggml_context* ctx, ggml_tensor* a) { return unary_impl(ctx, a, GGML_UNARY_OP_SIGMOID, false); }
 ggml_tensor* ggml_tanh(ggml_context* ctx, ggml_tensor* a) { return unary_impl(ctx, a, GGML_UNARY_OP_TANH, false); }
 ggml_tensor* ggml_relu(ggml_context* ctx, ggml_tensor* a) { return unary_impl(ctx, a, GGML_UNARY_OP_RELU, false); }

@@ -102,6 +102,8 @@ GGML_API struct ggml_tensor* ggml_gelu(struct ggml_context* ctx, struct ggml_ten
 GGML_API struct ggml_tensor* ggml_gelu_inplace(struct ggml_context* ctx, struct ggml_tensor* a);
 GGML_API struct ggml_tensor* ggml_gelu_quick(struct ggml_context* ctx, struct ggml_tensor* a);
 GGML_API struct ggml_tensor* ggml_gelu_quick_inplace(struct ggml_context* ctx, struct ggml_tensor* a);
+GGML_API struct ggml_tensor* ggml_gelu_erf(struct ggml_context* ctx, struct ggml_tensor* a);
+GGML_API struct ggml_tensor* ggml_gelu_erf_inplace(struct ggml_context* ctx, struct ggml_tensor* a);
 GGML_API struct ggml_tensor* ggml_sigmoid(struct ggml_context* ctx, struct ggml_tensor* a);
 GGML_API struct ggml_tensor* ggml_tanh(struct ggml_context* ctx, struct ggml_tensor* a);
 GGML_API struct ggml_tensor* ggml_relu(struct ggml_context* ctx, struct ggml_tensor* a);

@@ -30,6 +30,7 @@
 #include "ggml.h"
 #include "models.hpp"
 #include "conditioner.hpp"
+#include "clip_vision.hpp"
 #include "sampler.hpp"
 #include "step_cache.hpp"
 #include "preview.hpp"
@@ -686,6 +687,8 @@ struct sdm_ctx_t {
     // IP-Adapter (sd_ip_adapter_init): to_k_ip / to_v_ip of every attn2 and the image projection, in a weight buffer of their own — the resident weights stay untouched
     Runner ip_runner;
     ImageProjModel ip_proj;
+    Resampler ip_resampler;  // the "plus" adapters' projection: the context holds one of the two (ip_plus)
+    bool ip_plus = false;
     bool ip_ready = false;
     int64_t ip_dim = 0, ip_clip_dim = 0, ip_num_tokens = 0;
     // sd_set_ip_adapter: the image tokens of the sampling entries, [ip_dim, ip_set_n] each — `ip_tokens` for the cond branch, `ip_uncond` for every other branch
@@ -708,9 +711,14 @@ struct sdm_ctx_t {
         const float* data = nullptr;
         int ip_n          = 0;
     } ip_call;
+    // CLIP vision tower (sd_clip_vision_init / sd_load_clip_vision): parameters in a weight buffer of their own
+    Runner cv_runner;
+    ClipVisionModel clip_vision;
+    bool cv_ready = false;
     std::vector<Runner*> runners() {
         std::vector<Runner*> v{&unet_runner, &vae_runner};
         if (ip_ready) v.push_back(&ip_runner);
+        if (cv_ready) v.push_back(&cv_runner);
         if (tae_ready) v.push_back(&tae_runner);
         if (vae_enc_ready) v.push_back(&vae_enc_runner);
         if (te) {
@@ -1541,7 +1549,7 @@ bool sd_ip_adapter_init(sdm_ctx_t* ctx, int64_t ip_dim, int64_t clip_dim, int64_
         return false;
     }
     if (ctx->ip_ready) {
-        if (ip_dim == ctx->ip_dim && clip_dim == ctx->ip_clip_dim && num_tokens == ctx->ip_num_tokens) return true;
+        if (!ctx->ip_plus && ip_dim == ctx->ip_dim && clip_dim == ctx->ip_clip_dim && num_tokens == ctx->ip_num_tokens) return true;
         set_error("sd_ip_adapter_init: an adapter with other dimensions (ip_dim " + std::to_string(ctx->ip_dim) + ", clip_dim " + std::to_string(ctx->ip_clip_dim) + ", " +
                   std::to_string(ctx->ip_num_tokens) + " tokens) is initialised on this context already");
         return false;
@@ -1569,6 +1577,7 @@ bool sd_ip_adapter_init(sdm_ctx_t* ctx, int64_t ip_dim, int64_t clip_dim, int64_
 // An adapter file ("ip_adapter.<idx>.to_{k,v}_ip.weight", "image_proj.{proj,norm}.*"; names converted by ip_adapter_to_ldm): the dimensions are read from its shapes as
 // IPAdapterRunner reads them (ip_adapter.hpp:159-175) — ip_dim = to_k_ip's input width, clip_dim = proj's, num_tokens = proj's rows / norm's width — the adapter is
 // initialised from them if it is not yet, and the file's tensors are bound to the adapter's parameters only.  Returns the number loaded, -1 on error.
+bool sd_ip_adapter_init_plus(sdm_ctx_t* ctx, int64_t ip_dim, int64_t dim, int64_t depth, int64_t num_queries, int64_t embed_dim, int64_t ff_inner, uint64_t weight_seed);
 int64_t sd_load_ip_adapter(sdm_ctx_t* ctx, const char* path, int64_t* n_missing, int64_t* n_unused) {
     if (ctx->is_dit) {
         set_error("sd_load_ip_adapter: the IP-Adapter exists for the UNet families (SD15, SDXL and their tiny forms) only");
@@ -1581,6 +1590,26 @@ int64_t sd_load_ip_adapter(sdm_ctx_t* ctx, const char* path, int64_t* n_missing,
     }
     const NameDialect dialect = name_dialect(ctx);
     int64_t ip_dim = 0, clip_dim = 0, proj_rows = 0, norm_dim = 0;
+    // a "plus" file (ip_adapter.hpp:128-158): told by image_proj.latents; the Resampler's shapes as IPAdapterRunner reads them, with its defaults where a tensor is absent
+    bool is_plus = false;
+    int64_t rs_dim = 1280, rs_queries = 16, rs_embed = 1280, rs_out = 2048, rs_ff = 5120, rs_depth = 0;
+    std::map<std::string, bool> plus_q;
+    for (const FileTensor& t : mf.tensors) {
+        const std::string c = canonical_tensor_name(t.name, dialect);
+        const std::string ipp = "ip_adapter.image_proj.";
+        if (c.rfind(ipp, 0) != 0) continue;
+        const std::string r = c.substr(ipp.size());
+        if (r == "latents") is_plus = true, rs_dim = t.ne[0], rs_queries = t.ne[1];
+        if (r == "proj_in.weight") rs_embed = t.ne[0];
+        if (r == "proj_out.weight") rs_out = t.ne[1];
+        if (r == "layers.0.1.1.weight") rs_ff = t.ne[1];
+        plus_q[r] = true;
+    }
+    if (is_plus) {
+        while (plus_q.count("layers." + std::to_string(rs_depth) + ".0.to_q.weight")) ++rs_depth;
+        if (!sd_ip_adapter_init_plus(ctx, rs_out, rs_dim, rs_depth, rs_queries, rs_embed, rs_ff, ctx->params.weight_seed)) return -1;
+        return load_weights_scoped(ctx, path, nullptr, n_missing, n_unused, &ctx->ip_runner.ps.by_name);
+    }
     for (const FileTensor& t : mf.tensors) {
         const std::string c = canonical_tensor_name(t.name, dialect);
         const std::string tail = "attn2.to_k_ip.weight";
@@ -1592,7 +1621,7 @@ int64_t sd_load_ip_adapter(sdm_ctx_t* ctx, const char* path, int64_t* n_missing,
         if (c == "ip_adapter.image_proj.norm.weight") norm_dim = t.ne[0];
     }
     if (ip_dim < 1 || clip_dim < 1 || norm_dim < 1 || proj_rows % norm_dim != 0) {
-        set_error("sd_load_ip_adapter: the file holds no to_k_ip weight of this family's cross-attentions, or no image_proj.proj / image_proj.norm (the Resampler of the \"plus\" adapters is not supported)");
+        set_error("sd_load_ip_adapter: the file holds no to_k_ip weight of this family's cross-attentions, or neither image_proj.proj / image_proj.norm (a plain adapter) nor image_proj.latents (a plus adapter)");
         return -1;
     }
     if (norm_dim != ip_dim) {
@@ -1609,6 +1638,43 @@ bool sd_ip_adapter_info(sdm_ctx_t* ctx, int64_t* ip_dim, int64_t* clip_dim, int6
     if (num_tokens) *num_tokens = ctx->ip_num_tokens;
     return true;
 }
+// The general form: embeds [clip_dim, n_tok, n] (n_tok = 1 on a plain adapter, the tower's token count on a plus one) -> image tokens [ip_dim, num_tokens, n]
+bool sd_ip_adapter_project_tokens(sdm_ctx_t* ctx, const float* embeds, int64_t n_tok, int n, float* tokens_out) {
+    if (!ctx->ip_ready) {
+        set_error("sd_ip_adapter_project_tokens: no IP-Adapter is initialised on this context (sd_ip_adapter_init / sd_ip_adapter_init_plus)");
+        return false;
+    }
+    if (!embeds || !tokens_out || n < 1 || n_tok < 1) {
+        set_error("sd_ip_adapter_project_tokens: bad arguments");
+        return false;
+    }
+    if (!ctx->ip_plus) {
+        if (n_tok != 1) {
+            set_error("sd_ip_adapter_project_tokens: a plain adapter (ImageProjModel) takes one embedding per image");
+            return false;
+        }
+        return sd_ip_adapter_project(ctx, embeds, n, tokens_out);
+    }
+    if (g_graph_capture != 2) {  // the Resampler's feed-forward is GELU_ERF: ask the backend before a graph with it is submitted (a describe-only capture submits none)
+        ggml_init_params ip{ggml_tensor_overhead() * 4, nullptr, true};
+        ggml_context* pc  = ggml_init(ip);
+        ggml_tensor* node = ggml_gelu_erf(pc, ggml_new_tensor_1d(pc, GGML_TYPE_F32, 4));
+        const bool ok     = ggml_backend_supports_op(ctx->backend, node);
+        ggml_free(pc);
+        if (!ok) {
+            set_error("sd_ip_adapter_project: the Resampler needs GELU_ERF, which this backend does not support");
+            return false;
+        }
+    }
+    auto build = [&](GraphCtx& g, std::vector<HostInput>& in) {
+        g.flash_attn    = ctx->params.diffusion_flash_attn;
+        ggml_tensor* te = ggml_new_tensor_3d(g.ctx, GGML_TYPE_F32, ctx->ip_clip_dim, n_tok, n);
+        ggml_set_input(te);
+        in.push_back({te, embeds, ggml_nbytes(te)});
+        return ctx->ip_resampler.forward(g, te);
+    };
+    return ctx->ip_runner.compute(build, tokens_out, (size_t)ctx->ip_dim * ctx->ip_num_tokens * n * sizeof(float));
+}
 // CLIP image embeddings [clip_dim, n] -> image tokens [ip_dim, num_tokens, n]: a small graph of its own on the context's backend
 bool sd_ip_adapter_project(sdm_ctx_t* ctx, const float* embeds, int n, float* tokens_out) {
     if (!ctx->ip_ready) {
@@ -1618,6 +1684,13 @@ bool sd_ip_adapter_project(sdm_ctx_t* ctx, const float* embeds, int n, float* to
     if (!embeds || !tokens_out || n < 1) {
         set_error("sd_ip_adapter_project: bad arguments");
         return false;
+    }
+    if (ctx->ip_plus) {  // hidden states [embed_dim, n_tok, n] of the initialised tower
+        if (!ctx->cv_ready) {
+            set_error("sd_ip_adapter_project: a plus adapter takes [embed_dim, n_tok, n] hidden states; without a vision tower on this context their token count is unknown (sd_ip_adapter_project_tokens)");
+            return false;
+        }
+        return sd_ip_adapter_project_tokens(ctx, embeds, ctx->clip_vision.cfg.num_positions(), n, tokens_out);
     }
     auto build = [&](GraphCtx& g, std::vector<HostInput>& in) {
         ggml_tensor* te = ggml_new_tensor_2d(g.ctx, GGML_TYPE_F32, ctx->ip_clip_dim, n);
@@ -1656,8 +1729,13 @@ bool sd_set_ip_adapter(sdm_ctx_t* ctx, const float* tokens, const float* uncond_
                       " cond tokens uncond_tokens must be given");
             return false;
         }
-        const std::vector<float> zero((size_t)ctx->ip_clip_dim, 0.f);
-        if (!sd_ip_adapter_project(ctx, zero.data(), 1, un.data())) return false;
+        const int64_t zt = ctx->ip_plus ? (ctx->cv_ready ? ctx->clip_vision.cfg.num_positions() : 0) : 1;
+        if (zt < 1) {
+            set_error("sd_set_ip_adapter: the default uncond tokens of a plus adapter are the Resampler's output for all-zero hidden states of the tower's shape; without a vision tower uncond_tokens must be given");
+            return false;
+        }
+        const std::vector<float> zero((size_t)(ctx->ip_clip_dim * zt), 0.f);
+        if (!sd_ip_adapter_project_tokens(ctx, zero.data(), zt, 1, un.data())) return false;
     }
     ctx->ip_tokens.assign(tokens, tokens + cnt);
     ctx->ip_uncond   = std::move(un);
@@ -1670,6 +1748,10 @@ bool sd_set_ip_adapter_embeds(sdm_ctx_t* ctx, const float* embeds, float strengt
     if (!embeds) return sd_set_ip_adapter(ctx, nullptr, nullptr, 0, 0.f);
     if (!ctx->ip_ready) {
         set_error("sd_set_ip_adapter_embeds: no IP-Adapter is initialised on this context (sd_ip_adapter_init / sd_load_ip_adapter)");
+        return false;
+    }
+    if (ctx->ip_plus) {
+        set_error("sd_set_ip_adapter_embeds: a plus adapter projects hidden states, not one embedding (sd_set_ip_adapter_image, or sd_ip_adapter_project_tokens + sd_set_ip_adapter)");
         return false;
     }
     std::vector<float> tok((size_t)ctx->ip_dim * (size_t)ctx->ip_num_tokens);
@@ -1693,6 +1775,226 @@ bool sd_unet_forward_ip(sdm_ctx_t* ctx, const float* x, int w, int h, int c, int
         return false;
     }
     return unet_forward_skip(ctx, x, w, h, c, n, timesteps, context, ctx_dim, n_tokens, ctx_n, y, y_dim, y_n, out, nullptr, c_concat, cc, concat_n, ip_context, n_ip, ip_n, ip_scale);
+}
+// ---- the "plus" adapters: Resampler (ip_adapter.hpp:34-113) in place of the ImageProjModel ------------------------------------------------
+bool sd_ip_adapter_init_plus(sdm_ctx_t* ctx, int64_t ip_dim, int64_t dim, int64_t depth, int64_t num_queries, int64_t embed_dim, int64_t ff_inner, uint64_t weight_seed) {
+    if (ctx->is_dit) {
+        set_error("sd_ip_adapter_init_plus: the IP-Adapter exists for the UNet families (SD15, SDXL and their tiny forms) only");
+        return false;
+    }
+    if (ip_dim < 1 || dim < 64 || dim % 64 != 0 || depth < 1 || num_queries < 1 || embed_dim < 1 || ff_inner < 1) {
+        set_error("sd_ip_adapter_init_plus: every dimension must be positive and dim a multiple of the head size 64");
+        return false;
+    }
+    if (ctx->ip_ready) {
+        const Resampler& r = ctx->ip_resampler;
+        if (ctx->ip_plus && ip_dim == ctx->ip_dim && dim == r.dim && depth == r.depth && num_queries == r.num_queries && embed_dim == r.embed_dim && ff_inner == r.ff_inner) return true;
+        set_error("sd_ip_adapter_init_plus: another adapter (ip_dim " + std::to_string(ctx->ip_dim) + ", " + (ctx->ip_plus ? "plus" : "plain") + ") is initialised on this context already");
+        return false;
+    }
+    Runner& r        = ctx->ip_runner;
+    r.backend        = ctx->backend;
+    r.ps.linear_type = (ggml_type)ctx->params.wtype;
+    r.graph_size     = 1024;  // IPAdapterRunner::build_graph, ip_adapter.hpp:191
+    ctx->unet.init_ip_adapter(r.ps, ip_dim);
+    ctx->ip_resampler.init(r.ps, "ip_adapter.image_proj.", dim, depth, num_queries, embed_dim, ip_dim, ff_inner);
+    if (!r.alloc_weights(weight_seed)) {
+        ctx->unet.drop_ip_adapter();
+        set_error("IP-Adapter weight buffer allocation failed");
+        return false;
+    }
+    for (auto& sp : r.ps.specs) ctx->all_tensors.push_back({sp.name, sp.tensor});
+    ctx->stats.weight_bytes += ggml_backend_buffer_get_size(r.weights);
+    ctx->ip_dim        = ip_dim;
+    ctx->ip_clip_dim   = embed_dim;
+    ctx->ip_num_tokens = num_queries;
+    ctx->ip_plus       = true;
+    ctx->ip_ready      = true;
+    ctx->unet_runner.drop_cache();
+    return true;
+}
+bool sd_ip_adapter_info_ex(sdm_ctx_t* ctx, int64_t* ip_dim, int64_t* clip_dim, int64_t* num_tokens, bool* is_plus) {
+    if (!sd_ip_adapter_info(ctx, ip_dim, clip_dim, num_tokens)) return false;
+    if (is_plus) *is_plus = ctx->ip_plus;
+    return true;
+}
+
+// ---- CLIP vision tower (clip.hpp:183-238, 332-464; FrozenCLIPVisionEmbedder, conditioner.hpp:561-613) ------------------------------------
+static bool clip_vision_init_cfg(sdm_ctx_t* ctx, const ClipVisionConfig& c, uint64_t weight_seed) {
+    if (c.hidden_size < 1 || c.n_head < 1 || c.hidden_size % c.n_head != 0 || c.n_layer < 1 || c.patch_size < 1 || c.image_size < c.patch_size || c.image_size % c.patch_size != 0 ||
+        c.projection_dim < 1) {
+        set_error("sd_clip_vision_init: hidden must be a positive multiple of heads, layers and projection positive, image_size a positive multiple of patch_size");
+        return false;
+    }
+    if (ctx->cv_ready) {
+        const ClipVisionConfig& o = ctx->clip_vision.cfg;
+        if (o.hidden_size == c.hidden_size && o.intermediate_size == c.intermediate_size && o.n_head == c.n_head && o.n_layer == c.n_layer && o.image_size == c.image_size &&
+            o.patch_size == c.patch_size && o.projection_dim == c.projection_dim)
+            return true;
+        set_error("sd_clip_vision_init: a vision tower of another shape is initialised on this context already");
+        return false;
+    }
+    Runner& r        = ctx->cv_runner;
+    r.backend        = ctx->backend;
+    r.ps.linear_type = (ggml_type)ctx->params.wtype;
+    r.graph_size     = 4096;
+    ctx->clip_vision.init(r.ps, "clip_vision.", c);
+    if (!r.alloc_weights(weight_seed)) {
+        set_error("CLIP vision tower weight buffer allocation failed");
+        return false;
+    }
+    for (auto& sp : r.ps.specs) ctx->all_tensors.push_back({sp.name, sp.tensor});
+    ctx->stats.weight_bytes += ggml_backend_buffer_get_size(r.weights);
+    ctx->cv_ready = true;
+    return true;
+}
+bool sd_clip_vision_init(sdm_ctx_t* ctx, int version, const sd_clip_vision_tiny_t* tiny, uint64_t weight_seed) {
+    ClipVisionConfig c;
+    if (tiny) {
+        c = ClipVisionConfig::tiny(tiny->hidden_size, tiny->n_head, tiny->n_layer, tiny->image_size, tiny->patch_size, tiny->projection_dim);
+    } else if (version == CLIP_VIT_L_14) {
+        c = ClipVisionConfig::vit_l();
+    } else if (version == CLIP_VIT_H_14) {
+        c = ClipVisionConfig::vit_h();
+    } else if (version == CLIP_VIT_BIGG_14) {
+        c = ClipVisionConfig::vit_bigg();
+    } else {
+        set_error("sd_clip_vision_init: version is 0 (ViT-L/14), 1 (ViT-H/14) or 2 (ViT-bigG/14), or a tiny configuration is given");
+        return false;
+    }
+    return clip_vision_init_cfg(ctx, c, weight_seed);
+}
+bool sd_clip_vision_info(sdm_ctx_t* ctx, sd_clip_vision_info_t* out) {
+    if (!ctx->cv_ready || !out) return false;
+    const ClipVisionConfig& c = ctx->clip_vision.cfg;
+    out->image_size = c.image_size, out->patch_size = c.patch_size, out->hidden_size = c.hidden_size, out->intermediate_size = c.intermediate_size, out->n_head = c.n_head;
+    out->n_layer = c.n_layer, out->projection_dim = c.projection_dim, out->num_positions = c.num_positions(), out->use_gelu = c.use_gelu ? 1 : 0;
+    return true;
+}
+// A tower file (HF CLIPVisionModelWithProjection names): loaded under the "clip_vision." prefix with the reference's rule (name_conversion.cpp:1473: the prefix becomes
+// the cond-stage tower's, whose conversion leaves the HF vision tree alone but for "vision_model.visual_projection.weight" -> "visual_projection.weight").  The version is
+// read off the file's shapes: hidden from the class embedding, layers counted, intermediate from fc1, projection from visual_projection, patch and image size from the
+// patch weight and the position table; heads are 16 on every full-size tower, hidden / 64 otherwise.
+int64_t sd_load_clip_vision(sdm_ctx_t* ctx, const char* path, int64_t* n_missing, int64_t* n_unused) {
+    ModelFile mf;
+    if (!path || !read_model_file(path, mf)) {
+        set_error(path ? mf.error : std::string("sd_load_clip_vision: NULL path"));
+        return -1;
+    }
+    const NameDialect dialect = name_dialect(ctx);
+    const std::string vm      = "clip_vision.vision_model.";
+    int64_t hidden = 0, inter = 0, proj = 0, patch = 0, positions = 0, layers = 0;
+    std::map<std::string, bool> seen;
+    for (const FileTensor& t : mf.tensors) {
+        const std::string c = canonical_tensor_name("clip_vision." + t.name, dialect);
+        seen[c]             = true;
+        if (c == vm + "embeddings.class_embedding") hidden = t.ne[0];
+        if (c == vm + "embeddings.patch_embedding.weight") patch = t.ne[0];
+        if (c == vm + "embeddings.position_embedding.weight") positions = t.ne[1];
+        if (c == vm + "encoder.layers.0.mlp.fc1.weight") inter = t.ne[1];
+        if (c == "clip_vision.visual_projection.weight") proj = t.ne[1];
+    }
+    while (seen.count(vm + "encoder.layers." + std::to_string(layers) + ".layer_norm1.weight")) ++layers;
+    int64_t grid = 0;
+    while ((grid + 1) * (grid + 1) + 1 <= positions) ++grid;
+    if (hidden < 1 || inter < 1 || proj < 1 || patch < 1 || layers < 1 || grid < 1 || grid * grid + 1 != positions) {
+        set_error("sd_load_clip_vision: the file is no CLIP vision tower with projection (class_embedding, patch_embedding, position_embedding, encoder layers, visual_projection)");
+        return -1;
+    }
+    ClipVisionConfig c;
+    c.hidden_size = hidden, c.intermediate_size = inter, c.n_layer = layers, c.projection_dim = proj, c.patch_size = patch, c.image_size = grid * patch;
+    c.n_head   = (hidden == 1024 || hidden == 1280 || hidden == 1664) ? 16 : std::max<int64_t>(hidden / 64, 1);
+    c.version  = hidden == 1280 ? CLIP_VIT_H_14 : (hidden == 1664 ? CLIP_VIT_BIGG_14 : CLIP_VIT_L_14);
+    c.use_gelu = ClipVisionConfig::gelu_rule(hidden);
+    if (!clip_vision_init_cfg(ctx, c, ctx->params.weight_seed)) return -1;
+    return load_weights_scoped(ctx, path, "clip_vision.", n_missing, n_unused, &ctx->cv_runner.ps.by_name);
+}
+// n u8 HWC RGB pictures [n][h][w][3] -> pixel values [S, S, 3, n], S = the tower's image size: the kernel on a backend that exports it, the host restatement on others
+static bool clip_preprocess_size(sdm_ctx_t* ctx, const uint8_t* images, int w, int h, int n, int S, float* out) {
+    if (!images || !out || w < 1 || h < 1 || n < 1 || S < 1) {
+        set_error("sd_clip_preprocess: bad arguments");
+        return false;
+    }
+    std::vector<int32_t> xi, yi;
+    clip_preprocess_tables(w, h, S, xi, yi);
+    typedef bool (*pre_fn)(ggml_backend_t, const uint8_t*, int, int, int64_t, int, const int*, const int*, float*);
+    ggml_backend_dev_t dev = ggml_backend_get_device(ctx->backend);
+    ggml_backend_reg_t reg = dev ? ggml_backend_dev_backend_reg(dev) : nullptr;
+    pre_fn k               = reg ? (pre_fn)ggml_backend_reg_get_proc_address(reg, "ggml_backend_mi355x_clip_preprocess") : nullptr;
+    if (k) {
+        if (!k(ctx->backend, images, w, h, n, S, xi.data(), yi.data(), out)) {
+            set_error("sd_clip_preprocess: the preprocessing pass could not be run");
+            return false;
+        }
+        return true;
+    }
+    if (reg && strcmp(ggml_backend_reg_name(reg), "MI355X") == 0) {  // never a quiet fall-back on the product backend
+        set_error("sd_clip_preprocess: the MI355X backend does not export ggml_backend_mi355x_clip_preprocess");
+        return false;
+    }
+    clip_preprocess_host(images, w, h, n, S, xi, yi, out);
+    return true;
+}
+bool sd_clip_preprocess_size(sdm_ctx_t* ctx, const uint8_t* images, int w, int h, int n, int size, float* out) { return clip_preprocess_size(ctx, images, w, h, n, size, out); }
+bool sd_clip_preprocess(sdm_ctx_t* ctx, const uint8_t* images, int w, int h, int n, float* out) {
+    if (!ctx->cv_ready) {
+        set_error("sd_clip_preprocess: no vision tower is initialised on this context (sd_clip_vision_init / sd_load_clip_vision); sd_clip_preprocess_size takes the size itself");
+        return false;
+    }
+    return clip_preprocess_size(ctx, images, w, h, n, (int)ctx->clip_vision.cfg.image_size, out);
+}
+// pixel_values [S, S, 3, n] -> pooled [projection_dim, n], or the hidden state before post_layernorm [hidden, num_positions, n] (clip_skip as CLIPEncoder reads it)
+bool sd_clip_vision_encode(sdm_ctx_t* ctx, const float* pixel_values, int n, bool return_pooled, int clip_skip, float* out) {
+    if (!ctx->cv_ready) {
+        set_error("sd_clip_vision_encode: no vision tower is initialised on this context (sd_clip_vision_init / sd_load_clip_vision)");
+        return false;
+    }
+    const ClipVisionConfig& c = ctx->clip_vision.cfg;
+    if (!pixel_values || !out || n < 1) {
+        set_error("sd_clip_vision_encode: bad arguments");
+        return false;
+    }
+    auto build = [&](GraphCtx& g, std::vector<HostInput>& in) {
+        g.flash_attn    = ctx->params.diffusion_flash_attn;
+        g.conv_direct   = ctx->params.diffusion_conv_direct;
+        ggml_tensor* px = ggml_new_tensor_4d(g.ctx, GGML_TYPE_F32, c.image_size, c.image_size, c.num_channels, n);
+        ggml_set_input(px);
+        in.push_back({px, pixel_values, ggml_nbytes(px)});
+        return ctx->clip_vision.forward(g, px, return_pooled, clip_skip);
+    };
+    const size_t cnt = (size_t)(return_pooled ? c.projection_dim : c.hidden_size * c.num_positions()) * (size_t)n;
+    return ctx->cv_runner.compute(build, out, cnt * sizeof(float));
+}
+// compute_ip_adapter_tokens (stable-diffusion.cpp:2187-2215): preprocess, encode (pooled; the penultimate hidden state for a plus adapter), project; the uncond tokens
+// are the projection of an all-zero embedding of the same shape
+bool sd_set_ip_adapter_image(sdm_ctx_t* ctx, const uint8_t* image, int w, int h, float strength) {
+    if (!image) return sd_set_ip_adapter(ctx, nullptr, nullptr, 0, 0.f);
+    if (!ctx->ip_ready) {
+        set_error("sd_set_ip_adapter_image: no IP-Adapter is initialised on this context (sd_ip_adapter_init / _init_plus / sd_load_ip_adapter)");
+        return false;
+    }
+    if (!ctx->cv_ready) {
+        set_error("sd_set_ip_adapter_image: no vision tower is initialised on this context (sd_clip_vision_init / sd_load_clip_vision)");
+        return false;
+    }
+    const ClipVisionConfig& c = ctx->clip_vision.cfg;
+    const int64_t width       = ctx->ip_plus ? c.hidden_size : c.projection_dim;
+    if (width != ctx->ip_clip_dim) {
+        set_error("sd_set_ip_adapter_image: the tower hands the adapter " + std::to_string(width) + (ctx->ip_plus ? "-wide hidden states" : "-wide embeddings") + ", the adapter expects " +
+                  std::to_string(ctx->ip_clip_dim));
+        return false;
+    }
+    std::vector<float> px((size_t)(c.image_size * c.image_size * 3));
+    if (!sd_clip_preprocess(ctx, image, w, h, 1, px.data())) return false;
+    const int64_t n_tok = ctx->ip_plus ? c.num_positions() : 1;
+    std::vector<float> embed((size_t)(width * n_tok));
+    if (!sd_clip_vision_encode(ctx, px.data(), 1, !ctx->ip_plus, ctx->ip_plus ? 2 : -1, embed.data())) return false;
+    const size_t cnt = (size_t)ctx->ip_dim * (size_t)ctx->ip_num_tokens;
+    std::vector<float> tok(cnt), un(cnt);
+    if (!sd_ip_adapter_project_tokens(ctx, embed.data(), n_tok, 1, tok.data())) return false;
+    std::fill(embed.begin(), embed.end(), 0.f);
+    if (!sd_ip_adapter_project_tokens(ctx, embed.data(), n_tok, 1, un.data())) return false;
+    return sd_set_ip_adapter(ctx, tok.data(), un.data(), ctx->ip_num_tokens, strength);
 }
 int sd_unet_variant(sdm_ctx_t* ctx) { return ctx->variant; }
 int sd_concat_channels(sdm_ctx_t* ctx) { return ctx->concat_channels(); }

@@ -9,6 +9,7 @@
 // the tiny test widths.  Only the dialects of the engine's model families are handled (no LoRA / ControlNet / video models).
 #pragma once
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -318,6 +319,25 @@ inline std::string ip_adapter_to_ldm(const std::string& name, bool sdxl) {
 inline std::string canonical_tensor_name(const std::string& raw, const NameDialect& d) {
     using namespace nameconv;
     if (d.unet_family && (starts_with(raw, "ip_adapter.") || starts_with(raw, "image_proj."))) return ip_adapter_to_ldm(raw, d.sdxl);  // name_conversion.cpp:1351-1353
+    if (starts_with(raw, "clip_vision.")) {
+        // name_conversion.cpp:1473 makes the prefix "cond_stage_model.transformer."; the cond-stage rule (:1523-1532, :106-185) then sees "transformer." + rest.  Of
+        // convert_open_clip_to_hf_clip_name (:35-104) only the exact-match table of :67-70 can apply to a name that starts with "transformer." — HF spells the tower's
+        // first norm "pre_layrnorm" — the OpenCLIP tables (:36-65, :80-101) key on names starting with "model." and never match under this prefix; then the substring
+        // table of :107-111, in its order.  The engine keeps the tower under its own prefix (the reference's "cond_stage_model.transformer." is the text tower's here).
+        std::string n = "transformer." + raw.substr(12);
+        if (n == "transformer.vision_model.pre_layrnorm.weight") n = "transformer.vision_model.pre_layernorm.weight";
+        if (n == "transformer.vision_model.pre_layrnorm.bias") n = "transformer.vision_model.pre_layernorm.bias";
+        static const std::pair<const char*, const char*> clip_name_map[] = {
+            {"transformer.text_projection.weight", "transformer.text_model.text_projection"},
+            {"model.text_projection.weight", "transformer.text_model.text_projection"},
+            {"vision_model.visual_projection.weight", "visual_projection.weight"},
+        };
+        for (const auto& kv : clip_name_map) {
+            const size_t at = n.find(kv.first);
+            if (at != std::string::npos) n.replace(at, strlen(kv.first), kv.second);
+        }
+        return "clip_vision." + (starts_with(n, "transformer.") ? n.substr(12) : n);
+    }
     const std::string MDM = "model.diffusion_model.", FSM = "first_stage_model.";
     const std::string L = d.unet_family ? "cond_stage_model." : "text_encoders.clip_l.";
     const std::string G = d.unet_family ? "cond_stage_model.1." : "text_encoders.clip_g.";

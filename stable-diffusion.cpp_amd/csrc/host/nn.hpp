@@ -438,8 +438,7 @@ struct SpatialTransformer {
 };
 
 // ImageProjModel — src/model/adapter/ip_adapter.hpp:10-32: Linear(clip_dim -> num_tokens * ctx_dim) + bias, reshape to [ctx_dim, num_tokens, N],
-// LayerNorm over ctx_dim.  (The Resampler of the "plus" adapters needs GELU_ERF, which neither this front-end nor the backends implement: out of scope,
-// a caller with plus tokens passes them as tokens directly.)
+// LayerNorm over ctx_dim.  (The Resampler of the "plus" adapters and the CLIP vision tower in front of both: clip_vision.hpp.)
 struct ImageProjModel {
     int64_t clip_dim = 0, ctx_dim = 0, num_tokens = 0;
     Linear proj;

@@ -72,6 +72,7 @@ __device__ __forceinline__ float act_apply(float x) {
     if (OP == UN_TANH) return tanhf(x);
     if (OP == UN_RELU) return x > 0.f ? x : 0.f;
     if (OP == UN_NEG) return -x;
+    if (OP == UN_GELU_ERF) return 0.5f * x * (1.0f + erff(x * 0.70710678f));  // the exact GELU (ggml_gelu_erf): library erff, no fast approximation
     return expf(x);  // the EXP node is the library exp: __expf flushes a subnormal result to zero (exp(-88) = 6.05e-39, which ggml-cpu's expf keeps)
 }
 __device__ __forceinline__ float act_dyn(int op, float x) {
@@ -84,6 +85,7 @@ __device__ __forceinline__ float act_dyn(int op, float x) {
         case UN_RELU: return act_apply<UN_RELU>(x);
         case UN_NEG: return -x;
         case UN_EXP: return expf(x);
+        case UN_GELU_ERF: return act_apply<UN_GELU_ERF>(x);
         default: return x;
     }
 }

@@ -273,7 +273,7 @@ void launch_unary(hipStream_t s, UnOp op, float* dst, const float* src, int64_t 
     const int block = 256, grid = grid_for(n / 4 + 1, block);
 #define U(OPV) case OPV: k_unary<OPV><<<grid, block, 0, s>>>(dst, src, n); break;
     switch (op) {
-        U(UN_SILU) U(UN_GELU) U(UN_GELU_QUICK) U(UN_SIGMOID) U(UN_TANH) U(UN_RELU) U(UN_NEG) U(UN_EXP)
+        U(UN_SILU) U(UN_GELU) U(UN_GELU_QUICK) U(UN_SIGMOID) U(UN_TANH) U(UN_RELU) U(UN_NEG) U(UN_EXP) U(UN_GELU_ERF)
     }
 #undef U
 }

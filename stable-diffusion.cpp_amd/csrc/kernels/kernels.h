@@ -16,7 +16,7 @@ struct View4 {
 };
 
 enum BinOp { BIN_ADD = 0, BIN_SUB = 1, BIN_MUL = 2, BIN_DIV = 3 };
-enum UnOp { UN_SILU = 0, UN_GELU = 1, UN_GELU_QUICK = 2, UN_SIGMOID = 3, UN_TANH = 4, UN_RELU = 5, UN_NEG = 6, UN_EXP = 7 };
+enum UnOp { UN_SILU = 0, UN_GELU = 1, UN_GELU_QUICK = 2, UN_SIGMOID = 3, UN_TANH = 4, UN_RELU = 5, UN_NEG = 6, UN_EXP = 7, UN_GELU_ERF = 8 };
 
 // ---- elementwise.hip --------------------------------------------------------------------------------
 // Which kernel a launcher chose, counted per launch call where the choice is made (as FlashVariant is): the tests assert the route a shape takes.
@@ -104,6 +104,17 @@ bool launch_latent_preview(hipStream_t s, const float* x, int64_t plane, int c, 
 // x [plane, 3, n] f32 planar -> out [n * plane][3]: v = x * in_mul + in_add (only when (in_mul, in_add) != (1, 0)); v <= 0 or NaN -> 0, v >= 1 -> 255, else
 // (uint8_t)(v * 255.0f + 0.5f)
 bool launch_planar_to_u8(hipStream_t s, const float* x, int64_t plane, int64_t n, float in_mul, float in_add, uint8_t* out);
+
+// ---- clip_vision.hip: in front of the CLIP vision tower ----
+// img [n][h][w][3] u8 RGB (device), xi / yi: S source columns / rows (device ints, the host's restatement of the reference's nearest resize + centre crop) ->
+// out [S, S, 3, n] f32 = (clamp(img / 255, 0, 1) - mean[c]) / std[c], IEEE divisions.  false (nothing enqueued): bad arguments
+bool launch_clip_preprocess(hipStream_t s, const uint8_t* img, const int* xi, const int* yi, float* out, int w, int h, int S, int64_t n);
+// CLIPVisionEmbeddings in one launch (k_patch_embed): x [S, S, 3, N] f32, w16 [P, P, 3, E] f16, cls [E], pos [E, (S/P)^2 + 1] f32 -> out [E, (S/P)^2 + 1, N] f32:
+// row 0 = cls + pos row 0, row 1 + p = the stride-P conv of patch p (f16 operands, f32 accumulation) + pos row 1 + p.  Shapes outside patch_embed_shape_ok abort:
+// the planner asks first and runs them as plain nodes.
+bool patch_embed_shape_ok(int64_t S, int64_t P, int64_t E, int64_t N);
+void launch_patch_embed(hipStream_t s, float* out, const float* x, const void* w16, const float* cls, const float* pos, int64_t S, int64_t P, int64_t E, int64_t N);
+int64_t patch_embed_launches();
 
 // ---- norm.hip ---------------------------------------------------------------------------------------
 // GROUP_NORM over [W*H, C, N] contiguous f32; optional fused affine (w,b per channel) and SiLU
