@@ -3211,7 +3211,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                     if (to16) {
                         const int64_t ld = rup64(C);
                         const size_t off = B.alloc((size_t)Nimg * Lq * ld * 2);
-                        if (ld != C) B.emit_at(im.fb, i, [=](hipStream_t st) { (void)hipMemsetAsync(P->arena + off, 0, (size_t)Nimg * Lq * ld * 2, st); });
+                        if (ld != C) B.emit_at(im.fb, i, [=](hipStream_t st) { launch_zero(st, P->arena + off, (size_t)Nimg * Lq * ld * 2); });
                         B.emit_at(im.fb, i, [=](hipStream_t st) {
                             FlashOut f2;
                             f2.H     = (int)H;
@@ -3287,7 +3287,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                                 STAT(flash_slice_images)++;
                             }
                             if (ld != C) {  // zero the K padding once per launch
-                                B.emit([=](hipStream_t st) { (void)hipMemsetAsync(P->arena + off, 0, (size_t)Nimg * Lq * ld * 2, st); });
+                                B.emit([=](hipStream_t st) { launch_zero(st, P->arena + off, (size_t)Nimg * Lq * ld * 2); });
                             }
                             B.emit([=](hipStream_t st) {
                                 FlashOut f2;
@@ -3332,7 +3332,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                     Planner* P       = B.P;
                     const int64_t ld = rup64(C);
                     const size_t off = B.alloc((size_t)Lq * ld * 2);
-                    if (ld != C) B.emit([=](hipStream_t st) { (void)hipMemsetAsync(P->arena + off, 0, (size_t)Lq * ld * 2, st); });
+                    if (ld != C) B.emit([=](hipStream_t st) { launch_zero(st, P->arena + off, (size_t)Lq * ld * 2); });
                     B.emit([=](hipStream_t st) {
                         FlashOut f2;
                         f2.H     = (int)HN;
@@ -4421,7 +4421,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
     if (B.cnt_used > 0) {  // tile counters of the in-launch split-K combines: zero before the first launch of every run
         Planner* PP          = P;
         const size_t coff    = B.cnt_off, cbytes = B.cnt_used * sizeof(int);
-        plan->steps.insert(plan->steps.begin(), [=](hipStream_t st) { (void)hipMemsetAsync(PP->arena + coff, 0, cbytes, st); });
+        plan->steps.insert(plan->steps.begin(), [=](hipStream_t st) { launch_zero(st, PP->arena + coff, cbytes); });
     }
     plan->n_nodes      = g->n_nodes;
     plan->arena_needed = B.arena_off;

@@ -286,6 +286,17 @@ void launch_scale(hipStream_t s, float* dst, const float* src, int64_t n, float 
     k_scale<<<grid_for(n, 256), 256, 0, s>>>(dst, src, n, scale, bias);
 }
 
+// a plan's own clears (tile counters, the K padding of an f16 operand image): a kernel, not a memset node, so that a captured plan replays launches only
+__global__ void k_zero_words(uint32_t* __restrict__ dst, int64_t n) {
+    const int64_t n4 = n / 4;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) ((uint4*)dst)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) dst[(n & ~3ll) + threadIdx.x] = 0u;
+}
+void launch_zero(hipStream_t s, void* dst, size_t bytes) {
+    const int64_t n = (int64_t)(bytes / 4);
+    k_zero_words<<<grid_for(n / 4 + 1, 256), 256, 0, s>>>((uint32_t*)dst, n);
+}
+
 // ---------------------------------------------------------------------------------------- copy / cast
 struct CopyArgs {
     int64_t sne[4], snb[4], dne[4], dnb[4];

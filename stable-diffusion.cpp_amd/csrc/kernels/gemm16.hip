@@ -879,7 +879,7 @@ __global__ __launch_bounds__(WR * WC * 64, PIPE ? 2 : 2) void k_gemm16(G16Args g
     // ---- split-K, reduced in the launch: slab dump -> ticket; the last arriver sums the slices in slice order (bitwise deterministic whoever
     // arrives last) and falls through to the epilogue.  Protocol = cdna_hip_programming.md section 5 "in-launch split-K reduction", write-through
     // form: 16-byte sc1 stores, every storing wave drains vmcnt, barrier, ONE lane takes a relaxed agent-scope ticket; the reducer reads with
-    // sc1 loads.  Nobody ever waits for another workgroup, so residency does not matter.  The plan zeroes all its tile counters with one hipMemsetAsync ahead of its first launch.
+    // sc1 loads.  Nobody ever waits for another workgroup, so residency does not matter.  The plan zeroes all its tile counters with one launch_zero ahead of its first launch.
     // Only the 128-row tiles take this path (64 / 32 KB per slice: a few slices are a few microseconds of reading for the last arriver; the
     // 320 KB slabs of the 256x320 tile were measured 40-70 % slower than slabs + a chip-wide reduce pass, profiles/r02o_*).
     if (BM == 128 && g.split_k > 1 && g.sk_cnt) {

@@ -60,6 +60,8 @@ int64_t model_input_route_launches(int route);
 void launch_guidance3(hipStream_t s, float* out, const float* e3, const float* txt, const float* img, int64_t per, int64_t nb);
 void launch_unary(hipStream_t s, UnOp op, float* dst, const float* src, int64_t n);
 void launch_scale(hipStream_t s, float* dst, const float* src, int64_t n, float scale, float bias);
+// zero `bytes` (a multiple of 4) at dst (16-byte aligned: an arena block) with a kernel: what a plan clears ahead of its launches, captured or eager
+void launch_zero(hipStream_t s, void* dst, size_t bytes);
 // generic strided copy with conversion between f32/f16/bf16 (logical element order preserved)
 void launch_copy(hipStream_t s, const View4& dst, const View4& src);
 void launch_concat(hipStream_t s, const View4& dst, const View4& a, const View4& b, int dim);
