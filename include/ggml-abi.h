@@ -447,6 +447,10 @@ static inline int64_t ggml_abi_blck_size(enum ggml_type t) {
         case GGML_TYPE_Q8_0:
         case GGML_TYPE_Q8_1:
             return 32;
+        case GGML_TYPE_Q4_K:
+        case GGML_TYPE_Q5_K:
+        case GGML_TYPE_Q6_K:
+            return 256; /* super-blocks; the other K types stay unsized: decoded when a file is read */
         default:
             return 1;
     }
@@ -462,6 +466,9 @@ static inline size_t ggml_abi_type_size(enum ggml_type t) {
         case GGML_TYPE_Q5_1: return 24;
         case GGML_TYPE_Q8_0: return 34; /* half d; int8 qs[32] */
         case GGML_TYPE_Q8_1: return 36;
+        case GGML_TYPE_Q4_K: return 144; /* half d, dmin; uint8 scales[12]; uint8 qs[128] */
+        case GGML_TYPE_Q5_K: return 176; /* half d, dmin; uint8 scales[12]; uint8 qh[32]; uint8 qs[128] */
+        case GGML_TYPE_Q6_K: return 210; /* uint8 ql[128]; uint8 qh[64]; int8 scales[16]; half d */
         case GGML_TYPE_I8: return 1;
         case GGML_TYPE_I16: return 2;
         case GGML_TYPE_I32: return 4;

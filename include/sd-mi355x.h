@@ -75,6 +75,9 @@ enum sdm_type_t {
     SDM_TYPE_F16  = 1,
     SDM_TYPE_Q4_0 = 2,
     SDM_TYPE_Q8_0 = 8,
+    SDM_TYPE_Q4_K = 12, /* K-quant super-blocks (256 weights): Linears whose input width is a multiple of 256 take them, the others stay f32 (nn.hpp Linear, as for every block type); kept raw on the device */
+    SDM_TYPE_Q5_K = 13,
+    SDM_TYPE_Q6_K = 14,
     SDM_TYPE_BF16 = 30,
 };
 

@@ -23,6 +23,7 @@ BACKEND_LIB = Path(os.environ.get("SDCPP_BACKEND_LIB", str(LIB_DIR / "libggml-mi
 
 # ggml_type numeric values (include/ggml-abi.h)
 F32, F16, Q4_0, Q8_0, I32, BF16 = 0, 1, 2, 8, 26, 30
+Q4_K, Q5_K, Q6_K = 12, 13, 14  # K-quant super-blocks (256 weights): Linear weights only
 TYPE_SIZE = {F32: 4, F16: 2, BF16: 2, I32: 4}
 
 # sd_model_family_t
@@ -425,7 +426,8 @@ _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned 
                         "lin_qgemv lin_qgemv_rows4 lin_qgemv_rows8 lin_qgemv_rows16 lin_qgemv_group lin_qgemm16_rb1 lin_qgemm16_rb2 lin_qgemm16_rb4 lin_qgemm16_reduce "
                         "lin_fgemv_f16 lin_fgemv_f32 lin_wswz_q "
                         "fused_ip_attn flash_short_ip_launches "
-                        "fused_patch_embed patch_embed_launches").split()
+                        "fused_patch_embed patch_embed_launches "
+                        "lin_kq_gemm_rb1 lin_kq_gemm_rb2 lin_kq_gemm_rb4 lin_kq_gemm_reduce lin_kq_image kquant_linears").split()
 
 
 class BackendStats(C.Structure):

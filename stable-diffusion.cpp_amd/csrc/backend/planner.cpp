@@ -265,6 +265,11 @@ inline bool is_static_weight(const ggml_tensor* t) {
     return b != nullptr && b->usage == GGML_BACKEND_BUFFER_USAGE_WEIGHTS;
 }
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// a q4_K / q5_K / q6_K Linear weight the K-quant kernels (kernels/kquant.hip) take: whole super-blocks per row, rows packed
+inline bool kq_weight_ok(const ggml_tensor* w) {
+    return kq_type((int)w->type) && w->ne[0] >= 256 && w->ne[0] % 256 == 0 && w->ne[2] == 1 && w->ne[3] == 1 && w->nb[0] == ggml_abi_type_size(w->type) &&
+           (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, w->ne[0]);
+}
 
 uint64_t fnv(uint64_t h, const void* p, size_t n) {
     const unsigned char* c = (const unsigned char*)p;
@@ -717,7 +722,10 @@ const void* get_swz_linear(Planner* P, const ggml_tensor* w, hipStream_t s, int 
     const size_t bytes = wswz_bytes(R, K);
     void* d            = nullptr;
     if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-    launch_wswz_linear(s, d, w->data, (int)w->type, K, R, (int64_t)w->nb[1], geglu == 2 ? -(R / 2) : geglu_pairs ? R / 2 : 0);
+    if (kq_type((int)w->type))  // K-quant super-blocks: k_kq_image (every sub-block scale decoded once), never the per-element wload of k_wswz_linear
+        launch_kq_image(s, d, w->data, (int)w->type, K, R, geglu == 2 ? -(R / 2) : geglu_pairs ? R / 2 : 0);
+    else
+        launch_wswz_linear(s, d, w->data, (int)w->type, K, R, (int64_t)w->nb[1], geglu == 2 ? -(R / 2) : geglu_pairs ? R / 2 : 0);
     P->swz[key] = {d, bytes, w->data, ggml_abi_nbytes(w)};
     STAT(swizzled_weight_bytes) += (int64_t)bytes;
     return d;
@@ -958,7 +966,9 @@ bool linear_fast_ok(const ggml_tensor* n) {
     const ggml_tensor* x = n->src[1];
     if (!g_opt.mfma_gemm) return false;
     if (!is_static_weight(w) || !is_f32(x) || !is_f32(n)) return false;
-    if (!(w->type == GGML_TYPE_F16 || w->type == GGML_TYPE_F32 || w->type == GGML_TYPE_BF16 || w->type == GGML_TYPE_Q8_0 || w->type == GGML_TYPE_Q4_0)) return false;
+    if (!(w->type == GGML_TYPE_F16 || w->type == GGML_TYPE_F32 || w->type == GGML_TYPE_BF16 || w->type == GGML_TYPE_Q8_0 || w->type == GGML_TYPE_Q4_0 ||
+          (kq_weight_ok(w) && aligned16(w->data))))
+        return false;
     if (w->ne[2] != 1 || w->ne[3] != 1 || !contig(w)) return false;
     if (x->nb[0] != 4 || x->ne[0] % 4 != 0 || x->nb[1] % 16 != 0 || !aligned16(x->data)) return false;
     if (x->ne[2] > 1 && x->nb[2] != x->nb[1] * (size_t)x->ne[1]) {
@@ -1281,6 +1291,26 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     // the chain's output must not land on rows the kernel is still reading (the deferred SiLU's source may have been released by the allocator)
     const ggml_tensor* lastt   = gi.node(last);
     const bool src_safe        = xsrc == x || !overlaps(lastt->data, ggml_abi_nbytes(lastt), xsrc->data, ggml_abi_nbytes(xsrc));
+    // K-quant weights (q4_K / q5_K / q6_K) under 1 .. 4 rows: k_kq_gemm reads the f32 rows itself (deferred SiLU applied while they are staged), as k_qgemv does
+    const bool kq = kq_type((int)w->type);
+    if (kq) STAT(kquant_linears)++;
+    if (kq && g_opt.qgemm16 && tokens <= 4 && plain_epi && simple_rows && src_safe && kq_gemm_supported((int)w->type, tokens, K, M)) {
+        const int S        = kq_gemm_split_k(tokens, K, M);
+        const size_t wsoff = S > 1 ? B.alloc((size_t)S * tokens * M * 4) : 0;
+        Planner* P         = B.P;
+        float* qdst        = (float*)gi.node(last)->data;
+        const float* qx    = (const float*)xsrc->data;
+        const int64_t qxs  = (int64_t)x->nb[1] / 4;
+        const void* wraw   = w->data;
+        const int wt       = (int)w->type;
+        const bool silu    = xsrc != x;
+        B.emit_at(emit_node, i, [=](hipStream_t st) {
+            launch_kq_gemm(st, qdst, nullptr, 0, nullptr, 0, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S, qx, qxs, 1.0f, silu);
+        });
+        STAT(fused_linear)++;
+        if (silu) STAT(fused_presilu)++;
+        return;
+    }
     // q8_0 / q4_0 weights under one or two rows: stream the RAW quantised blocks once, dequantise in registers (qgemm.hip) — no f16 weight image is ever built for these tensors
     if (g_opt.qgemv && plain_epi && simple_rows && src_safe && qgemv_supported((int)w->type, tokens, K)) {
         const size_t wsoff = B.alloc(qgemv_workspace_bytes(tokens, K));
@@ -1319,7 +1349,8 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     }
     // ... and under a few hundred rows (text-stream Linears, text encoders): the raw blocks again, dequantised in registers on the way into the
     // MFMA units (k_qgemm16) — below ~300 rows a GEMM is bound by its weight stream, and the quantised stream is 1.9x / 3.6x smaller
-    const bool useq  = g_opt.qgemm16 && hm_d == 0 && geglu_out < 0 && qgemm16_supported((int)w->type, tokens, K, M);
+    // (K-quant weights: k_kq_gemm in its place, from one row on)
+    const bool useq  = g_opt.qgemm16 && hm_d == 0 && geglu_out < 0 && (kq ? kq_gemm_supported((int)w->type, tokens, K, M) : qgemm16_supported((int)w->type, tokens, K, M));
     const void* wraw = w->data;
     const int wt     = (int)w->type;
     // resident-quantised weights (option jit_qimages = least activation rows, default 4096; 1 = always, 0 = never): such a Linear gets NO cached f16 image — the image is
@@ -1335,7 +1366,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         ep.qrow_bytes = (int64_t)w->nb[1];
         STAT(qinloop_linears)++;
     }
-    const bool jit = !useq && !qin && g_opt.jit_qimages > 0 && tokens >= g_opt.jit_qimages && geglu_out < 0 && hm_d == 0 && !B.hm_hoisting && wswz_q_supported((int)w->type, K) &&
+    const bool jit = !useq && !qin && g_opt.jit_qimages > 0 && tokens >= g_opt.jit_qimages && geglu_out < 0 && hm_d == 0 && !B.hm_hoisting && (wswz_q_supported((int)w->type, K) || kq_image_supported((int)w->type, K)) &&
                      (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, K) && aligned16(w->data);
     const int geglu_mode = geglu_out >= 0 ? gemm16_geglu_mode(tokens, M, K) : 0;
     const void* swz = useq ? nullptr : qin ? w->data : (jit ? B.P->jit_buffer(wswz_bytes(M, K), B.jit_seq[wswz_bytes(M, K)]++) : get_swz_linear(B.P, w, s, geglu_mode));
@@ -1343,7 +1374,10 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         void* jb          = const_cast<void*>(swz);
         const void* wsrc  = w->data;
         const int wty     = (int)w->type;
-        B.emit_at(emit_node, i, [=](hipStream_t st) { launch_wswz_q(st, jb, wsrc, wty, K, M); });
+        B.emit_at(emit_node, i, [=](hipStream_t st) {
+            if (kq) launch_kq_image(st, jb, wsrc, wty, K, M);
+            else launch_wswz_q(st, jb, wsrc, wty, K, M);
+        });
         STAT(jit_images)++;
     }
     float* dst      = (float*)gi.node(last)->data;
@@ -1416,8 +1450,11 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     } else if (gelu_out >= 0) {
         const size_t ooff = B.alloc((size_t)tokens * M * 2);
         if (useq) {
-            B.emit([=](hipStream_t st) { launch_qgemm16(st, nullptr, P->arena + ooff, M, P->arena + off, ld, tokens, wraw, wt, K, M, ep); });
-            STAT(qgemm16_linears)++;
+            B.emit([=](hipStream_t st) {
+                if (kq) launch_kq_gemm(st, nullptr, P->arena + ooff, M, P->arena + off, ld, tokens, wraw, wt, K, M, ep);
+                else launch_qgemm16(st, nullptr, P->arena + ooff, M, P->arena + off, ld, tokens, wraw, wt, K, M, ep);
+            });
+            if (!kq) STAT(qgemm16_linears)++;
         } else {
             const Builder::Split sk = B.plan_split(tokens, M, K, false, false);
             B.emit([=](hipStream_t st) { launch_gemm16_linear(st, nullptr, P->arena + ooff, M, P->arena + off, ld, swz, tokens, K, M, M, ep, 0, 0, 0, sk.ws(P), sk.cnt(P), sk.S); });
@@ -1457,13 +1494,15 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
                 });
         }
     } else if (useq) {
-        const int S        = ep.gate ? 1 : qgemm16_split_k(tokens, K, M);
+        const int S        = ep.gate ? 1 : kq ? kq_gemm_split_k(tokens, K, M) : qgemm16_split_k(tokens, K, M);
         const size_t wsoff = S > 1 ? B.alloc((size_t)S * tokens * M * 4) : 0;
         B.emit_at(emit_node, i, [=](hipStream_t st) {
-            launch_qgemm16(st, redir ? (float*)(P->arena + redir_off) : dst, nullptr, 0, P->arena + off, ld, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S);
+            float* qd = redir ? (float*)(P->arena + redir_off) : dst;
+            if (kq) launch_kq_gemm(st, qd, nullptr, 0, P->arena + off, ld, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S);
+            else launch_qgemm16(st, qd, nullptr, 0, P->arena + off, ld, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S);
         });
         if (redir) B.redirect_taken.insert(gi.node(last));
-        STAT(qgemm16_linears)++;
+        if (!kq) STAT(qgemm16_linears)++;
     } else if (g_opt.fuse_rows16 && !ep.gate && emit_node == i && M % 64 == 0 && x->ne[3] == 1 && only_consumer_is_tokens_to_conv(gi, last)) {
         // FF2 (+bias, +residual) of a SpatialTransformer whose result only proj_out reads (block.hpp:566-572): write the 1x1 conv's f16 operand
         // rows directly — no f32 tensor, no pack pass (the conv rounds its input to f16 anyway: same rounding point).  Option fuse_rows16,
@@ -3029,6 +3068,11 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
             return true;
         }
         case GGML_OP_MUL_MAT: {
+            if (kq_type((int)n->src[0]->type)) {  // no generic matmul over super-blocks (k_mul_mat_generic would read them as q4_0): fail the graph, loudly
+                fprintf(stderr, "[ggml-mi355x] node %d: MUL_MAT with a %s weight outside the Linear path (weight not in a WEIGHTS buffer, unaligned rows, or option mfma_gemm = 0)\n", i,
+                        n->src[0]->type == GGML_TYPE_Q4_K ? "q4_K" : n->src[0]->type == GGML_TYPE_Q5_K ? "q5_K" : "q6_K");
+                return false;
+            }
             View4 a = view_of(n->src[0]), b = view_of(n->src[1]);
             View4 d = view_of(n);
             B.emit([=](hipStream_t st) { launch_mul_mat_generic(st, (float*)d.data, d.ne, d.nb, a, b); });
@@ -4324,12 +4368,13 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                 // applied by the weight-streaming kernel while it stages the rows (plan_linear); adjacency keeps the source rows alive
                 const ggml_tensor* src = n->src[0];
                 const int c            = gi.sole(i);
-                if (g_opt.fusion && (g_opt.fgemv || g_opt.qgemv) && xunary(n) == GGML_UNARY_OP_SILU && c == i + 1 && is_f32(src) && contig(src) && contig(n) &&
+                if (g_opt.fusion && (g_opt.fgemv || g_opt.qgemv || g_opt.qgemm16) && xunary(n) == GGML_UNARY_OP_SILU && c == i + 1 && is_f32(src) && contig(src) && contig(n) &&
                     B.packed.find(strip_reshape(src)) == B.packed.end() &&
                     !(n->flags & GGML_TENSOR_FLAG_OUTPUT) && xop(gi.node(c)) == GGML_OP_MUL_MAT && gi.node(c)->src[1] == n && linear_fast_ok(gi.node(c))) {
                     const ggml_tensor* w = gi.node(c)->src[0];
                     const int64_t rows   = n->ne[1] * n->ne[2] * n->ne[3];
-                    if ((g_opt.fgemv && fgemv_supported((int)w->type, rows, w->ne[0])) || (g_opt.qgemv && qgemv_supported((int)w->type, rows, w->ne[0]))) {
+                    if ((g_opt.fgemv && fgemv_supported((int)w->type, rows, w->ne[0])) || (g_opt.qgemv && qgemv_supported((int)w->type, rows, w->ne[0])) ||
+                        (g_opt.qgemm16 && rows <= 4 && kq_gemm_supported((int)w->type, rows, w->ne[0], w->ne[1]))) {  // k_kq_gemm stages 1 .. 4 f32 rows itself
                         B.presilu[n] = src;
                         chain        = {i};
                         ok           = true;
@@ -4646,6 +4691,11 @@ bool planner_supports_op(const ggml_tensor* n) {
             if (!a || !b || n->type != GGML_TYPE_F32) return false;
             const bool at = a->type == GGML_TYPE_F32 || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_Q8_0 || a->type == GGML_TYPE_Q4_0;
             const bool bt = b->type == GGML_TYPE_F32 || b->type == GGML_TYPE_F16;
+            // q4_K / q5_K / q6_K: Linear weights only (the K-quant kernels; there is no generic matmul over super-blocks)
+            // — and what linear_fast_ok asks that is known here; what is not (the weight's buffer usage, the addresses) makes the plan fail loudly (plan_single)
+            if (kq_type((int)a->type))
+                return g_opt.mfma_gemm && kq_weight_ok(a) && ggml_abi_is_contiguous(a) && b->type == GGML_TYPE_F32 && b->nb[0] == 4 && b->ne[0] % 4 == 0 && b->nb[1] % 16 == 0 &&
+                       ggml_abi_is_contiguous(n);
             return at && bt && a->nb[0] == ggml_abi_type_size(a->type) && b->nb[0] == ggml_abi_type_size(b->type);
         }
         case GGML_OP_IM2COL:
@@ -4711,6 +4761,10 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     static_assert(offsetof(ggml_backend_mi355x_stats, lin_wswz_q) - offsetof(ggml_backend_mi355x_stats, lin_t128) == (LIN_ROUTE_COUNT - 1) * sizeof(int64_t),
                   "ggml_backend_mi355x_stats: one lin_* field per LinearRoute, in its order");
     for (int r = 0; r < LIN_ROUTE_COUNT; ++r) (&o->lin_t128)[r] = linear_route_launches(r);
+    // ... and the K-quant launchers (kernels/kquant.hip): the lin_kq_* fields lie in the order of KQRoute
+    static_assert(offsetof(ggml_backend_mi355x_stats, lin_kq_image) - offsetof(ggml_backend_mi355x_stats, lin_kq_gemm_rb1) == (KQ_ROUTE_COUNT - 1) * sizeof(int64_t),
+                  "ggml_backend_mi355x_stats: one lin_kq_* field per KQRoute, in its order");
+    for (int r = 0; r < KQ_ROUTE_COUNT; ++r) (&o->lin_kq_gemm_rb1)[r] = kq_route_launches(r);
 }
 
 namespace {

@@ -134,6 +134,9 @@ const char* ggml_type_name(enum ggml_type type) {
         case GGML_TYPE_BF16: return "bf16";
         case GGML_TYPE_Q4_0: return "q4_0";
         case GGML_TYPE_Q8_0: return "q8_0";
+        case GGML_TYPE_Q4_K: return "q4_K";
+        case GGML_TYPE_Q5_K: return "q5_K";
+        case GGML_TYPE_Q6_K: return "q6_K";
         case GGML_TYPE_I8: return "i8";
         case GGML_TYPE_I16: return "i16";
         case GGML_TYPE_I32: return "i32";
@@ -418,6 +421,153 @@ static void quantize_row_q4_0(const float* x, uint8_t* y, int64_t k) {
     }
 }
 
+// ---- K-quants (ggml-common.h block_q{4,5,6}_K; 256 weights per super-block, little-endian fields).  The decoders restate upstream's dequantize_row_q*_K with
+// its operations in its order, each rounded on its own (d1 = d * sc; m1 = dmin * m; y = d1 * q - m1 / y = d * sc * q): the values the device kernels
+// (kernels/kquant.hip) round to f16, and what the model loader decodes a file tensor of these types with.
+//   q4_K {f16 d; f16 dmin; u8 scales[12] (8 six-bit scales + 8 six-bit mins, get_scale_min_k4); u8 qs[128]}: per 64 weights, 32 low nibbles then 32 high
+//   q5_K {f16 d; f16 dmin; u8 scales[12]; u8 qh[32] (bit 2 g + 0 / 1 of qh[l]: fifth bit of the low / high nibble weight l of group g); u8 qs[128]}
+static inline void kq_scale_min(const uint8_t* s12, int j, int& sc, int& mn) {
+    if (j < 4) {
+        sc = s12[j] & 63;
+        mn = s12[j + 4] & 63;
+    } else {
+        sc = (s12[j + 4] & 0xF) | ((s12[j - 4] >> 6) << 4);
+        mn = (s12[j + 4] >> 4) | ((s12[j] >> 6) << 4);
+    }
+}
+static void dequantize_row_q45_K(const uint8_t* raw, float* dst, int64_t n, bool five) {
+    const int bs = five ? 176 : 144;
+    for (int64_t blk = 0; blk < n / 256; ++blk) {
+        const uint8_t* p = raw + blk * bs;
+        ggml_fp16_t dh, mh;
+        memcpy(&dh, p, 2);
+        memcpy(&mh, p + 2, 2);
+        const float d = ggml_fp16_to_fp32(dh), dmin = ggml_fp16_to_fp32(mh);
+        const uint8_t* s12 = p + 4;
+        const uint8_t* qh  = p + 16;
+        const uint8_t* q   = p + (five ? 48 : 16);
+        float* y = dst + blk * 256;
+        for (int g = 0; g < 4; ++g, q += 32)
+            for (int part = 0; part < 2; ++part) {
+                const int j = 2 * g + part;
+                int sc, mn;
+                kq_scale_min(s12, j, sc, mn);
+                const float dl = d * (float)sc, ml = dmin * (float)mn;
+                for (int l = 0; l < 32; ++l) {
+                    int v = part ? (q[l] >> 4) : (q[l] & 0xF);
+                    if (five && ((qh[l] >> j) & 1)) v += 16;
+                    const float pv = dl * (float)v;  // (a statement of its own: never contracted with the subtraction)
+                    *y++ = pv - ml;
+                }
+            }
+    }
+}
+//   q6_K {u8 ql[128]; u8 qh[64]; i8 scales[16] (per 16 weights); f16 d}: per 128-weight half, weight l + 32 c (c = 0..3) has its low 4 bits in
+//        ql[l + 32 (c & 1)] (low nibble for c < 2, high nibble otherwise) and its high 2 bits at bits 2 c of qh[l];  x = d * scale * (q - 32)
+static void dequantize_row_q6_K(const uint8_t* raw, float* dst, int64_t n) {
+    for (int64_t blk = 0; blk < n / 256; ++blk) {
+        const uint8_t* p  = raw + blk * 210;
+        const uint8_t* ql = p;
+        const uint8_t* qh = p + 128;
+        const int8_t* sc  = (const int8_t*)(p + 192);
+        ggml_fp16_t dh;
+        memcpy(&dh, p + 208, 2);
+        const float d = ggml_fp16_to_fp32(dh);
+        float* y = dst + blk * 256;
+        for (int half = 0; half < 2; ++half, y += 128, ql += 64, qh += 32, sc += 8)
+            for (int l = 0; l < 32; ++l)
+                for (int c = 0; c < 4; ++c) {
+                    const int lo = (c < 2) ? (ql[l + 32 * (c & 1)] & 0xF) : (ql[l + 32 * (c & 1)] >> 4);
+                    const int q6 = (lo | (((qh[l] >> (2 * c)) & 3) << 4)) - 32;
+                    y[l + 32 * c] = d * (float)sc[l / 16 + 2 * c] * (float)q6;
+                }
+    }
+}
+// PLAIN encoders — NOT ggml's search-based make_qkx / make_qx_quants: per sub-block min / max, 6-bit (q6_K: 8-bit) scales against the super-block maximum, scales and
+// mins rounded UP so that every value of the sub-block stays inside the code range.  They exist for synthetic weights and for file tensors of another type; a tensor
+// already stored in the parameter's K type is copied raw and never passes through them.
+static void quantize_row_q45_K(const float* x, uint8_t* y, int64_t k, bool five) {
+    const int bs = five ? 176 : 144, qmax = five ? 31 : 15;
+    for (int64_t blk = 0; blk < k / 256; ++blk, x += 256) {
+        uint8_t* p = y + blk * bs;
+        memset(p, 0, bs);
+        float mnv[8], mxv[8], maxmn = 0.f;
+        for (int j = 0; j < 8; ++j) {
+            float lo = 0.f, hi = 0.f;  // the code range starts at -dmin * m <= 0
+            for (int l = 0; l < 32; ++l) {
+                lo = std::min(lo, x[32 * j + l]);
+                hi = std::max(hi, x[32 * j + l]);
+            }
+            mnv[j] = -lo;
+            mxv[j] = hi;
+            maxmn  = std::max(maxmn, mnv[j]);
+        }
+        const ggml_fp16_t mh = ggml_fp32_to_fp16(maxmn / 63.0f);
+        const float dmin     = ggml_fp16_to_fp32(mh);
+        int sc[8], mn[8];
+        float off[8], maxneed = 0.f;
+        for (int j = 0; j < 8; ++j) {
+            mn[j]   = dmin > 0.f ? std::min(63, (int)ceilf(mnv[j] / dmin)) : 0;
+            off[j]  = dmin * (float)mn[j];
+            maxneed = std::max(maxneed, (mxv[j] + off[j]) / (float)qmax);
+        }
+        const ggml_fp16_t dh = ggml_fp32_to_fp16(maxneed / 63.0f);
+        const float d        = ggml_fp16_to_fp32(dh);
+        memcpy(p, &dh, 2);
+        memcpy(p + 2, &mh, 2);
+        uint8_t* s12 = p + 4;
+        for (int j = 0; j < 8; ++j) {
+            sc[j] = d > 0.f ? std::min(63, (int)ceilf((mxv[j] + off[j]) / (float)qmax / d)) : 0;
+            if (j < 4) {
+                s12[j] |= (uint8_t)sc[j];
+                s12[j + 4] |= (uint8_t)mn[j];
+            } else {
+                s12[j + 4] = (uint8_t)((sc[j] & 0xF) | ((mn[j] & 0xF) << 4));
+                s12[j - 4] |= (uint8_t)((sc[j] >> 4) << 6);
+                s12[j] |= (uint8_t)((mn[j] >> 4) << 6);
+            }
+        }
+        uint8_t* qh = p + 16;
+        uint8_t* qs = p + (five ? 48 : 16);
+        for (int j = 0; j < 8; ++j) {
+            const float step = d * (float)sc[j], inv = step > 0.f ? 1.0f / step : 0.f;
+            for (int l = 0; l < 32; ++l) {
+                const int v = std::max(0, std::min(qmax, (int)lrintf((x[32 * j + l] + off[j]) * inv)));
+                qs[32 * (j / 2) + l] |= (uint8_t)((v & 0xF) << (4 * (j & 1)));
+                if (five && (v & 16)) qh[l] |= (uint8_t)(1u << j);
+            }
+        }
+    }
+}
+static void quantize_row_q6_K(const float* x, uint8_t* y, int64_t k) {
+    for (int64_t blk = 0; blk < k / 256; ++blk, x += 256) {
+        uint8_t* p = y + blk * 210;
+        memset(p, 0, 210);
+        float need[16], maxneed = 0.f;
+        for (int j = 0; j < 16; ++j) {
+            float amax = 0.f;
+            for (int l = 0; l < 16; ++l) amax = std::max(amax, fabsf(x[16 * j + l]));
+            need[j] = amax / 31.0f;
+            maxneed = std::max(maxneed, need[j]);
+        }
+        const ggml_fp16_t dh = ggml_fp32_to_fp16(maxneed / 127.0f);
+        const float d        = ggml_fp16_to_fp32(dh);
+        memcpy(p + 208, &dh, 2);
+        int8_t* scales = (int8_t*)(p + 192);
+        for (int j = 0; j < 16; ++j) {
+            const int sc   = d > 0.f ? std::min(127, (int)ceilf(need[j] / d)) : 0;
+            scales[j]      = (int8_t)sc;
+            const float st = d * (float)sc, inv = st > 0.f ? 1.0f / st : 0.f;
+            const int half = j / 8, c = (j % 8) / 2, l0 = 16 * (j & 1);  // weight 128 half + 32 c + l
+            for (int l = l0; l < l0 + 16; ++l) {
+                const int v = std::max(-32, std::min(31, (int)lrintf(x[16 * j + (l - l0)] * inv))) + 32;
+                p[64 * half + l + 32 * (c & 1)] |= (uint8_t)((v & 0xF) << (c < 2 ? 0 : 4));
+                p[128 + 32 * half + l] |= (uint8_t)((v >> 4) << (2 * c));
+            }
+        }
+    }
+}
+
 size_t ggml_quantize_chunk(enum ggml_type type, const float* src, void* dst, int64_t start, int64_t nrows, int64_t n_per_row, const float*) {
     GGML_ASSERT(start % n_per_row == 0);
     const size_t row_size = ggml_row_size(type, n_per_row);
@@ -429,6 +579,9 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float* src, void* dst, int
         switch (type) {
             case GGML_TYPE_Q8_0: quantize_row_q8_0(x, y, n_per_row); break;
             case GGML_TYPE_Q4_0: quantize_row_q4_0(x, y, n_per_row); break;
+            case GGML_TYPE_Q4_K: quantize_row_q45_K(x, y, n_per_row, false); break;
+            case GGML_TYPE_Q5_K: quantize_row_q45_K(x, y, n_per_row, true); break;
+            case GGML_TYPE_Q6_K: quantize_row_q6_K(x, y, n_per_row); break;
             case GGML_TYPE_F16: ggml_fp32_to_fp16_row(x, (ggml_fp16_t*)y, n_per_row); break;
             case GGML_TYPE_BF16: ggml_fp32_to_bf16_row(x, (ggml_bf16_t*)y, n_per_row); break;
             case GGML_TYPE_F32: memcpy(y, x, n_per_row * 4); break;
@@ -465,6 +618,9 @@ void ggml_dequantize_row(enum ggml_type type, const void* src, float* dst, int64
                 }
             }
             break;
+        case GGML_TYPE_Q4_K: dequantize_row_q45_K(p, dst, n, false); break;
+        case GGML_TYPE_Q5_K: dequantize_row_q45_K(p, dst, n, true); break;
+        case GGML_TYPE_Q6_K: dequantize_row_q6_K(p, dst, n); break;
         default: GGML_ASSERT(!"ggml_dequantize_row: unsupported type");
     }
 }

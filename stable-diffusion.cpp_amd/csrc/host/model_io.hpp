@@ -26,7 +26,8 @@ namespace sdmi {
 // Q4_1 / Q5_0 / Q5_1: GGUF block quantisations the graph never computes in (the engine's parameter types are f32 / f16 / bf16 / q8_0 / q4_0); they are
 // decoded to f32 at load time and re-encoded in the parameter's type, like convert_tensor does for every source type (src/model_loader.cpp:155-205)
 // K-quants (Q2_K .. Q6_K: super-blocks of 256 weights with 4- / 6-bit sub-block scales — the q2_k / q3_k / q4_k FLUX and SD3.5 files docs/flux.md:36-38
-// points its users at) and IQ4_NL (32 weights, non-linear 4-bit code book) take the same route: decoded to f32 at load, re-encoded in the parameter's type.
+// points its users at) and IQ4_NL (32 weights, non-linear 4-bit code book) take the same route: decoded to f32 at load, re-encoded in the parameter's type —
+// except a q4_K / q5_K / q6_K tensor whose parameter has that very type (context wtype): its super-blocks are copied raw (engine.cpp, FileTensor::src_type).
 enum class SrcKind { NATIVE, F64, I64, F8_E4M3, F8_E5M2, Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL };
 
 // ggml type id -> (kind, weights per block, bytes per block) of the block formats decoded at load time; false for every other type
@@ -49,6 +50,7 @@ struct FileTensor {
     std::string name;
     ggml_type type = GGML_TYPE_F32;
     SrcKind kind   = SrcKind::NATIVE;
+    int src_type   = -1;            // kind != NATIVE in a GGUF file: the ggml type id the bytes are stored in (a parameter of that very type takes them raw)
     int64_t ne[4]  = {1, 1, 1, 1};  // ggml order (ne0 fastest)
     int n_dims     = 0;
     uint64_t offset = 0;            // absolute file offset of the data
@@ -289,65 +291,10 @@ inline void decode_src_kind(SrcKind kind, const uint8_t* raw, int64_t n, float* 
                         }
             }
             break;
-        //   q4_K {f16 d; f16 dmin; u8 scales[12] (8 six-bit scales + 8 six-bit mins, get_scale_min_k4); u8 qs[128]}: per 64 weights, 32 low nibbles then 32 high
-        //   q5_K {f16 d; f16 dmin; u8 scales[12]; u8 qh[32] (bit 2 g + 0 / 1 of qh[l]: fifth bit of the low / high nibble weight l of group g); u8 qs[128]}
-        //        x = d * sc * q - dmin * mn
-        case SrcKind::Q4_K:
-        case SrcKind::Q5_K: {
-            const bool five = kind == SrcKind::Q5_K;
-            const int bs    = five ? 176 : 144;
-            for (int64_t blk = 0; blk < n / 256; ++blk) {
-                const uint8_t* p  = raw + blk * bs;
-                ggml_fp16_t dh, mh;
-                memcpy(&dh, p, 2);
-                memcpy(&mh, p + 2, 2);
-                const float d = ggml_fp16_to_fp32(dh), dmin = ggml_fp16_to_fp32(mh);
-                const uint8_t* s12 = p + 4;
-                const uint8_t* qh  = p + 16;
-                const uint8_t* q   = p + (five ? 48 : 16);
-                float* y = dst + blk * 256;
-                for (int g = 0; g < 4; ++g, q += 32)
-                    for (int part = 0; part < 2; ++part) {
-                        const int j = 2 * g + part;
-                        int sc, mn;
-                        if (j < 4) {
-                            sc = s12[j] & 63;
-                            mn = s12[j + 4] & 63;
-                        } else {
-                            sc = (s12[j + 4] & 0xF) | ((s12[j - 4] >> 6) << 4);
-                            mn = (s12[j + 4] >> 4) | ((s12[j] >> 6) << 4);
-                        }
-                        const float dl = d * (float)sc, ml = dmin * (float)mn;
-                        for (int l = 0; l < 32; ++l) {
-                            int v = part ? (q[l] >> 4) : (q[l] & 0xF);
-                            if (five && ((qh[l] >> j) & 1)) v += 16;
-                            *y++ = dl * (float)v - ml;
-                        }
-                    }
-            }
-            break;
-        }
-        //   q6_K {u8 ql[128]; u8 qh[64]; i8 scales[16] (per 16 weights); f16 d}: per 128-weight half, weight l + 32 c (c = 0..3) has its low 4 bits in
-        //        ql[l + 32 (c & 1)] (low nibble for c < 2, high nibble otherwise) and its high 2 bits at bits 2 c of qh[l];  x = d * scale * (q - 32)
-        case SrcKind::Q6_K:
-            for (int64_t blk = 0; blk < n / 256; ++blk) {
-                const uint8_t* p  = raw + blk * 210;
-                const uint8_t* ql = p;
-                const uint8_t* qh = p + 128;
-                const int8_t* sc  = (const int8_t*)(p + 192);
-                ggml_fp16_t dh;
-                memcpy(&dh, p + 208, 2);
-                const float d = ggml_fp16_to_fp32(dh);
-                float* y = dst + blk * 256;
-                for (int half = 0; half < 2; ++half, y += 128, ql += 64, qh += 32, sc += 8)
-                    for (int l = 0; l < 32; ++l)
-                        for (int c = 0; c < 4; ++c) {
-                            const int lo = (c < 2) ? (ql[l + 32 * (c & 1)] & 0xF) : (ql[l + 32 * (c & 1)] >> 4);
-                            const int q6 = (lo | (((qh[l] >> (2 * c)) & 3) << 4)) - 32;
-                            y[l + 32 * c] = d * (float)sc[l / 16 + 2 * c] * (float)q6;
-                        }
-            }
-            break;
+        //   q4_K / q5_K / q6_K: the front-end's decoders (ggml.cpp), the one host restatement of these formats
+        case SrcKind::Q4_K: ggml_dequantize_row(GGML_TYPE_Q4_K, raw, dst, n); break;
+        case SrcKind::Q5_K: ggml_dequantize_row(GGML_TYPE_Q5_K, raw, dst, n); break;
+        case SrcKind::Q6_K: ggml_dequantize_row(GGML_TYPE_Q6_K, raw, dst, n); break;
         //   iq4_nl {f16 d; u8 qs[16]}: x = d * kvalues[q], element j in the low nibble of byte j, element j + 16 in the high nibble
         case SrcKind::IQ4_NL: {
             static const int8_t kv[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
@@ -595,8 +542,9 @@ inline bool read_gguf(const std::string& path, ModelFile& mf) {
                 mf.error = "tensor '" + t.name + "' has invalid dimensions or lies outside the file";
                 return false;
             }
-            t.kind   = dk;
-            t.type   = GGML_TYPE_F32;  // what decode_src_kind delivers
+            t.kind     = dk;
+            t.src_type = ty;
+            t.type     = GGML_TYPE_F32;  // what decode_src_kind delivers
             t.nbytes = nb;
             t.offset += data0;
             keep.push_back(t);

@@ -363,8 +363,26 @@ void launch_wswz_q(hipStream_t s, void* dst, const void* wraw, int wtype, int64_
 void qgemm16_set_max_rows(int v);
 void launch_qgemm16(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const void* a16, int64_t lda, int64_t rows, const void* wraw, int wtype, int64_t K,
                     int64_t M, const Epilogue& ep, float* splitk_ws = nullptr, int splitk_S = 1);
+int qgemm16_max_rows();
+int qgemm16_rb();
 // dst[i] = sum_s ws[s * n + i] + bias[i % C] + residual[i] (gemm16.hip's k_splitk_reduce on a row-major [rows][C] output)
 void splitk_reduce_rows(hipStream_t s, float* dst, const float* ws, int S, int64_t n, const float* bias, int64_t C, const float* residual);
+
+// ---- kquant.hip: Linears over RAW q4_K (wtype 12) / q5_K (13) / q6_K (14) super-blocks; every route multiplies by w16 = f16(ggml's dequantised f32 value) ----
+bool kq_type(int wtype);
+// k_kq_gemm: 1 .. qgemm16_max_rows activation rows, the super-blocks decoded in registers into MFMA fragments (no image).  Exactly one of a16 (f16 operand image
+// [rows][lda]) and x32 (f32 rows, stride xs floats, staged as f16(silu?(x) * pre_scale): the deferred SiLU / ggml_ext_linear scale of launch_qgemv) is given.
+// Epilogues as launch_qgemm16; split-K (S slices, workspace of S * rows * M floats) only for plain outputs.  wraw 16-byte aligned for q4_K / q5_K.
+bool kq_gemm_supported(int wtype, int64_t rows, int64_t K, int64_t M);
+int kq_gemm_split_k(int64_t rows, int64_t K, int64_t M);
+void launch_kq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const void* a16, int64_t lda, int64_t rows, const void* wraw, int wtype, int64_t K, int64_t M,
+                    const Epilogue& ep, float* splitk_ws = nullptr, int splitk_S = 1, const float* x32 = nullptr, int64_t xs = 0, float pre_scale = 1.0f, bool pre_silu = false);
+// k_kq_image: raw super-blocks -> the f16 MFMA weight image (wswz_bytes(R, K)); geglu_inner as launch_wswz_linear: 0 plain, > 0 128-column pairing, < 0 16-column interleave
+bool kq_image_supported(int wtype, int64_t K);
+void launch_kq_image(hipStream_t s, void* dst, const void* wraw, int wtype, int64_t K, int64_t R, int64_t geglu_inner = 0);
+// launches counted where the launchers choose (statistics lin_kq_*)
+enum KQRoute { KQ_GEMM_RB1 = 0, KQ_GEMM_RB2, KQ_GEMM_RB4, KQ_GEMM_REDUCE, KQ_IMAGE, KQ_ROUTE_COUNT };
+int64_t kq_route_launches(int route);
 
 // ---- flash_attn.hip ---------------------------------------------------------------------------------
 // q [D,Lq,HN] (f32, strides in bytes), k [D,Lk,HN], v [DV,Lk,HN] (f16 or f32; v may be a transposed view,

@@ -1,0 +1,543 @@
+// kquant.hip — Linear layers whose weights are K-quant super-blocks (q4_K / q5_K / q6_K: 256 weights with packed 6-bit sub-block scales, the types the
+// Q4_K_S / Q4_K_M / Q5_K_S / Q6_K GGUF files of FLUX, SD3.5 and SDXL store), kept RAW in HBM (0.5625 / 0.6875 / 0.82 B per weight).
+//
+// ONE weight value on every route: w16 = f16(y), y = the f32 value ggml's dequantize_row_q{4,5,6}_K produces with its operations in ggml's order, unfused:
+//   q4_K / q5_K   d1 = d * sc;  m1 = dmin * m;  y = d1 * q - m1          q6_K   y = (d * sc) * q
+// (kq_w8 / kq_w8s below: separately rounded operations under fp contract(off), never an FMA).  The few-row kernel and the image kernel share these decoders, so a Linear differs between its
+// routes by f32 summation order only.
+//
+//   k_kq_gemm<KT, RB>   1 .. qgemm16_max_rows activation rows: the raw super-blocks stream from HBM once and are decoded in registers into the f16 B fragments of
+//                       v_mfma_f32_32x32x16_f16; no image exists.  One super-block IS one 256-wide K segment: per segment a wave fetches the 144 / 176 / 210-byte piece
+//                       of each of ITS 32 columns with coalesced 16-byte loads into a per-wave LDS strip, every lane (column n = lane % 32, k half kg = lane / 32)
+//                       unpacks the 6-bit scales of its column ONCE (8 x (d1, m1) / 16 x d * sc in registers) and then walks the quant bytes in THEIR order:
+//                         q4_K / q5_K  group g (64 weights), t: bytes 32 g + 8 r .. + 7 with r = 2 t + kg; their low nibbles are weights 64 g + 8 r + i (one MFMA
+//                                      step), their high nibbles weights 64 g + 32 + 8 r + i (the next step); q5_K adds bit 2 g / 2 g + 1 of qh[8 r + i]
+//                         q6_K         half hf (128 weights), t: ql[64 hf + 8 r ..], ql[64 hf + 32 + 8 r ..], qh[32 hf + 8 r ..] give the four steps c = 0 .. 3,
+//                                      weights 128 hf + 32 c + 8 r + i
+//                       and the A fragment of each step is read from LDS at the same permuted k offset: no lane shuffles.
+//                       q6_K rows are only 2-byte aligned (210 K / 256 bytes): the fetch takes the 14 ALIGNED 16-byte granules that cover the piece (they share
+//                       their first and last valid byte's granule with it, so they never touch a page the tensor does not) and the LDS reads re-align with v_alignbit.
+//                       Tile: 32 RB rows x 128 columns (4 waves x 32), next segment's global loads in flight during the MFMAs; split-K over gridDim.z into f32 slabs.
+//                       A = the f16 operand image, or for 1 .. 4 rows the f32 rows themselves (SiLU and pre_scale applied while they are staged).
+//   k_kq_image<KT>      raw super-blocks -> the f16 fragment-order image [col/32][K/16][64 lanes][8 halfs] of k_gemm16 (plain row order and both GEGLU orders of
+//                       k_wswz_linear): a workgroup owns 32 image rows x 256 k, loads the 32 super-blocks coalesced into LDS, wave w decodes ITS group g = w
+//                       (q4_K / q5_K: two sub-block scales per lane) / (half, t) = (w / 2, w % 2) (q6_K: four scales) and writes four whole 1 KiB fragments.
+#include <algorithm>
+#include <atomic>
+#include <cstdio>
+#include <cstdlib>
+#include "device_utils.h"
+#include "kernels.h"
+#include "ktime.h"
+
+namespace mi355x {
+
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+
+template <int KT>
+struct KQ;
+template <>
+struct KQ<4> {
+    static constexpr int BS = 144, NGC = 9, QS = 16, QH = 0;
+};
+template <>
+struct KQ<5> {
+    static constexpr int BS = 176, NGC = 11, QS = 48, QH = 16;
+};
+template <>
+struct KQ<6> {
+    static constexpr int BS = 210, NGC = 14, QS = 0, QH = 128;  // NGC: aligned granules covering 210 bytes at any even phase (14 + 210 = 224)
+};
+
+// 8 bytes at byte offset off of an LDS strip: 8-byte aligned (q4_K / q5_K fields), or 2-byte aligned (q6_K) through three dwords and v_alignbit
+template <bool ALIGNED>
+__device__ __forceinline__ void kq_ld8(const char* strip, uint32_t off, uint32_t& a, uint32_t& b) {
+    if (ALIGNED) {
+        const uint2 v = *(const uint2*)(strip + off);
+        a = v.x;
+        b = v.y;
+    } else {
+        const char* p     = strip + (off & ~3u);
+        const uint32_t sh = (off & 2u) * 8u;
+        const uint32_t r0 = *(const uint32_t*)p, r1 = *(const uint32_t*)(p + 4), r2 = *(const uint32_t*)(p + 8);
+        a = __builtin_amdgcn_alignbit(r1, r0, sh);
+        b = __builtin_amdgcn_alignbit(r2, r1, sh);
+    }
+}
+
+// eight quants (one per byte of a, b) -> f16(d1 * q - m1), each operation rounded on its own
+__device__ __forceinline__ half8_t kq_w8(uint32_t a, uint32_t b, float d1, float m1) {
+#pragma clang fp contract(off)  // plain operators under this pragma (the rounding intrinsics of the HIP headers are inlined WITH their contract flag: v_fma_mix)
+    half8_t o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float pa = d1 * (float)((a >> (8 * j)) & 0xFFu), pb = d1 * (float)((b >> (8 * j)) & 0xFFu);
+        o[j]     = (_Float16)(pa - m1);
+        o[4 + j] = (_Float16)(pb - m1);
+    }
+    return o;
+}
+// q6_K: eight 6-bit values -> f16(ds * (v - 32)), ds = d * sc already rounded
+__device__ __forceinline__ half8_t kq_w8s(uint32_t a, uint32_t b, float ds) {
+#pragma clang fp contract(off)  // plain operators under this pragma (the rounding intrinsics of the HIP headers are inlined WITH their contract flag: v_fma_mix)
+    half8_t o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float qa = (float)((a >> (8 * j)) & 0xFFu) - 32.0f, qb = (float)((b >> (8 * j)) & 0xFFu) - 32.0f;
+        o[j]     = (_Float16)(ds * qa);
+        o[4 + j] = (_Float16)(ds * qb);
+    }
+    return o;
+}
+
+// q4_K / q5_K header of the super-block at blk (16-byte aligned): d, dmin and the 12 scale bytes as three dwords
+struct KQHead {
+    float d, dmin;
+    uint32_t s0, s1, s2;
+};
+__device__ __forceinline__ KQHead kq_head45(const char* blk) {
+    const u32x4_t h = *(const u32x4_t*)blk;
+    KQHead r;
+    r.d    = (float)__builtin_bit_cast(_Float16, (uint16_t)(h[0] & 0xFFFFu));
+    r.dmin = (float)__builtin_bit_cast(_Float16, (uint16_t)(h[0] >> 16));
+    r.s0 = h[1];
+    r.s1 = h[2];
+    r.s2 = h[3];
+    return r;
+}
+// get_scale_min_k4 of sub-block j on the three dwords: bytes 0..3 hold sc 0..3 (6 bits) + the top 2 bits of sc 4..7, bytes 4..7 the same for m, bytes 8..11 the
+// low 4 bits of sc 4..7 (low nibble) and m 4..7 (high nibble)
+__device__ __forceinline__ void kq_scale45(const KQHead& h, int j, float& d1, float& m1) {
+    const int i = (j & 3) * 8;
+    uint32_t sc, mn;
+    if (j < 4) {
+        sc = (h.s0 >> i) & 63u;
+        mn = (h.s1 >> i) & 63u;
+    } else {
+        sc = ((h.s2 >> i) & 0xFu) | (((h.s0 >> (i + 6)) & 3u) << 4);
+        mn = ((h.s2 >> (i + 4)) & 0xFu) | (((h.s1 >> (i + 6)) & 3u) << 4);
+    }
+    d1 = __fmul_rn(h.d, (float)sc);
+    m1 = __fmul_rn(h.dmin, (float)mn);
+}
+// group g (weights 64 g .. 64 g + 63), run r (0..3) of a q4_K / q5_K super-block at strip + off: lo = weights 64 g + 8 r + i, hi = weights 64 g + 32 + 8 r + i
+template <int KT>
+__device__ __forceinline__ void kq_dec45(const char* strip, uint32_t off, int g, int r, uint32_t ha, uint32_t hb, float d1lo, float m1lo, float d1hi, float m1hi, half8_t& lo,
+                                         half8_t& hi) {
+    uint32_t qa, qb;
+    kq_ld8<true>(strip, off + KQ<KT>::QS + 32 * g + 8 * r, qa, qb);
+    uint32_t la = qa & 0x0F0F0F0Fu, lb = qb & 0x0F0F0F0Fu, ua = (qa >> 4) & 0x0F0F0F0Fu, ub = (qb >> 4) & 0x0F0F0F0Fu;
+    if (KT == 5) {  // ha, hb: qh[8 r .. 8 r + 7]; bit 2 g is the fifth bit of the low-nibble weight, bit 2 g + 1 of the high-nibble weight
+        la |= ((ha >> (2 * g)) & 0x01010101u) << 4;
+        lb |= ((hb >> (2 * g)) & 0x01010101u) << 4;
+        ua |= ((ha >> (2 * g + 1)) & 0x01010101u) << 4;
+        ub |= ((hb >> (2 * g + 1)) & 0x01010101u) << 4;
+    }
+    lo = kq_w8(la, lb, d1lo, m1lo);
+    hi = kq_w8(ua, ub, d1hi, m1hi);
+}
+// half hf, run r of a q6_K super-block at strip + off (any even off): o[c] = weights 128 hf + 32 c + 8 r + i; ds[c] = d * scales[8 hf + 2 c + r / 2]
+__device__ __forceinline__ void kq_dec6(const char* strip, uint32_t off, int hf, int r, const float (&ds)[4], half8_t (&o)[4]) {
+    uint32_t a0, b0, a1, b1, ha, hb;
+    kq_ld8<false>(strip, off + 64 * hf + 8 * r, a0, b0);
+    kq_ld8<false>(strip, off + 64 * hf + 32 + 8 * r, a1, b1);
+    kq_ld8<false>(strip, off + 128 + 32 * hf + 8 * r, ha, hb);
+    const uint32_t m4 = 0x0F0F0F0Fu, m2 = 0x03030303u;
+    o[0] = kq_w8s((a0 & m4) | ((ha & m2) << 4), (b0 & m4) | ((hb & m2) << 4), ds[0]);
+    o[1] = kq_w8s((a1 & m4) | (((ha >> 2) & m2) << 4), (b1 & m4) | (((hb >> 2) & m2) << 4), ds[1]);
+    o[2] = kq_w8s(((a0 >> 4) & m4) | (((ha >> 4) & m2) << 4), ((b0 >> 4) & m4) | (((hb >> 4) & m2) << 4), ds[2]);
+    o[3] = kq_w8s(((a1 >> 4) & m4) | (((ha >> 6) & m2) << 4), ((b1 >> 4) & m4) | (((hb >> 6) & m2) << 4), ds[3]);
+}
+__device__ __forceinline__ float kq_ds6(const char* strip, uint32_t off, int idx) {
+    const float d = (float)*(const _Float16*)(strip + off + 208);
+    return __fmul_rn(d, (float)(int)*(const int8_t*)(strip + off + 192 + idx));
+}
+
+// =====================================================================================================
+// k_kq_gemm
+// =====================================================================================================
+struct KQArgs {
+    const char* W;
+    int64_t row_bytes;
+    const _Float16* A;  // f16 operand image [rows][lda], or nullptr:
+    int64_t lda;
+    const float* x32;   // ... the f32 activation rows (row stride xs floats), staged as f16(silu?(x) * pre_scale)
+    int64_t xs;
+    float pre_scale;
+    int pre_silu;
+    float* dst;
+    int64_t ldd;
+    _Float16* dst16;
+    int64_t ldd16;
+    const float* bias;
+    const float* residual;
+    const float* gate;
+    int gate_L, gelu;
+    float scale;
+    int R, M;
+    int nseg, nseg_slice;
+    int64_t slab;
+    int a_runL, a_runS;
+};
+
+template <int KT, int RB>
+__global__ __launch_bounds__(256) void k_kq_gemm(KQArgs g) {
+    constexpr int BS  = KQ<KT>::BS;
+    constexpr int NGC = KQ<KT>::NGC;
+    constexpr int CP  = NGC * 16;          // bytes between the columns of a strip
+    constexpr int NGW = 32 * NGC;          // granules of a wave's strip
+    constexpr int NLW = (NGW + 63) / 64;   // loads per lane: 5 / 6 / 7
+    constexpr int RT  = RB * 32;
+    constexpr int AS  = 256 * 2 + 16;      // bytes between A rows in LDS
+    constexpr int NLA = RT * 32 / 256;     // A granules per thread
+    __shared__ __attribute__((aligned(16))) char As[RT * AS];
+    __shared__ __attribute__((aligned(16))) char Wsm[4][32 * CP + 16];  // (+ 16: the third dword of an unaligned 8-byte read at a strip's end)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = lane & 31, kg = lane >> 5;
+    char* Ws           = Wsm[wave];
+    const int64_t row0 = (int64_t)blockIdx.x * RT;
+    const int colw     = (int)blockIdx.y * 128 + wave * 32;
+    const int seg0     = (int)blockIdx.z * g.nseg_slice;
+    const int seg1     = min(g.nseg, seg0 + g.nseg_slice);
+    const char* mycol  = g.W + (int64_t)min(colw + n, g.M - 1) * g.row_bytes;  // this lane's column (q6_K: its phase inside the strip)
+
+    float16_t acc[RB];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[rb][i] = 0.f;
+
+    u32x4_t wreg[NLW], areg[NLA];
+    auto a_phys = [&](int64_t r) -> int64_t {
+        return g.a_runL > 0 ? (int64_t)((uint32_t)r / (uint32_t)g.a_runL) * g.a_runS + (uint32_t)r % (uint32_t)g.a_runL : r;
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (int i = 0; i < NLW; ++i) {
+            const int idx = i * 64 + lane;
+            if (idx < NGW) *(u32x4_t*)(Ws + idx * 16) = wreg[i];
+        }
+#pragma unroll
+        for (int i = 0; i < NLA; ++i) {
+            const int idx = i * 256 + (int)threadIdx.x;
+            *(u32x4_t*)(As + (idx >> 5) * AS + (idx & 31) * 16) = areg[i];
+        }
+    };
+    auto fetch = [&](int seg) {
+#pragma unroll
+        for (int i = 0; i < NLW; ++i) {
+            const int idx = i * 64 + lane;
+            const int col = idx / NGC, gr = idx - col * NGC;
+            const int cc  = min(colw + col, g.M - 1);
+            wreg[i]       = (u32x4_t){0, 0, 0, 0};
+            if (idx < NGW) {
+                const char* p = g.W + (int64_t)cc * g.row_bytes + (int64_t)seg * BS;
+                if (KT == 6) p = (const char*)((uintptr_t)p & ~(uintptr_t)15);
+                wreg[i] = *(const u32x4_t*)(p + gr * 16);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NLA; ++i) {
+            const int idx     = i * 256 + (int)threadIdx.x;
+            const int row     = idx >> 5, gr = idx & 31;
+            const int64_t grw = row0 + row;
+            areg[i]           = (u32x4_t){0, 0, 0, 0};
+            if (grw < g.R) {
+                if (g.A) {
+                    areg[i] = *(const u32x4_t*)(g.A + a_phys(grw) * g.lda + (int64_t)seg * 256 + gr * 8);
+                } else {
+                    const float* xr = g.x32 + grw * g.xs + (int64_t)seg * 256 + gr * 8;
+                    const float4 a = *(const float4*)xr, b = *(const float4*)(xr + 4);
+                    float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+                    half8_t h;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const float u = g.pre_silu ? act_apply<UN_SILU>(v[j]) : v[j];
+                        h[j]          = (_Float16)(u * g.pre_scale);
+                    }
+                    areg[i] = __builtin_bit_cast(u32x4_t, h);
+                }
+            }
+        }
+    };
+    auto step = [&](const half8_t& bf, int k0) {
+        half8_t af[RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) af[rb] = *(const half8_t*)(As + (rb * 32 + n) * AS + k0 * 2);
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[rb], bf, acc[rb], 0, 0, 0);
+    };
+    auto compute_seg = [&](int seg) {
+        if constexpr (KT == 6) {
+            const uint32_t off = (uint32_t)n * CP + (uint32_t)((uintptr_t)(mycol + (int64_t)seg * BS) & 15);
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int r = 2 * t + kg;
+                    float ds[4];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) ds[c] = kq_ds6(Ws, off, 8 * hf + 2 * c + t);
+                    half8_t o[4];
+                    kq_dec6(Ws, off, hf, r, ds, o);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) step(o[c], 128 * hf + 32 * c + 8 * r);
+                }
+        } else {
+            const uint32_t off = (uint32_t)n * CP;
+            const KQHead h     = kq_head45(Ws + off);
+            float d1[8], m1[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) kq_scale45(h, j, d1[j], m1[j]);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int r = 2 * t + kg;
+                uint32_t ha = 0, hb = 0;
+                if (KT == 5) kq_ld8<true>(Ws, off + KQ<KT>::QH + 8 * r, ha, hb);
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    half8_t lo, hi;
+                    kq_dec45<KT>(Ws, off, gq, r, ha, hb, d1[2 * gq], m1[2 * gq], d1[2 * gq + 1], m1[2 * gq + 1], lo, hi);
+                    step(lo, 64 * gq + 8 * r);
+                    step(hi, 64 * gq + 32 + 8 * r);
+                }
+            }
+        }
+    };
+    if (seg0 < seg1) fetch(seg0);
+    for (int seg = seg0; seg < seg1; ++seg) {
+        __syncthreads();  // every wave is done reading the previous segment
+        stash();
+        __syncthreads();
+        if (seg + 1 < seg1) fetch(seg + 1);  // in flight during the MFMAs below
+        compute_seg(seg);
+    }
+    // ---- store: register r of a 32x32 block holds row (r & 3) + 8 (r >> 2) + 4 kg, lanes run along columns
+    const int col = colw + n;
+    if (col >= g.M) return;
+    const float bias = (g.bias && g.slab == 0) ? g.bias[col] : 0.f;
+    float* dst       = g.dst + (g.slab > 0 ? (int64_t)blockIdx.z * g.slab : 0);
+    const int mode   = g.slab > 0 ? 0 : g.gelu ? 1 : g.gate ? 2 : g.residual ? 3 : 0;  // workgroup-uniform
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+        const int rbase = (int)row0 + rb * 32 + 4 * kg;
+        if ((int)row0 + rb * 32 >= g.R) break;
+        if (mode == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rbase + (r & 3) + 8 * (r >> 2);
+                if (row < g.R) dst[(int64_t)row * g.ldd + col] = acc[rb][r] * g.scale + bias;
+            }
+        } else if (mode == 1) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rbase + (r & 3) + 8 * (r >> 2);
+                if (row < g.R) g.dst16[(int64_t)row * g.ldd16 + col] = (_Float16)act_apply<UN_GELU>(acc[rb][r] * g.scale + bias);
+            }
+        } else {
+            float rv[16], gv[16];  // fetched together from clamped rows (cf. k_qgemm16)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = min(rbase + (r & 3) + 8 * (r >> 2), g.R - 1);
+                rv[r]         = g.residual[(int64_t)row * g.ldd + col];
+                gv[r]         = mode == 2 ? g.gate[(int64_t)((uint32_t)row / (uint32_t)g.gate_L) * g.M + col] : 1.f;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rbase + (r & 3) + 8 * (r >> 2);
+                if (row < g.R) dst[(int64_t)row * g.ldd + col] = (acc[rb][r] * g.scale + bias) * gv[r] + rv[r];
+            }
+        }
+    }
+}
+
+// =====================================================================================================
+// k_kq_image
+// =====================================================================================================
+// source row of image row (32-row block rb, n) under k_wswz_linear's three orders; >= R: a zero row
+__device__ __forceinline__ int64_t kq_image_row(int64_t rb, int n, int64_t R, int64_t geglu_inner) {
+    if (geglu_inner > 0) {  // 128-column value / gate pairing
+        const int64_t t = rb >> 2, q = rb & 3, b = (2 * t + (q >> 1)) * 32;
+        return b >= geglu_inner ? R : (q & 1) * geglu_inner + b + n;
+    }
+    if (geglu_inner < 0) {  // 16-column interleave
+        const int64_t inner = -geglu_inner, out = rb * 16 + (n & 15);
+        return out < inner ? ((n & 16) ? inner : 0) + out : R;
+    }
+    return rb * 32 + n;
+}
+
+template <int KT>
+__global__ __launch_bounds__(256) void k_kq_image(half8_t* __restrict__ dst, const char* __restrict__ W, int64_t row_bytes, int64_t R, int64_t kfr, int64_t geglu_inner) {
+    constexpr int BS  = KQ<KT>::BS;
+    constexpr int NGC = KQ<KT>::NGC;
+    constexpr int CP  = NGC * 16;
+    constexpr int NGW = 32 * NGC;
+    __shared__ __attribute__((aligned(16))) char Ws[32 * CP + 16];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = lane & 31, hi = lane >> 5;
+    const int64_t rb = blockIdx.x;
+    const int seg    = blockIdx.y;
+    for (int idx = threadIdx.x; idx < NGW; idx += 256) {
+        const int col    = idx / NGC, gr = idx - col * NGC;
+        const int64_t rr = min(kq_image_row(rb, col, R, geglu_inner), R - 1);
+        const char* p    = W + rr * row_bytes + (int64_t)seg * BS;
+        if (KT == 6) p = (const char*)((uintptr_t)p & ~(uintptr_t)15);
+        *(u32x4_t*)(Ws + idx * 16) = *(const u32x4_t*)(p + gr * 16);
+    }
+    __syncthreads();
+    const int64_t src = kq_image_row(rb, n, R, geglu_inner);
+    const bool real   = src < R;
+    half8_t* out      = dst + (rb * kfr + (int64_t)seg * 16) * 64 + lane;
+    const half8_t z   = {0, 0, 0, 0, 0, 0, 0, 0};
+    if constexpr (KT == 6) {
+        const uint32_t off = (uint32_t)n * CP + (uint32_t)((uintptr_t)(W + min(src, R - 1) * row_bytes + (int64_t)seg * BS) & 15);
+        const int hf = wave >> 1, t = wave & 1, r = 2 * t + hi;
+        float ds[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ds[c] = kq_ds6(Ws, off, 8 * hf + 2 * c + t);
+        half8_t o[4];
+        kq_dec6(Ws, off, hf, r, ds, o);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out[(8 * hf + 2 * c + t) * 64] = real ? o[c] : z;  // weights 128 hf + 32 c + 16 t + 8 hi + i
+    } else {
+        const uint32_t off = (uint32_t)n * CP;
+        const KQHead h     = kq_head45(Ws + off);
+        const int gq       = wave;
+        float d1lo, m1lo, d1hi, m1hi;
+        kq_scale45(h, 2 * gq, d1lo, m1lo);
+        kq_scale45(h, 2 * gq + 1, d1hi, m1hi);
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int r = 2 * rr + hi;
+            uint32_t ha = 0, hb = 0;
+            if (KT == 5) kq_ld8<true>(Ws, off + KQ<KT>::QH + 8 * r, ha, hb);
+            half8_t lo, up;
+            kq_dec45<KT>(Ws, off, gq, r, ha, hb, d1lo, m1lo, d1hi, m1hi, lo, up);
+            out[(4 * gq + rr) * 64]     = real ? lo : z;  // weights 64 g + 16 rr + 8 hi + i
+            out[(4 * gq + 2 + rr) * 64] = real ? up : z;  // weights 64 g + 32 + 16 rr + 8 hi + i
+        }
+    }
+}
+
+// =====================================================================================================
+// launchers
+// =====================================================================================================
+static std::atomic<int64_t> g_kq_route_launches[KQ_ROUTE_COUNT];
+int64_t kq_route_launches(int route) { return route >= 0 && route < KQ_ROUTE_COUNT ? g_kq_route_launches[route].load(std::memory_order_relaxed) : 0; }
+static void kq_route_taken(KQRoute r) { g_kq_route_launches[r].fetch_add(1, std::memory_order_relaxed); }
+
+bool kq_type(int wtype) { return wtype == 12 || wtype == 13 || wtype == 14; }
+static int64_t kq_block_bytes(int wtype) { return wtype == 12 ? 144 : wtype == 13 ? 176 : 210; }
+
+// The row range is k_qgemv's and k_qgemm16's together (options qgemm16_max_rows / qgemm16_rb are shared with k_qgemm16); the hand-over to the image route is
+// set by profiles/kquant_probe.txt (one Linear, weights cache-warm, us):    4096 -> 3072 at 256 / 512 rows      3072 -> 9216 at 256 / 512 rows
+//   q4_K  k_kq_gemm (64-row tiles)                                               56.1 / 75.0                         67.4 /  99.7
+//   q4_0  k_qgemm16, parent commit                                               57.2 / 71.0                         81.0 /  80.5
+//   q6_K  k_kq_gemm                                                              62.9 / 88.5                         89.1 / 134.2
+//   q8_0  k_qgemm16, parent commit                                               60.8 / 75.9                         85.1 /  92.5
+// q4_K keeps q4_0's range (option qgemm16_max_rows, 512): on a par with it, and the same argument holds (inside a model the weights arrive cold and the raw
+// stream is 3.6x smaller than the image; the cache-warm image route measures 34 .. 64 us for every type).  q6_K is on a par with q8_0 up to 256 rows and 1.2 ..
+// 1.5x slower at 512 (its decode reads three byte runs through v_alignbit per four fragments): it hands over at HALF the option, 256 rows.  q5_K (not probed:
+// q4_K's decode plus one bit plane) takes q4_K's range.
+bool kq_gemm_supported(int wtype, int64_t rows, int64_t K, int64_t M) {
+    const int64_t max_rows = wtype == 14 ? qgemm16_max_rows() / 2 : qgemm16_max_rows();
+    return kq_type(wtype) && rows >= 1 && rows <= max_rows && K % 256 == 0 && K >= 256 && M >= 1 && M < (1ll << 30);
+}
+bool kq_image_supported(int wtype, int64_t K) { return kq_type(wtype) && K % 256 == 0 && K >= 256; }
+
+// The grid of a launch, tile height and K slices together (the slices are counted on the tiles that are launched).
+//   RB     32-row blocks per workgroup: 1 up to 32 rows, else 2; option qgemm16_rb = 1 / 2 / 4 forces that above 32 rows.  128-row tiles (RB 4: 86 .. 96 KB of
+//          LDS and ~340 registers, one workgroup per CU) measured SLOWER than 64-row tiles on every probed shape, 256 rows to 4608 (q4_K 4096 -> 3072 at 512 rows
+//          90.6 vs 75.0 us, 3072 -> 12288 at 4608 rows 870 vs 839 us; profiles/kquant_probe.txt): the default never takes them.
+//   Split-K.  A launch of T = row tiles x ceil(M / 128) workgroups streams its weights at the HBM rate only with about two workgroups on each of the 256 CUs
+//          (one is one wave per SIMD walking fetch -> LDS -> decode -> MFMA; a second hides that chain): S = 512 / T slices, each at least two segments long
+//          (so that the prefetch overlaps something), at most 16.  FLUX modulation 3072 -> 18432 at 1 or 2 rows: T = 144, S = 3 -> 432 workgroups of 4 segments.
+//          can_split = false (gated / GELU epilogues): S = 1.
+static void kq_gemm_grid(int64_t rows, int64_t K, int64_t M, bool can_split, int& rb, int& S) {
+    const int opt = qgemm16_rb();
+    rb            = rows <= 32 ? 1 : 2;
+    if (opt == 1 || opt == 2 || opt == 4) rb = rows <= 32 ? 1 : (rows <= 64 && opt > 2) ? 2 : opt;
+    auto tiles  = [&](int b) { return ((rows + 32 * b - 1) / (32 * b)) * ((M + 127) / 128); };
+    auto slices = [&](int64_t t) {
+        int64_t n = can_split ? std::min<int64_t>(std::min<int64_t>(512 / t, K / 256 / 2), 16) : 1;
+        return n < 2 ? 1 : (int)n;
+    };
+    S = slices(tiles(rb));
+}
+int kq_gemm_split_k(int64_t rows, int64_t K, int64_t M) {
+    int rb, S;
+    kq_gemm_grid(rows, K, M, true, rb, S);
+    return S;
+}
+
+void launch_kq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const void* a16, int64_t lda, int64_t rows, const void* wraw, int wtype, int64_t K, int64_t M,
+                    const Epilogue& ep, float* splitk_ws, int splitk_S, const float* x32, int64_t xs, float pre_scale, bool pre_silu) {
+    if (!kq_gemm_supported(wtype, rows, K, M) || (a16 == nullptr) == (x32 == nullptr) || (ep.gelu && !dst16) || (!ep.gelu && !dst) || (ep.gate && !ep.residual) ||
+        (wtype != 14 && ((uintptr_t)wraw & 15))) {
+        fprintf(stderr, "ggml-mi355x: invalid k_kq_gemm request\n");
+        abort();
+    }
+    const int64_t rowb = K / 256 * kq_block_bytes(wtype);
+    KScope ks_(s, KF_QGEMM, 2.0 * rows * K * M, (double)M * rowb + (double)rows * K * (a16 ? 2.0 : 4.0) + (double)rows * M * 4.0);
+    KQArgs g{};
+    g.W = (const char*)wraw;
+    g.row_bytes = rowb;
+    g.A = (const _Float16*)a16; g.lda = lda;
+    g.x32 = x32; g.xs = xs; g.pre_scale = pre_scale; g.pre_silu = pre_silu ? 1 : 0;
+    g.dst = dst; g.ldd = M; g.dst16 = (_Float16*)dst16; g.ldd16 = ldd16;
+    g.bias = ep.bias; g.residual = ep.residual; g.gate = ep.gate; g.gate_L = ep.gate_L > 0 ? ep.gate_L : 1; g.gelu = ep.gelu; g.scale = ep.scale;
+    g.R = (int)rows; g.M = (int)M;
+    if (ep.a_run_L > 0 && ep.a_run_S != ep.a_run_L) {
+        g.a_runL = (int)ep.a_run_L;
+        g.a_runS = (int)ep.a_run_S;
+    }
+    g.nseg = (int)(K / 256);
+    const bool can_split = splitk_ws && splitk_S > 1 && !ep.gate && !ep.gelu && dst;
+    int rb, S;
+    kq_gemm_grid(rows, K, M, can_split, rb, S);
+    if (can_split && S != splitk_S) {  // the planner sized the workspace with kq_gemm_split_k: same function, same answer
+        fprintf(stderr, "ggml-mi355x: k_kq_gemm launched with %d K slices where its rule gives %d\n", splitk_S, S);
+        abort();
+    }
+    g.nseg_slice = (g.nseg + S - 1) / S;
+    if (S > 1) {
+        g.slab = rows * M;
+        g.dst  = splitk_ws;
+    }
+    const dim3 grid((unsigned)((rows + rb * 32 - 1) / (rb * 32)), (unsigned)((M + 127) / 128), (unsigned)S);
+    kq_route_taken(rb == 1 ? KQ_GEMM_RB1 : rb == 2 ? KQ_GEMM_RB2 : KQ_GEMM_RB4);
+#define KQ_LAUNCH(KT_)                                        \
+    do {                                                      \
+        if (rb == 1) k_kq_gemm<KT_, 1><<<grid, 256, 0, s>>>(g); \
+        else if (rb == 2) k_kq_gemm<KT_, 2><<<grid, 256, 0, s>>>(g); \
+        else k_kq_gemm<KT_, 4><<<grid, 256, 0, s>>>(g);       \
+    } while (0)
+    if (wtype == 12) KQ_LAUNCH(4);
+    else if (wtype == 13) KQ_LAUNCH(5);
+    else KQ_LAUNCH(6);
+#undef KQ_LAUNCH
+    if (S > 1) {
+        kq_route_taken(KQ_GEMM_REDUCE);
+        splitk_reduce_rows(s, dst, splitk_ws, S, rows * M, ep.bias, M, ep.residual);
+    }
+}
+
+// dst: image of wswz_bytes(R, K) bytes (rows padded to 128); geglu_inner as launch_wswz_linear takes it
+void launch_kq_image(hipStream_t s, void* dst, const void* wraw, int wtype, int64_t K, int64_t R, int64_t geglu_inner) {
+    if (!kq_image_supported(wtype, K) || R < 1 || (wtype != 14 && ((uintptr_t)wraw & 15))) {
+        fprintf(stderr, "ggml-mi355x: invalid k_kq_image request\n");
+        abort();
+    }
+    const int64_t Rp = (R + 127) / 128 * 128, rowb = K / 256 * kq_block_bytes(wtype);
+    KScope ks_(s, KF_PACK_F16, 0.0, (double)R * rowb + (double)Rp * K * 2.0);
+    const dim3 grid((unsigned)(Rp / 32), (unsigned)(K / 256));
+    kq_route_taken(KQ_IMAGE);
+    if (wtype == 12) k_kq_image<4><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, rowb, R, K / 16, geglu_inner);
+    else if (wtype == 13) k_kq_image<5><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, rowb, R, K / 16, geglu_inner);
+    else k_kq_image<6><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, rowb, R, K / 16, geglu_inner);
+}
+
+}  // namespace mi355x

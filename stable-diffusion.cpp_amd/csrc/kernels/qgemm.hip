@@ -817,8 +817,10 @@ void launch_wswz_q(hipStream_t s, void* dst, const void* wraw, int wtype, int64_
 // qgemm16_max_rows = 8192 the step takes 167 ms (+30 %) for 26 MB of images instead of 12.9 GB — the resident-quantised mode, selectable.
 static int g_qg16_max_rows = 512;
 void qgemm16_set_max_rows(int v) { g_qg16_max_rows = v; }
+int qgemm16_max_rows() { return g_qg16_max_rows; }
 static int g_qg16_rb = 3;  // option "qgemm16_rb": 32-row blocks per workgroup tile (1 / 2 / 4 forced); 0 = by row count only; 3 (default) = by row count, 64-row tiles for small grids (FLUX text stream: 7.0 -> 6.1 ms per forward, profiles/r05d_family_flux_qgemm16_rb.txt)
 void qgemm16_set_rb(int v) { g_qg16_rb = v; }
+int qgemm16_rb() { return g_qg16_rb; }
 
 bool qgemm16_supported(int wtype, int64_t rows, int64_t K, int64_t M) {
     // column pieces are fetched with 16-byte loads: rows of the weight must start 16-byte aligned (K % 256 == 0); 1-2 rows belong to k_qgemv
