@@ -446,6 +446,7 @@ static inline int64_t ggml_abi_blck_size(enum ggml_type t) {
         case GGML_TYPE_Q5_1:
         case GGML_TYPE_Q8_0:
         case GGML_TYPE_Q8_1:
+        case GGML_TYPE_IQ4_NL:
             return 32;
         case GGML_TYPE_Q4_K:
         case GGML_TYPE_Q5_K:
@@ -461,9 +462,10 @@ static inline size_t ggml_abi_type_size(enum ggml_type t) {
         case GGML_TYPE_F16: return 2;
         case GGML_TYPE_BF16: return 2;
         case GGML_TYPE_Q4_0: return 18; /* half d; uint8 qs[16] */
-        case GGML_TYPE_Q4_1: return 20;
-        case GGML_TYPE_Q5_0: return 22;
-        case GGML_TYPE_Q5_1: return 24;
+        case GGML_TYPE_Q4_1: return 20; /* half d, m; uint8 qs[16] */
+        case GGML_TYPE_Q5_0: return 22; /* half d; uint8 qh[4]; uint8 qs[16] */
+        case GGML_TYPE_Q5_1: return 24; /* half d, m; uint8 qh[4]; uint8 qs[16] */
+        case GGML_TYPE_IQ4_NL: return 18; /* half d; uint8 qs[16] (codes into a 16-entry table) */
         case GGML_TYPE_Q8_0: return 34; /* half d; int8 qs[32] */
         case GGML_TYPE_Q8_1: return 36;
         case GGML_TYPE_Q4_K: return 144; /* half d, dmin; uint8 scales[12]; uint8 qs[128] */

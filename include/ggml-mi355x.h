@@ -191,6 +191,12 @@ struct ggml_backend_mi355x_stats {
     int64_t lin_kq_gemm_reduce;      /* the slab reduce behind a split launch_kq_gemm */
     int64_t lin_kq_image;            /* launch_kq_image: the f16 weight image of a K-quant weight (cached once per weight, or just in time under option jit_qimages) */
     int64_t kquant_linears;          /* Linears with a q4_K / q5_K / q6_K weight (per plan, whatever route they take) */
+    /* 32-weight block Linear weights (q4_1 / q5_0 / q5_1 / iq4_nl raw in HBM, kernels/bquant.hip); lin_bq_*: per launch call, in the order of BQRoute */
+    int64_t lin_bq_gemm_rb1;         /* launch_bq_gemm: k_bq_gemm<BT, 1> (32-row tiles; 1 .. 4 rows read their f32 rows themselves) */
+    int64_t lin_bq_gemm_rb2;         /* ... k_bq_gemm<BT, 2> */
+    int64_t lin_bq_gemm_reduce;      /* the slab reduce behind a split launch_bq_gemm */
+    int64_t lin_bq_image;            /* launch_bq_image: the f16 weight image of such a weight (cached once per weight, or just in time under option jit_qimages) */
+    int64_t bquant_linears;          /* Linears with a q4_1 / q5_0 / q5_1 / iq4_nl weight (per plan, whatever route they take) */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and

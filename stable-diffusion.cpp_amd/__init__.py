@@ -24,6 +24,7 @@ BACKEND_LIB = Path(os.environ.get("SDCPP_BACKEND_LIB", str(LIB_DIR / "libggml-mi
 # ggml_type numeric values (include/ggml-abi.h)
 F32, F16, Q4_0, Q8_0, I32, BF16 = 0, 1, 2, 8, 26, 30
 Q4_K, Q5_K, Q6_K = 12, 13, 14  # K-quant super-blocks (256 weights): Linear weights only
+Q4_1, Q5_0, Q5_1, IQ4_NL = 3, 6, 7, 20  # 32-weight blocks kept raw on the device (kernels/bquant.hip): Linear weights only
 TYPE_SIZE = {F32: 4, F16: 2, BF16: 2, I32: 4}
 
 # sd_model_family_t
@@ -427,7 +428,8 @@ _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned 
                         "lin_fgemv_f16 lin_fgemv_f32 lin_wswz_q "
                         "fused_ip_attn flash_short_ip_launches "
                         "fused_patch_embed patch_embed_launches "
-                        "lin_kq_gemm_rb1 lin_kq_gemm_rb2 lin_kq_gemm_rb4 lin_kq_gemm_reduce lin_kq_image kquant_linears").split()
+                        "lin_kq_gemm_rb1 lin_kq_gemm_rb2 lin_kq_gemm_rb4 lin_kq_gemm_reduce lin_kq_image kquant_linears "
+                        "lin_bq_gemm_rb1 lin_bq_gemm_rb2 lin_bq_gemm_reduce lin_bq_image bquant_linears").split()
 
 
 class BackendStats(C.Structure):

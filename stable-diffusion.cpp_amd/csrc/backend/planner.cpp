@@ -270,6 +270,12 @@ inline bool kq_weight_ok(const ggml_tensor* w) {
     return kq_type((int)w->type) && w->ne[0] >= 256 && w->ne[0] % 256 == 0 && w->ne[2] == 1 && w->ne[3] == 1 && w->nb[0] == ggml_abi_type_size(w->type) &&
            (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, w->ne[0]);
 }
+// a q4_1 / q5_0 / q5_1 / iq4_nl Linear weight the block kernels (kernels/bquant.hip) take: whole 32-weight blocks per row, rows packed
+inline bool bq_weight_ok(const ggml_tensor* w) {
+    return bq_type((int)w->type) && w->ne[0] >= 32 && w->ne[0] % 32 == 0 && w->ne[2] == 1 && w->ne[3] == 1 && w->nb[0] == ggml_abi_type_size(w->type) &&
+           (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, w->ne[0]);
+}
+inline const char* bq_type_name(int t) { return t == GGML_TYPE_Q4_1 ? "q4_1" : t == GGML_TYPE_Q5_0 ? "q5_0" : t == GGML_TYPE_Q5_1 ? "q5_1" : "iq4_nl"; }
 
 uint64_t fnv(uint64_t h, const void* p, size_t n) {
     const unsigned char* c = (const unsigned char*)p;
@@ -724,6 +730,8 @@ const void* get_swz_linear(Planner* P, const ggml_tensor* w, hipStream_t s, int 
     if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
     if (kq_type((int)w->type))  // K-quant super-blocks: k_kq_image (every sub-block scale decoded once), never the per-element wload of k_wswz_linear
         launch_kq_image(s, d, w->data, (int)w->type, K, R, geglu == 2 ? -(R / 2) : geglu_pairs ? R / 2 : 0);
+    else if (bq_type((int)w->type))  // q4_1 / q5_0 / q5_1 / iq4_nl blocks: k_bq_image
+        launch_bq_image(s, d, w->data, (int)w->type, K, R, geglu == 2 ? -(R / 2) : geglu_pairs ? R / 2 : 0);
     else
         launch_wswz_linear(s, d, w->data, (int)w->type, K, R, (int64_t)w->nb[1], geglu == 2 ? -(R / 2) : geglu_pairs ? R / 2 : 0);
     P->swz[key] = {d, bytes, w->data, ggml_abi_nbytes(w)};
@@ -967,7 +975,7 @@ bool linear_fast_ok(const ggml_tensor* n) {
     if (!g_opt.mfma_gemm) return false;
     if (!is_static_weight(w) || !is_f32(x) || !is_f32(n)) return false;
     if (!(w->type == GGML_TYPE_F16 || w->type == GGML_TYPE_F32 || w->type == GGML_TYPE_BF16 || w->type == GGML_TYPE_Q8_0 || w->type == GGML_TYPE_Q4_0 ||
-          (kq_weight_ok(w) && aligned16(w->data))))
+          ((kq_weight_ok(w) || bq_weight_ok(w)) && aligned16(w->data))))
         return false;
     if (w->ne[2] != 1 || w->ne[3] != 1 || !contig(w)) return false;
     if (x->nb[0] != 4 || x->ne[0] % 4 != 0 || x->nb[1] % 16 != 0 || !aligned16(x->data)) return false;
@@ -1292,10 +1300,13 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     const ggml_tensor* lastt   = gi.node(last);
     const bool src_safe        = xsrc == x || !overlaps(lastt->data, ggml_abi_nbytes(lastt), xsrc->data, ggml_abi_nbytes(xsrc));
     // K-quant weights (q4_K / q5_K / q6_K) under 1 .. 4 rows: k_kq_gemm reads the f32 rows itself (deferred SiLU applied while they are staged), as k_qgemv does
-    const bool kq = kq_type((int)w->type);
+    // (q4_1 / q5_0 / q5_1 / iq4_nl blocks: k_bq_gemm, kernels/bquant.hip, the same way on every route below)
+    const bool kq = kq_type((int)w->type), bq = bq_type((int)w->type);
     if (kq) STAT(kquant_linears)++;
-    if (kq && g_opt.qgemm16 && tokens <= 4 && plain_epi && simple_rows && src_safe && kq_gemm_supported((int)w->type, tokens, K, M)) {
-        const int S        = kq_gemm_split_k(tokens, K, M);
+    if (bq) STAT(bquant_linears)++;
+    const bool rawq_gemm = kq ? kq_gemm_supported((int)w->type, tokens, K, M) : bq && bq_gemm_supported((int)w->type, tokens, K, M);
+    if (g_opt.qgemm16 && tokens <= 4 && plain_epi && simple_rows && src_safe && rawq_gemm) {
+        const int S        = kq ? kq_gemm_split_k(tokens, K, M) : bq_gemm_split_k(tokens, K, M);
         const size_t wsoff = S > 1 ? B.alloc((size_t)S * tokens * M * 4) : 0;
         Planner* P         = B.P;
         float* qdst        = (float*)gi.node(last)->data;
@@ -1305,7 +1316,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         const int wt       = (int)w->type;
         const bool silu    = xsrc != x;
         B.emit_at(emit_node, i, [=](hipStream_t st) {
-            launch_kq_gemm(st, qdst, nullptr, 0, nullptr, 0, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S, qx, qxs, 1.0f, silu);
+            (kq ? launch_kq_gemm : launch_bq_gemm)(st, qdst, nullptr, 0, nullptr, 0, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S, qx, qxs, 1.0f, silu);
         });
         STAT(fused_linear)++;
         if (silu) STAT(fused_presilu)++;
@@ -1350,7 +1361,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     // ... and under a few hundred rows (text-stream Linears, text encoders): the raw blocks again, dequantised in registers on the way into the
     // MFMA units (k_qgemm16) — below ~300 rows a GEMM is bound by its weight stream, and the quantised stream is 1.9x / 3.6x smaller
     // (K-quant weights: k_kq_gemm in its place, from one row on)
-    const bool useq  = g_opt.qgemm16 && hm_d == 0 && geglu_out < 0 && (kq ? kq_gemm_supported((int)w->type, tokens, K, M) : qgemm16_supported((int)w->type, tokens, K, M));
+    const bool useq  = g_opt.qgemm16 && hm_d == 0 && geglu_out < 0 && (kq || bq ? rawq_gemm : qgemm16_supported((int)w->type, tokens, K, M));
     const void* wraw = w->data;
     const int wt     = (int)w->type;
     // resident-quantised weights (option jit_qimages = least activation rows, default 4096; 1 = always, 0 = never): such a Linear gets NO cached f16 image — the image is
@@ -1366,7 +1377,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         ep.qrow_bytes = (int64_t)w->nb[1];
         STAT(qinloop_linears)++;
     }
-    const bool jit = !useq && !qin && g_opt.jit_qimages > 0 && tokens >= g_opt.jit_qimages && geglu_out < 0 && hm_d == 0 && !B.hm_hoisting && (wswz_q_supported((int)w->type, K) || kq_image_supported((int)w->type, K)) &&
+    const bool jit = !useq && !qin && g_opt.jit_qimages > 0 && tokens >= g_opt.jit_qimages && geglu_out < 0 && hm_d == 0 && !B.hm_hoisting && (wswz_q_supported((int)w->type, K) || kq_image_supported((int)w->type, K) || bq_image_supported((int)w->type, K)) &&
                      (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, K) && aligned16(w->data);
     const int geglu_mode = geglu_out >= 0 ? gemm16_geglu_mode(tokens, M, K) : 0;
     const void* swz = useq ? nullptr : qin ? w->data : (jit ? B.P->jit_buffer(wswz_bytes(M, K), B.jit_seq[wswz_bytes(M, K)]++) : get_swz_linear(B.P, w, s, geglu_mode));
@@ -1376,6 +1387,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         const int wty     = (int)w->type;
         B.emit_at(emit_node, i, [=](hipStream_t st) {
             if (kq) launch_kq_image(st, jb, wsrc, wty, K, M);
+            else if (bq) launch_bq_image(st, jb, wsrc, wty, K, M);
             else launch_wswz_q(st, jb, wsrc, wty, K, M);
         });
         STAT(jit_images)++;
@@ -1452,9 +1464,10 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
         if (useq) {
             B.emit([=](hipStream_t st) {
                 if (kq) launch_kq_gemm(st, nullptr, P->arena + ooff, M, P->arena + off, ld, tokens, wraw, wt, K, M, ep);
+                else if (bq) launch_bq_gemm(st, nullptr, P->arena + ooff, M, P->arena + off, ld, tokens, wraw, wt, K, M, ep);
                 else launch_qgemm16(st, nullptr, P->arena + ooff, M, P->arena + off, ld, tokens, wraw, wt, K, M, ep);
             });
-            if (!kq) STAT(qgemm16_linears)++;
+            if (!kq && !bq) STAT(qgemm16_linears)++;
         } else {
             const Builder::Split sk = B.plan_split(tokens, M, K, false, false);
             B.emit([=](hipStream_t st) { launch_gemm16_linear(st, nullptr, P->arena + ooff, M, P->arena + off, ld, swz, tokens, K, M, M, ep, 0, 0, 0, sk.ws(P), sk.cnt(P), sk.S); });
@@ -1494,15 +1507,16 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
                 });
         }
     } else if (useq) {
-        const int S        = ep.gate ? 1 : kq ? kq_gemm_split_k(tokens, K, M) : qgemm16_split_k(tokens, K, M);
+        const int S        = ep.gate ? 1 : kq ? kq_gemm_split_k(tokens, K, M) : bq ? bq_gemm_split_k(tokens, K, M) : qgemm16_split_k(tokens, K, M);
         const size_t wsoff = S > 1 ? B.alloc((size_t)S * tokens * M * 4) : 0;
         B.emit_at(emit_node, i, [=](hipStream_t st) {
             float* qd = redir ? (float*)(P->arena + redir_off) : dst;
             if (kq) launch_kq_gemm(st, qd, nullptr, 0, P->arena + off, ld, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S);
+            else if (bq) launch_bq_gemm(st, qd, nullptr, 0, P->arena + off, ld, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S);
             else launch_qgemm16(st, qd, nullptr, 0, P->arena + off, ld, tokens, wraw, wt, K, M, ep, S > 1 ? (float*)(P->arena + wsoff) : nullptr, S);
         });
         if (redir) B.redirect_taken.insert(gi.node(last));
-        if (!kq) STAT(qgemm16_linears)++;
+        if (!kq && !bq) STAT(qgemm16_linears)++;
     } else if (g_opt.fuse_rows16 && !ep.gate && emit_node == i && M % 64 == 0 && x->ne[3] == 1 && only_consumer_is_tokens_to_conv(gi, last)) {
         // FF2 (+bias, +residual) of a SpatialTransformer whose result only proj_out reads (block.hpp:566-572): write the 1x1 conv's f16 operand
         // rows directly — no f32 tensor, no pack pass (the conv rounds its input to f16 anyway: same rounding point).  Option fuse_rows16,
@@ -3073,6 +3087,11 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                         n->src[0]->type == GGML_TYPE_Q4_K ? "q4_K" : n->src[0]->type == GGML_TYPE_Q5_K ? "q5_K" : "q6_K");
                 return false;
             }
+            if (bq_type((int)n->src[0]->type)) {  // ... nor over q4_1 / q5_0 / q5_1 / iq4_nl blocks
+                fprintf(stderr, "[ggml-mi355x] node %d: MUL_MAT with a %s weight outside the Linear path (weight not in a WEIGHTS buffer, unaligned rows, or option mfma_gemm = 0)\n", i,
+                        bq_type_name((int)n->src[0]->type));
+                return false;
+            }
             View4 a = view_of(n->src[0]), b = view_of(n->src[1]);
             View4 d = view_of(n);
             B.emit([=](hipStream_t st) { launch_mul_mat_generic(st, (float*)d.data, d.ne, d.nb, a, b); });
@@ -4374,7 +4393,7 @@ bool build_plan(Planner* P, Plan* plan, const ggml_cgraph* g, hipStream_t s, boo
                     const ggml_tensor* w = gi.node(c)->src[0];
                     const int64_t rows   = n->ne[1] * n->ne[2] * n->ne[3];
                     if ((g_opt.fgemv && fgemv_supported((int)w->type, rows, w->ne[0])) || (g_opt.qgemv && qgemv_supported((int)w->type, rows, w->ne[0])) ||
-                        (g_opt.qgemm16 && rows <= 4 && kq_gemm_supported((int)w->type, rows, w->ne[0], w->ne[1]))) {  // k_kq_gemm stages 1 .. 4 f32 rows itself
+                        (g_opt.qgemm16 && rows <= 4 && (kq_gemm_supported((int)w->type, rows, w->ne[0], w->ne[1]) || bq_gemm_supported((int)w->type, rows, w->ne[0], w->ne[1])))) {  // k_kq_gemm / k_bq_gemm stage 1 .. 4 f32 rows themselves
                         B.presilu[n] = src;
                         chain        = {i};
                         ok           = true;
@@ -4693,8 +4712,9 @@ bool planner_supports_op(const ggml_tensor* n) {
             const bool bt = b->type == GGML_TYPE_F32 || b->type == GGML_TYPE_F16;
             // q4_K / q5_K / q6_K: Linear weights only (the K-quant kernels; there is no generic matmul over super-blocks)
             // — and what linear_fast_ok asks that is known here; what is not (the weight's buffer usage, the addresses) makes the plan fail loudly (plan_single)
-            if (kq_type((int)a->type))
-                return g_opt.mfma_gemm && kq_weight_ok(a) && ggml_abi_is_contiguous(a) && b->type == GGML_TYPE_F32 && b->nb[0] == 4 && b->ne[0] % 4 == 0 && b->nb[1] % 16 == 0 &&
+            // q4_1 / q5_0 / q5_1 / iq4_nl (kernels/bquant.hip): the same, with whole 32-weight blocks per row
+            if (kq_type((int)a->type) || bq_type((int)a->type))
+                return g_opt.mfma_gemm && (kq_weight_ok(a) || bq_weight_ok(a)) && ggml_abi_is_contiguous(a) && b->type == GGML_TYPE_F32 && b->nb[0] == 4 && b->ne[0] % 4 == 0 && b->nb[1] % 16 == 0 &&
                        ggml_abi_is_contiguous(n);
             return at && bt && a->nb[0] == ggml_abi_type_size(a->type) && b->nb[0] == ggml_abi_type_size(b->type);
         }
@@ -4765,6 +4785,10 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     static_assert(offsetof(ggml_backend_mi355x_stats, lin_kq_image) - offsetof(ggml_backend_mi355x_stats, lin_kq_gemm_rb1) == (KQ_ROUTE_COUNT - 1) * sizeof(int64_t),
                   "ggml_backend_mi355x_stats: one lin_kq_* field per KQRoute, in its order");
     for (int r = 0; r < KQ_ROUTE_COUNT; ++r) (&o->lin_kq_gemm_rb1)[r] = kq_route_launches(r);
+    // ... and the 32-weight block launchers (kernels/bquant.hip): the lin_bq_* fields lie in the order of BQRoute
+    static_assert(offsetof(ggml_backend_mi355x_stats, lin_bq_image) - offsetof(ggml_backend_mi355x_stats, lin_bq_gemm_rb1) == (BQ_ROUTE_COUNT - 1) * sizeof(int64_t),
+                  "ggml_backend_mi355x_stats: one lin_bq_* field per BQRoute, in its order");
+    for (int r = 0; r < BQ_ROUTE_COUNT; ++r) (&o->lin_bq_gemm_rb1)[r] = bq_route_launches(r);
 }
 
 namespace {

@@ -133,6 +133,10 @@ const char* ggml_type_name(enum ggml_type type) {
         case GGML_TYPE_F16: return "f16";
         case GGML_TYPE_BF16: return "bf16";
         case GGML_TYPE_Q4_0: return "q4_0";
+        case GGML_TYPE_Q4_1: return "q4_1";
+        case GGML_TYPE_Q5_0: return "q5_0";
+        case GGML_TYPE_Q5_1: return "q5_1";
+        case GGML_TYPE_IQ4_NL: return "iq4_nl";
         case GGML_TYPE_Q8_0: return "q8_0";
         case GGML_TYPE_Q4_K: return "q4_K";
         case GGML_TYPE_Q5_K: return "q5_K";
@@ -421,6 +425,131 @@ static void quantize_row_q4_0(const float* x, uint8_t* y, int64_t k) {
     }
 }
 
+// ---- q4_1 / q5_0 / q5_1 / iq4_nl (32 weights per block, little-endian fields; byte j of qs holds element j in its low and element j + 16 in its high nibble,
+// the fifth bit of element e is bit e of the u32 qh).  The decoders restate upstream's dequantize_row_*: the values the device kernels (kernels/bquant.hip)
+// round to f16, and what the model loader decodes a file tensor of these types with.
+//   q4_1 {f16 d, f16 m, u8 qs[16]}             x = q * d + m
+//   q5_0 {f16 d, u8 qh[4], u8 qs[16]}          x = (q - 16) * d
+//   q5_1 {f16 d, f16 m, u8 qh[4], u8 qs[16]}   x = q * d + m
+//   iq4_nl {f16 d, u8 qs[16]}                  x = d * kvalues[q]
+// Every product is exact in f32 (at most 7 x 11 bits), so "+ m" is the only rounding and a contracted q * d + m gives the same value.
+static const int8_t kvalues_iq4nl[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+struct BlockQ {  // field offsets inside a block of `type`
+    int bs, m, qh, qs;
+};
+static inline BlockQ block_q_layout(enum ggml_type type) {
+    switch (type) {
+        case GGML_TYPE_Q4_1: return {20, 2, -1, 4};
+        case GGML_TYPE_Q5_0: return {22, -1, 2, 6};
+        case GGML_TYPE_Q5_1: return {24, 2, 4, 8};
+        default: return {18, -1, -1, 2};  // iq4_nl
+    }
+}
+static void dequantize_row_q4_1_q5(enum ggml_type type, const uint8_t* raw, float* dst, int64_t n) {
+    const BlockQ L = block_q_layout(type);
+    for (int64_t b = 0; b < n / 32; ++b) {
+        const uint8_t* p = raw + b * L.bs;
+        ggml_fp16_t dh, mh = 0;
+        memcpy(&dh, p, 2);
+        if (L.m >= 0) memcpy(&mh, p + L.m, 2);
+        const float d = ggml_fp16_to_fp32(dh), m = L.m >= 0 ? ggml_fp16_to_fp32(mh) : 0.f;
+        uint32_t qh = 0;
+        if (L.qh >= 0) memcpy(&qh, p + L.qh, 4);
+        const uint8_t* qs = p + L.qs;
+        float* y          = dst + b * 32;
+        for (int j = 0; j < 16; ++j) {
+            const int x0 = (qs[j] & 0x0F) | (int)(((qh >> j) & 1u) << 4), x1 = (qs[j] >> 4) | (int)(((qh >> (j + 16)) & 1u) << 4);
+            if (type == GGML_TYPE_Q5_0) {
+                y[j]      = (float)(x0 - 16) * d;
+                y[j + 16] = (float)(x1 - 16) * d;
+            } else {
+                y[j]      = (float)x0 * d + m;
+                y[j + 16] = (float)x1 * d + m;
+            }
+        }
+    }
+}
+static void dequantize_row_iq4_nl(const uint8_t* raw, float* dst, int64_t n) {
+    for (int64_t b = 0; b < n / 32; ++b) {
+        const uint8_t* p = raw + b * 18;
+        ggml_fp16_t dh;
+        memcpy(&dh, p, 2);
+        const float d = ggml_fp16_to_fp32(dh);
+        float* y      = dst + b * 32;
+        for (int j = 0; j < 16; ++j) {
+            y[j]      = d * (float)kvalues_iq4nl[p[2 + j] & 0xF];
+            y[j + 16] = d * (float)kvalues_iq4nl[p[2 + j] >> 4];
+        }
+    }
+}
+// Encoders: q4_1 / q5_0 / q5_1 by the rules of upstream's quantize_row_*_ref (q4_1 / q5_1: d = (max - min) / 15 or 31, m = min; q5_0: the value of largest
+// magnitude, with its sign, maps onto -16).
+static void quantize_row_q4_1_q5(enum ggml_type type, const float* x, uint8_t* y, int64_t k) {
+    const BlockQ L = block_q_layout(type);
+    const int qmax = type == GGML_TYPE_Q4_1 ? 15 : 31;
+    for (int64_t i = 0; i < k / 32; ++i, x += 32) {
+        uint8_t* p = y + i * L.bs;
+        float d, mn = 0.f, add;
+        if (type == GGML_TYPE_Q5_0) {
+            float amax = 0.f, maxv = 0.f;
+            for (int j = 0; j < 32; ++j)
+                if (amax < fabsf(x[j])) {
+                    amax = fabsf(x[j]);
+                    maxv = x[j];
+                }
+            d   = maxv / -16.0f;
+            add = 16.5f;
+        } else {
+            float mx = x[0];
+            mn       = x[0];
+            for (int j = 1; j < 32; ++j) {
+                mn = std::min(mn, x[j]);
+                mx = std::max(mx, x[j]);
+            }
+            d   = (mx - mn) / (float)qmax;
+            add = 0.5f;
+            const ggml_fp16_t mh = ggml_fp32_to_fp16(mn);
+            memcpy(p + L.m, &mh, 2);
+        }
+        const float id      = d ? 1.0f / d : 0.0f;
+        const ggml_fp16_t h = ggml_fp32_to_fp16(d);
+        memcpy(p, &h, 2);
+        uint32_t qh = 0;
+        for (int j = 0; j < 16; ++j) {
+            const int q0 = std::min(qmax, (int)(int8_t)((x[j] - mn) * id + add)), q1 = std::min(qmax, (int)(int8_t)((x[j + 16] - mn) * id + add));
+            p[L.qs + j]  = (uint8_t)((q0 & 0x0F) | ((q1 & 0x0F) << 4));
+            qh |= (uint32_t)((q0 & 0x10) >> 4) << j;
+            qh |= (uint32_t)((q1 & 0x10) >> 4) << (j + 16);
+        }
+        if (L.qh >= 0) memcpy(p + L.qh, &qh, 4);
+    }
+}
+// iq4_nl: a PLAIN encoder, NOT ggml's search (quantize_row_iq4_nl_impl tries several scales and weights the error): the value of largest magnitude, with its
+// sign, maps onto the table's -127, every other value takes the nearest table entry.  It exists for synthetic weights and for file tensors of another type; a
+// tensor a file already stores as iq4_nl is copied raw and never passes through it.
+static void quantize_row_iq4_nl(const float* x, uint8_t* y, int64_t k) {
+    for (int64_t i = 0; i < k / 32; ++i, x += 32) {
+        uint8_t* p = y + i * 18;
+        float amax = 0.f, maxv = 0.f;
+        for (int j = 0; j < 32; ++j)
+            if (amax < fabsf(x[j])) {
+                amax = fabsf(x[j]);
+                maxv = x[j];
+            }
+        const float d       = maxv / -127.0f;
+        const float id      = d ? 1.0f / d : 0.0f;
+        const ggml_fp16_t h = ggml_fp32_to_fp16(d);
+        memcpy(p, &h, 2);
+        auto nearest = [&](float v) {
+            int best = 0;
+            for (int c = 1; c < 16; ++c)
+                if (fabsf(v - (float)kvalues_iq4nl[c]) < fabsf(v - (float)kvalues_iq4nl[best])) best = c;
+            return best;
+        };
+        for (int j = 0; j < 16; ++j) p[2 + j] = (uint8_t)(nearest(x[j] * id) | (nearest(x[j + 16] * id) << 4));
+    }
+}
+
 // ---- K-quants (ggml-common.h block_q{4,5,6}_K; 256 weights per super-block, little-endian fields).  The decoders restate upstream's dequantize_row_q*_K with
 // its operations in its order, each rounded on its own (d1 = d * sc; m1 = dmin * m; y = d1 * q - m1 / y = d * sc * q): the values the device kernels
 // (kernels/kquant.hip) round to f16, and what the model loader decodes a file tensor of these types with.
@@ -579,6 +708,10 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float* src, void* dst, int
         switch (type) {
             case GGML_TYPE_Q8_0: quantize_row_q8_0(x, y, n_per_row); break;
             case GGML_TYPE_Q4_0: quantize_row_q4_0(x, y, n_per_row); break;
+            case GGML_TYPE_Q4_1:
+            case GGML_TYPE_Q5_0:
+            case GGML_TYPE_Q5_1: quantize_row_q4_1_q5(type, x, y, n_per_row); break;
+            case GGML_TYPE_IQ4_NL: quantize_row_iq4_nl(x, y, n_per_row); break;
             case GGML_TYPE_Q4_K: quantize_row_q45_K(x, y, n_per_row, false); break;
             case GGML_TYPE_Q5_K: quantize_row_q45_K(x, y, n_per_row, true); break;
             case GGML_TYPE_Q6_K: quantize_row_q6_K(x, y, n_per_row); break;
@@ -618,6 +751,10 @@ void ggml_dequantize_row(enum ggml_type type, const void* src, float* dst, int64
                 }
             }
             break;
+        case GGML_TYPE_Q4_1:
+        case GGML_TYPE_Q5_0:
+        case GGML_TYPE_Q5_1: dequantize_row_q4_1_q5(type, p, dst, n); break;
+        case GGML_TYPE_IQ4_NL: dequantize_row_iq4_nl(p, dst, n); break;
         case GGML_TYPE_Q4_K: dequantize_row_q45_K(p, dst, n, false); break;
         case GGML_TYPE_Q5_K: dequantize_row_q45_K(p, dst, n, true); break;
         case GGML_TYPE_Q6_K: dequantize_row_q6_K(p, dst, n); break;

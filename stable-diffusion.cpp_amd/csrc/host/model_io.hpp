@@ -23,11 +23,11 @@ namespace sdmi {
 
 // dtypes the safetensors format names that ggml has no element type for: decoded to f32 at load time (the reference widens them the
 // same way before its own convert step — F8 -> F16, F64 -> F32, I64 -> I32: src/model_io/safetensors_io.cpp:79-99, src/model_loader.cpp:81-153)
-// Q4_1 / Q5_0 / Q5_1: GGUF block quantisations the graph never computes in (the engine's parameter types are f32 / f16 / bf16 / q8_0 / q4_0); they are
+// Q4_1 / Q5_0 / Q5_1: GGUF block quantisations; unless the parameter has that very type (below) they are
 // decoded to f32 at load time and re-encoded in the parameter's type, like convert_tensor does for every source type (src/model_loader.cpp:155-205)
 // K-quants (Q2_K .. Q6_K: super-blocks of 256 weights with 4- / 6-bit sub-block scales — the q2_k / q3_k / q4_k FLUX and SD3.5 files docs/flux.md:36-38
 // points its users at) and IQ4_NL (32 weights, non-linear 4-bit code book) take the same route: decoded to f32 at load, re-encoded in the parameter's type —
-// except a q4_K / q5_K / q6_K tensor whose parameter has that very type (context wtype): its super-blocks are copied raw (engine.cpp, FileTensor::src_type).
+// except a q4_1 / q5_0 / q5_1 / iq4_nl / q4_K / q5_K / q6_K tensor whose parameter has that very type (context wtype): its blocks are copied raw (engine.cpp, FileTensor::src_type).
 enum class SrcKind { NATIVE, F64, I64, F8_E4M3, F8_E5M2, Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL };
 
 // ggml type id -> (kind, weights per block, bytes per block) of the block formats decoded at load time; false for every other type
@@ -197,47 +197,11 @@ inline void decode_src_kind(SrcKind kind, const uint8_t* raw, int64_t n, float* 
         case SrcKind::F8_E5M2:
             for (int64_t i = 0; i < n; ++i) dst[i] = f8_e5m2_to_f32(raw[i]);
             break;
-        // ggml block layouts (32 weights per block; byte j of qs holds element j in its low and element j + 16 in its high nibble):
-        //   q4_1 {f16 d, f16 m, u8 qs[16]}            x = q * d + m
-        //   q5_0 {f16 d, u8 qh[4], u8 qs[16]}         x = ((q | bit5 << 4) - 16) * d, bit5 of element j = bit j of the little-endian u32 qh
-        //   q5_1 {f16 d, f16 m, u8 qh[4], u8 qs[16]}  x = (q | bit5 << 4) * d + m
-        case SrcKind::Q4_1:
-        case SrcKind::Q5_0:
-        case SrcKind::Q5_1: {
-            const int bs = kind == SrcKind::Q4_1 ? 20 : (kind == SrcKind::Q5_0 ? 22 : 24);
-            for (int64_t b = 0; b < n / 32; ++b) {
-                const uint8_t* p = raw + b * bs;
-                ggml_fp16_t dh, mh = 0;
-                memcpy(&dh, p, 2);
-                p += 2;
-                if (kind != SrcKind::Q5_0) {
-                    memcpy(&mh, p, 2);
-                    p += 2;
-                }
-                const float d = ggml_fp16_to_fp32(dh), m = kind != SrcKind::Q5_0 ? ggml_fp16_to_fp32(mh) : 0.f;
-                uint32_t qh = 0;
-                if (kind != SrcKind::Q4_1) {
-                    memcpy(&qh, p, 4);
-                    p += 4;
-                }
-                float* y = dst + b * 32;
-                for (int j = 0; j < 16; ++j) {
-                    int x0 = p[j] & 0x0F, x1 = p[j] >> 4;
-                    if (kind != SrcKind::Q4_1) {
-                        x0 |= (int)((qh >> j) & 1u) << 4;
-                        x1 |= (int)((qh >> (j + 16)) & 1u) << 4;
-                    }
-                    if (kind == SrcKind::Q5_0) {
-                        y[j]      = (float)(x0 - 16) * d;
-                        y[j + 16] = (float)(x1 - 16) * d;
-                    } else {
-                        y[j]      = (float)x0 * d + m;
-                        y[j + 16] = (float)x1 * d + m;
-                    }
-                }
-            }
-            break;
-        }
+        //   q4_1 / q5_0 / q5_1 / iq4_nl (32 weights per block): the front-end's decoders (ggml.cpp), the one host restatement of these formats
+        case SrcKind::Q4_1: ggml_dequantize_row(GGML_TYPE_Q4_1, raw, dst, n); break;
+        case SrcKind::Q5_0: ggml_dequantize_row(GGML_TYPE_Q5_0, raw, dst, n); break;
+        case SrcKind::Q5_1: ggml_dequantize_row(GGML_TYPE_Q5_1, raw, dst, n); break;
+        case SrcKind::IQ4_NL: ggml_dequantize_row(GGML_TYPE_IQ4_NL, raw, dst, n); break;
         // ---- K-quants (ggml-common.h block_q{2,3,4,5,6}_K; QK_K = 256; all fields little-endian).  Values follow upstream's dequantize_row_q*_K.
         //   q2_K {u8 scales[16] (low nibble: scale, high nibble: min, per 16 weights); u8 qs[64] (2 bits per weight); f16 d; f16 dmin}
         //        x = d * sc * q - dmin * mn.  Weight order: per 128-weight half, bit pairs 0..3 of qs[0..31]: pair s covers weights 32 s .. 32 s + 31
@@ -295,22 +259,6 @@ inline void decode_src_kind(SrcKind kind, const uint8_t* raw, int64_t n, float* 
         case SrcKind::Q4_K: ggml_dequantize_row(GGML_TYPE_Q4_K, raw, dst, n); break;
         case SrcKind::Q5_K: ggml_dequantize_row(GGML_TYPE_Q5_K, raw, dst, n); break;
         case SrcKind::Q6_K: ggml_dequantize_row(GGML_TYPE_Q6_K, raw, dst, n); break;
-        //   iq4_nl {f16 d; u8 qs[16]}: x = d * kvalues[q], element j in the low nibble of byte j, element j + 16 in the high nibble
-        case SrcKind::IQ4_NL: {
-            static const int8_t kv[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
-            for (int64_t blk = 0; blk < n / 32; ++blk) {
-                const uint8_t* p = raw + blk * 18;
-                ggml_fp16_t dh;
-                memcpy(&dh, p, 2);
-                const float d = ggml_fp16_to_fp32(dh);
-                float* y = dst + blk * 32;
-                for (int j = 0; j < 16; ++j) {
-                    y[j]      = d * (float)kv[p[2 + j] & 0xF];
-                    y[j + 16] = d * (float)kv[p[2 + j] >> 4];
-                }
-            }
-            break;
-        }
         default: break;
     }
 }

@@ -384,6 +384,23 @@ void launch_kq_image(hipStream_t s, void* dst, const void* wraw, int wtype, int6
 enum KQRoute { KQ_GEMM_RB1 = 0, KQ_GEMM_RB2, KQ_GEMM_RB4, KQ_GEMM_REDUCE, KQ_IMAGE, KQ_ROUTE_COUNT };
 int64_t kq_route_launches(int route);
 
+// ---- bquant.hip: Linears over RAW q4_1 (wtype 3) / q5_0 (6) / q5_1 (7) / iq4_nl (20) blocks of 32 weights, any K % 32 == 0; every route multiplies by
+// w16 = f16(ggml's dequantised f32 value) ----
+bool bq_type(int wtype);
+// k_bq_gemm: 1 .. bq_gemm_max_rows(wtype) activation rows, the blocks decoded in registers into MFMA fragments (no image).  Operands, epilogues and split-K as
+// launch_kq_gemm.  wraw 16-byte aligned (the rows themselves are only 2 / 4 / 8-byte aligned).
+int bq_gemm_max_rows(int wtype);
+bool bq_gemm_supported(int wtype, int64_t rows, int64_t K, int64_t M);
+int bq_gemm_split_k(int64_t rows, int64_t K, int64_t M);
+void launch_bq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const void* a16, int64_t lda, int64_t rows, const void* wraw, int wtype, int64_t K, int64_t M,
+                    const Epilogue& ep, float* splitk_ws = nullptr, int splitk_S = 1, const float* x32 = nullptr, int64_t xs = 0, float pre_scale = 1.0f, bool pre_silu = false);
+// k_bq_image: raw blocks -> the f16 MFMA weight image (wswz_bytes(R, K), K padded to 64 with zeros); geglu_inner as launch_wswz_linear
+bool bq_image_supported(int wtype, int64_t K);
+void launch_bq_image(hipStream_t s, void* dst, const void* wraw, int wtype, int64_t K, int64_t R, int64_t geglu_inner = 0);
+// launches counted where the launchers choose (statistics lin_bq_*)
+enum BQRoute { BQ_GEMM_RB1 = 0, BQ_GEMM_RB2, BQ_GEMM_REDUCE, BQ_IMAGE, BQ_ROUTE_COUNT };
+int64_t bq_route_launches(int route);
+
 // ---- flash_attn.hip ---------------------------------------------------------------------------------
 // q [D,Lq,HN] (f32, strides in bytes), k [D,Lk,HN], v [DV,Lk,HN] (f16 or f32; v may be a transposed view,
 // any nb[0]) -> dst f32 written with strides
