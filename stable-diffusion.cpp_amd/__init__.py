@@ -429,7 +429,8 @@ _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned 
                         "fused_ip_attn flash_short_ip_launches "
                         "fused_patch_embed patch_embed_launches "
                         "lin_kq_gemm_rb1 lin_kq_gemm_rb2 lin_kq_gemm_rb4 lin_kq_gemm_reduce lin_kq_image kquant_linears "
-                        "lin_bq_gemm_rb1 lin_bq_gemm_rb2 lin_bq_gemm_reduce lin_bq_image bquant_linears").split()
+                        "lin_bq_gemm_rb1 lin_bq_gemm_rb2 lin_bq_gemm_reduce lin_bq_image bquant_linears "
+                        "flash_wide_launches").split()
 
 
 class BackendStats(C.Structure):

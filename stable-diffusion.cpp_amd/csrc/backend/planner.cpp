@@ -1750,7 +1750,9 @@ void plan_hoisted_kv(Builder& B, hipStream_t s) {
                 jf = c;
                 ++nread;
             }
-        if (nread != 1 || (gi.node(j5)->flags & GGML_TENSOR_FLAG_OUTPUT) || xop(gi.node(jf)) != GGML_OP_FLASH_ATTN_EXT || !planner_supports_op(gi.node(jf))) continue;
+        if (nread != 1 || (gi.node(j5)->flags & GGML_TENSOR_FLAG_OUTPUT) || xop(gi.node(jf)) != GGML_OP_FLASH_ATTN_EXT || !planner_supports_op(gi.node(jf)) ||
+            !flash_attn_supported(gi.node(jf)->src[0]->ne[0], gi.node(jf)->src[2]->ne[0]))  // (the wide kernel, d > 160, reads K / V where the graph puts them)
+            continue;
         const ggml_tensor* f = gi.node(jf);
         if (!((f->src[1] == gi.node(j5)) != (f->src[2] == gi.node(j5))) || f->src[0] == gi.node(j5)) continue;  // exactly one of K, V
         const ggml_tensor* r4 = gi.node(j1);
@@ -4750,6 +4752,8 @@ bool planner_supports_op(const ggml_tensor* n) {
             if (ggml_abi_op_param_f32(n, 1) != 0.0f || ggml_abi_op_param_f32(n, 2) != 0.0f) return false;
             if (q->nb[0] != 4 || k->nb[0] != ggml_abi_type_size(k->type) || v->nb[0] != ggml_abi_type_size(v->type)) return false;
             if (q->ne[3] != 1 || k->ne[2] != q->ne[2]) return false;
+            // 160 < d <= 512 (k_flash_wide): f16 d-contiguous K / V with 16-byte aligned rows only — f32 or strided K / V stay refused there
+            if (flash_attn_wide_supported(q->ne[0], v->ne[0])) return flash_attn_wide_operands_ok(view_of(q), view_of(k), view_of(v));
             return flash_attn_supported(q->ne[0], v->ne[0]);
         }
         default:
@@ -4766,6 +4770,7 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     o->flash_mslot_launches   = flash_attn_variant_launches(FLASH_VAR_MSLOT);
     o->flash_generic_launches = flash_attn_variant_launches(FLASH_VAR_GENERIC);
     o->flash_short_ip_launches = flash_attn_variant_launches(FLASH_VAR_SHORT_IP);
+    o->flash_wide_launches     = flash_attn_variant_launches(FLASH_VAR_WIDE);
     // ... and where the elementwise launchers choose theirs: the ew_* fields lie in the order of EwRoute
     static_assert(offsetof(ggml_backend_mi355x_stats, ew_tile_merge_v1) - offsetof(ggml_backend_mi355x_stats, ew_bin_same) == (EW_ROUTE_COUNT - 1) * sizeof(int64_t),
                   "ggml_backend_mi355x_stats: one ew_* field per EwRoute, in its order");

@@ -1,5 +1,6 @@
 // flash_attn.hip — fused scaled-dot-product attention forward for gfx950 (no mask, no GQA broadcast needed on
 // the UNet / VAE path): softmax(scale * Q K^T) V with online softmax, never materialising the [Lk, Lq] scores.
+// Head dims 8 .. 160 here; the FLASH_ATTN_EXT node at 192 .. 512 (the VAE mid-block) is dispatched to flash_wide.hip.
 // Serves both encodings the reference emits (ggml_ext_attention_ext, src/core/ggml_extend.hpp:1349-1485):
 //   * the FLASH_ATTN_EXT node (flash flag on; K/V arrive as f16), and
 //   * the manual MUL_MAT -> SCALE -> SOFT_MAX -> MUL_MAT chain (flag off; K/V f32), pattern-matched by the planner.
@@ -29,7 +30,6 @@
 namespace mi355x {
 
 constexpr int FA_KT  = 64;  // keys per tile
-constexpr float FA_THR = 8.0f;  // deferred-max threshold, log2 units
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 typedef float float2_t __attribute__((ext_vector_type(2)));
 constexpr int FA_VTS = 68;  // Vt row stride in halfs (136 B: conflict-free ds_read_b64 over 32 rows)
@@ -1201,6 +1201,11 @@ int64_t flash_attn_variant_launches(int variant) { return variant >= 0 && varian
 
 void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale) {
     KScope ks_(s, KF_FLASH, 4.0 * (double)q.ne[1] * (double)k.ne[1] * (double)q.ne[2] * (double)q.ne[0], 0.0);  // 4 * Lq * Lk * (H*N) * d
+    if (flash_attn_wide_supported(q.ne[0], v.ne[0])) {  // 160 < d <= 512 (flash_wide.hip): a plan of its own, the same operand and output forms
+        g_variant_launches[FLASH_VAR_WIDE]++;
+        launch_flash_wide(s, out, q, k, v, scale);
+        return;
+    }
     FAArgs g;
     g.qi = 0;
     g.q = (const char*)q.data;

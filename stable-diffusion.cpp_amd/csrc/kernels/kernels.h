@@ -406,6 +406,7 @@ int64_t bq_route_launches(int route);
 // any nb[0]) -> dst f32 written with strides
 // (dst_nb_d=4 implied) dst element (d, q, hn) at dst + q*dst_nb_q + hn*dst_nb_h
 bool flash_attn_supported(int64_t D, int64_t DV);
+constexpr float FA_THR = 8.0f;  // deferred-max threshold of the tile kernels (flash_attn.hip, flash_wide.hip), log2 units
 // output: f32 element (d, q, hn) at dst + q*dst_nb_q + (hn % H)*dst_nb_h + (hn / H)*dst_nb_n   (H = 0: flat head index),
 // and/or f16 operand image dst16[(n*Lq + q)*ld16 + h*D + d] (the packed [tok][C] input of the to_out projection)
 struct FlashOut {
@@ -421,7 +422,14 @@ bool gemm16_split_col_supported(int64_t rows, int64_t M, int64_t K);  // a Linea
 void gemm16_set_streamk(int v);    // option "streamk" (0; 1 = launches of two rounds or more, 2 = every candidate): Linears whose tile count leaves the last round of a one-workgroup-per-CU tile mostly empty run as one round of persistent workgroups over equal (tile, K-tile) ranges
 void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale);
 // which instantiation launch_flash_attn chose, counted per call (statistics flash_*_launches; the other FAST tile kernels are not counted)
-enum FlashVariant { FLASH_VAR_SHORT = 0, FLASH_VAR_QB2, FLASH_VAR_MSLOT, FLASH_VAR_GENERIC, FLASH_VAR_SHORT_IP, FLASH_VAR_COUNT };
+enum FlashVariant { FLASH_VAR_SHORT = 0, FLASH_VAR_QB2, FLASH_VAR_MSLOT, FLASH_VAR_GENERIC, FLASH_VAR_SHORT_IP, FLASH_VAR_WIDE, FLASH_VAR_COUNT };
+// flash_wide.hip — head dims beyond flash_attn_supported: 160 < D = DV <= 512, D % 64 == 0 (the KL-VAE mid-block: one head of d = 512).  Only the FLASH_ATTN_EXT node
+// asks this (supports_op and its planner case); the manual chain beyond d = 160 stays the GEMM composition (plan_manual_attention branches on flash_attn_supported).
+// Operands: Q f32 rows, d-contiguous, any row / head stride; K and V f16, d-contiguous, rows and heads 16-byte aligned, Lk rows within 2 GiB
+// (flash_attn_wide_operands_ok on the strides; launch_flash_attn aborts on anything else at these head dims).  launch_flash_attn dispatches to launch_flash_wide.
+bool flash_attn_wide_supported(int64_t D, int64_t DV);
+bool flash_attn_wide_operands_ok(const View4& q, const View4& k, const View4& v);  // types, strides and sizes (not the base addresses: unknown before allocation)
+void launch_flash_wide(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale);
 // IP-Adapter cross-attention in one launch (k_flash_short_ip): softmax(scale q k^T) v + ip_scale * softmax(scale q k_ip^T) v_ip into one output.  Text K / V as
 // k_flash_short takes them (64 < Lk <= 96), image K / V [D, Lk_ip, HN] with 1 <= Lk_ip <= 32, all f16, d-contiguous, 16-byte aligned rows; d <= 64, d % 8 == 0; Q f32
 // or an f16 image; exactly one of out.dst / out.dst16.  Anything else aborts: the planner asks flash_attn_ip_shape_ok first and runs other shapes as plain nodes.
