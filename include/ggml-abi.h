@@ -448,10 +448,12 @@ static inline int64_t ggml_abi_blck_size(enum ggml_type t) {
         case GGML_TYPE_Q8_1:
         case GGML_TYPE_IQ4_NL:
             return 32;
+        case GGML_TYPE_Q2_K:
+        case GGML_TYPE_Q3_K:
         case GGML_TYPE_Q4_K:
         case GGML_TYPE_Q5_K:
         case GGML_TYPE_Q6_K:
-            return 256; /* super-blocks; the other K types stay unsized: decoded when a file is read */
+            return 256; /* super-blocks */
         default:
             return 1;
     }
@@ -468,6 +470,8 @@ static inline size_t ggml_abi_type_size(enum ggml_type t) {
         case GGML_TYPE_IQ4_NL: return 18; /* half d; uint8 qs[16] (codes into a 16-entry table) */
         case GGML_TYPE_Q8_0: return 34; /* half d; int8 qs[32] */
         case GGML_TYPE_Q8_1: return 36;
+        case GGML_TYPE_Q2_K: return 84;  /* uint8 scales[16]; uint8 qs[64]; half d, dmin */
+        case GGML_TYPE_Q3_K: return 110; /* uint8 hmask[32]; uint8 qs[64]; uint8 scales[12]; half d */
         case GGML_TYPE_Q4_K: return 144; /* half d, dmin; uint8 scales[12]; uint8 qs[128] */
         case GGML_TYPE_Q5_K: return 176; /* half d, dmin; uint8 scales[12]; uint8 qh[32]; uint8 qs[128] */
         case GGML_TYPE_Q6_K: return 210; /* uint8 ql[128]; uint8 qh[64]; int8 scales[16]; half d */

@@ -184,13 +184,13 @@ struct ggml_backend_mi355x_stats {
     /* CLIP vision tower (option fuse_patch_embed) */
     int64_t fused_patch_embed;       /* CLIPVisionEmbeddings chains (REPEAT class, IM2COL .. CONT of the stride = kernel conv, CONCAT, ADD position) planned as ONE launch of k_patch_embed (per plan) */
     int64_t patch_embed_launches;    /* launch_patch_embed calls (per launch call) */
-    /* K-quant Linear weights (q4_K / q5_K / q6_K raw in HBM, kernels/kquant.hip); lin_kq_*: per launch call, in the order of KQRoute */
+    /* K-quant Linear weights (q2_K .. q6_K raw in HBM, kernels/kquant.hip); lin_kq_*: per launch call, in the order of KQRoute */
     int64_t lin_kq_gemm_rb1;         /* launch_kq_gemm: k_kq_gemm<KT, 1> (32-row tiles; 1 .. 4 rows read their f32 rows themselves) */
     int64_t lin_kq_gemm_rb2;         /* ... k_kq_gemm<KT, 2> */
     int64_t lin_kq_gemm_rb4;         /* ... k_kq_gemm<KT, 4> */
     int64_t lin_kq_gemm_reduce;      /* the slab reduce behind a split launch_kq_gemm */
     int64_t lin_kq_image;            /* launch_kq_image: the f16 weight image of a K-quant weight (cached once per weight, or just in time under option jit_qimages) */
-    int64_t kquant_linears;          /* Linears with a q4_K / q5_K / q6_K weight (per plan, whatever route they take) */
+    int64_t kquant_linears;          /* Linears with a q2_K .. q6_K weight (per plan, whatever route they take) */
     /* 32-weight block Linear weights (q4_1 / q5_0 / q5_1 / iq4_nl raw in HBM, kernels/bquant.hip); lin_bq_*: per launch call, in the order of BQRoute */
     int64_t lin_bq_gemm_rb1;         /* launch_bq_gemm: k_bq_gemm<BT, 1> (32-row tiles; 1 .. 4 rows read their f32 rows themselves) */
     int64_t lin_bq_gemm_rb2;         /* ... k_bq_gemm<BT, 2> */

@@ -78,6 +78,8 @@ enum sdm_type_t {
     SDM_TYPE_Q5_0 = 6,
     SDM_TYPE_Q5_1 = 7,
     SDM_TYPE_Q8_0 = 8,
+    SDM_TYPE_Q2_K = 10, /* the 2-bit-plane members of the super-block family below (84 / 110 bytes per 256 weights), on the same terms */
+    SDM_TYPE_Q3_K = 11,
     SDM_TYPE_Q4_K = 12, /* K-quant super-blocks (256 weights): Linears whose input width is a multiple of 256 take them, the others stay f32 (nn.hpp Linear, as for every block type); kept raw on the device */
     SDM_TYPE_Q5_K = 13,
     SDM_TYPE_Q6_K = 14,
@@ -219,7 +221,7 @@ SD_API bool sd_set_tensor_f32(sdm_ctx_t* ctx, const char* name, const float* src
 /* ---- checkpoint files, told apart by their first bytes:
  *   safetensors          F32 / F16 / BF16 native; F64 / I64 / F8_E4M3 / F8_E5M2 widened at load
  *   GGUF v2 / v3         F32 / F16 / BF16 / Q8_0 / Q4_0 native; Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_NL decoded at load —
- *                        except a tensor stored in its parameter's own type (wtype Q4_1 / Q5_0 / Q5_1 / IQ4_NL / Q4_K / Q5_K / Q6_K): its blocks are copied raw
+ *                        except a tensor stored in its parameter's own type (wtype Q4_1 / Q5_0 / Q5_1 / IQ4_NL / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K): its blocks are copied raw
  *                          type    block (little-endian)                       bytes / 32 weights   value
  *                          Q4_1    f16 d, f16 m, u8 qs[16]                     20                   q * d + m
  *                          Q5_0    f16 d, u8 qh[4], u8 qs[16]                  22                   (q - 16) * d

@@ -265,7 +265,10 @@ inline bool is_static_weight(const ggml_tensor* t) {
     return b != nullptr && b->usage == GGML_BACKEND_BUFFER_USAGE_WEIGHTS;
 }
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-// a q4_K / q5_K / q6_K Linear weight the K-quant kernels (kernels/kquant.hip) take: whole super-blocks per row, rows packed
+inline const char* kq_type_name(int t) {
+    return t == GGML_TYPE_Q2_K ? "q2_K" : t == GGML_TYPE_Q3_K ? "q3_K" : t == GGML_TYPE_Q4_K ? "q4_K" : t == GGML_TYPE_Q5_K ? "q5_K" : "q6_K";
+}
+// a q2_K .. q6_K Linear weight the K-quant kernels (kernels/kquant.hip) take: whole super-blocks per row, rows packed
 inline bool kq_weight_ok(const ggml_tensor* w) {
     return kq_type((int)w->type) && w->ne[0] >= 256 && w->ne[0] % 256 == 0 && w->ne[2] == 1 && w->ne[3] == 1 && w->nb[0] == ggml_abi_type_size(w->type) &&
            (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, w->ne[0]);
@@ -1299,7 +1302,7 @@ void plan_linear(Builder& B, int i, hipStream_t s, std::vector<int>& chain) {
     // the chain's output must not land on rows the kernel is still reading (the deferred SiLU's source may have been released by the allocator)
     const ggml_tensor* lastt   = gi.node(last);
     const bool src_safe        = xsrc == x || !overlaps(lastt->data, ggml_abi_nbytes(lastt), xsrc->data, ggml_abi_nbytes(xsrc));
-    // K-quant weights (q4_K / q5_K / q6_K) under 1 .. 4 rows: k_kq_gemm reads the f32 rows itself (deferred SiLU applied while they are staged), as k_qgemv does
+    // K-quant weights (q2_K .. q6_K) under 1 .. 4 rows: k_kq_gemm reads the f32 rows itself (deferred SiLU applied while they are staged), as k_qgemv does
     // (q4_1 / q5_0 / q5_1 / iq4_nl blocks: k_bq_gemm, kernels/bquant.hip, the same way on every route below)
     const bool kq = kq_type((int)w->type), bq = bq_type((int)w->type);
     if (kq) STAT(kquant_linears)++;
@@ -3086,7 +3089,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
         case GGML_OP_MUL_MAT: {
             if (kq_type((int)n->src[0]->type)) {  // no generic matmul over super-blocks (k_mul_mat_generic would read them as q4_0): fail the graph, loudly
                 fprintf(stderr, "[ggml-mi355x] node %d: MUL_MAT with a %s weight outside the Linear path (weight not in a WEIGHTS buffer, unaligned rows, or option mfma_gemm = 0)\n", i,
-                        n->src[0]->type == GGML_TYPE_Q4_K ? "q4_K" : n->src[0]->type == GGML_TYPE_Q5_K ? "q5_K" : "q6_K");
+                        kq_type_name((int)n->src[0]->type));
                 return false;
             }
             if (bq_type((int)n->src[0]->type)) {  // ... nor over q4_1 / q5_0 / q5_1 / iq4_nl blocks
@@ -4712,7 +4715,7 @@ bool planner_supports_op(const ggml_tensor* n) {
             if (!a || !b || n->type != GGML_TYPE_F32) return false;
             const bool at = a->type == GGML_TYPE_F32 || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_Q8_0 || a->type == GGML_TYPE_Q4_0;
             const bool bt = b->type == GGML_TYPE_F32 || b->type == GGML_TYPE_F16;
-            // q4_K / q5_K / q6_K: Linear weights only (the K-quant kernels; there is no generic matmul over super-blocks)
+            // q2_K .. q6_K: Linear weights only (the K-quant kernels; there is no generic matmul over super-blocks)
             // — and what linear_fast_ok asks that is known here; what is not (the weight's buffer usage, the addresses) makes the plan fail loudly (plan_single)
             // q4_1 / q5_0 / q5_1 / iq4_nl (kernels/bquant.hip): the same, with whole 32-weight blocks per row
             if (kq_type((int)a->type) || bq_type((int)a->type))

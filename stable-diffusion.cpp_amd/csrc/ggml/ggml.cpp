@@ -138,6 +138,8 @@ const char* ggml_type_name(enum ggml_type type) {
         case GGML_TYPE_Q5_1: return "q5_1";
         case GGML_TYPE_IQ4_NL: return "iq4_nl";
         case GGML_TYPE_Q8_0: return "q8_0";
+        case GGML_TYPE_Q2_K: return "q2_K";
+        case GGML_TYPE_Q3_K: return "q3_K";
         case GGML_TYPE_Q4_K: return "q4_K";
         case GGML_TYPE_Q5_K: return "q5_K";
         case GGML_TYPE_Q6_K: return "q6_K";
@@ -697,6 +699,117 @@ static void quantize_row_q6_K(const float* x, uint8_t* y, int64_t k) {
     }
 }
 
+// ---- q2_K / q3_K (block_q2_K / block_q3_K): 2-bit planes.  In half hf (128 weights), bit pair c of qs[32 hf + l] is weight 128 hf + 32 c + l, its sub-block
+// scale has index 8 hf + 2 c + l / 16 = weight / 16.  Decoders as above: upstream's operations in its order, each rounded on its own.
+//   q2_K {u8 scales[16] (low nibble: scale, high nibble: min); u8 qs[64]; f16 d; f16 dmin}      dl = d * sc; ml = dmin * mn; y = dl * q - ml
+//   q3_K {u8 hmask[32] (bit 4 hf + c of hmask[l]: third bit of that weight); u8 qs[64]; u8 scales[12] (16 six-bit scales: low 4 bits as nibbles of bytes
+//        0..7, high 2 bits in bytes 8..11); f16 d}                                                dl = d * (sc - 32); y = dl * (q2 - (hbit ? 0 : 4))
+static inline int q3k_scale(const uint8_t* s12, int j) {
+    const int lo = j < 8 ? (s12[j] & 0xF) : (s12[j - 8] >> 4), hi = (s12[8 + (j & 3)] >> (2 * (j >> 2))) & 3;
+    return (lo | (hi << 4)) - 32;
+}
+static void dequantize_row_q23_K(const uint8_t* raw, float* dst, int64_t n, bool three) {
+    const int bs = three ? 110 : 84;
+    for (int64_t blk = 0; blk < n / 256; ++blk) {
+        const uint8_t* p  = raw + blk * bs;
+        const uint8_t* hm = p;
+        const uint8_t* q  = p + (three ? 32 : 16);
+        ggml_fp16_t dh, mh;
+        memcpy(&dh, p + (three ? 108 : 80), 2);
+        memcpy(&mh, p + 82, 2);
+        const float d = ggml_fp16_to_fp32(dh), dmin = three ? 0.f : ggml_fp16_to_fp32(mh);
+        float* y = dst + blk * 256;
+        for (int j = 0; j < 16; ++j) {
+            const int hf = j >> 3, c = (j >> 1) & 3, l0 = 16 * (j & 1);
+            if (three) {
+                const float dl = d * (float)q3k_scale(p + 96, j);
+                for (int l = l0; l < l0 + 16; ++l) *y++ = dl * (float)((int)((q[32 * hf + l] >> (2 * c)) & 3) - (((hm[l] >> (4 * hf + c)) & 1) ? 0 : 4));
+            } else {
+                const float dl = d * (float)(p[j] & 0xF), ml = dmin * (float)(p[j] >> 4);
+                for (int l = l0; l < l0 + 16; ++l) {
+                    const float pv = dl * (float)((q[32 * hf + l] >> (2 * c)) & 3);  // (a statement of its own: never contracted with the subtraction)
+                    *y++ = pv - ml;
+                }
+            }
+        }
+    }
+}
+// PLAIN encoders as above — NOT ggml's search-based make_qkx2_quants / make_q3_quants.  q2_K: per 16-weight sub-block min / max, 4-bit scales and mins against the
+// super-block maxima, rounded UP so that every value stays inside the code range 0 .. 3.  q3_K: per sub-block the absolute maximum goes to code -4 (the
+// scale takes the opposite sign of that weight: step = amax / 4, the other side clips at 3 steps), 6-bit scales against the super-block maximum, rounded up.
+// Quants are rounded to nearest.
+static void quantize_row_q2_K(const float* x, uint8_t* y, int64_t k) {
+    for (int64_t blk = 0; blk < k / 256; ++blk, x += 256) {
+        uint8_t* p = y + blk * 84;
+        memset(p, 0, 84);
+        float mnv[16], mxv[16], maxmn = 0.f, maxneed = 0.f, off[16];
+        for (int j = 0; j < 16; ++j) {
+            float lo = 0.f, hi = 0.f;  // the code range starts at -dmin * m <= 0
+            for (int l = 0; l < 16; ++l) {
+                lo = std::min(lo, x[16 * j + l]);
+                hi = std::max(hi, x[16 * j + l]);
+            }
+            mnv[j] = -lo;
+            mxv[j] = hi;
+            maxmn  = std::max(maxmn, mnv[j]);
+        }
+        const ggml_fp16_t mh = ggml_fp32_to_fp16(maxmn / 15.0f);
+        const float dmin     = ggml_fp16_to_fp32(mh);
+        int mn[16];
+        for (int j = 0; j < 16; ++j) {
+            mn[j]   = dmin > 0.f ? std::min(15, (int)ceilf(mnv[j] / dmin)) : 0;
+            off[j]  = dmin * (float)mn[j];
+            maxneed = std::max(maxneed, (mxv[j] + off[j]) / 3.0f);
+        }
+        const ggml_fp16_t dh = ggml_fp32_to_fp16(maxneed / 15.0f);
+        const float d        = ggml_fp16_to_fp32(dh);
+        memcpy(p + 80, &dh, 2);
+        memcpy(p + 82, &mh, 2);
+        for (int j = 0; j < 16; ++j) {
+            const int sc   = d > 0.f ? std::min(15, (int)ceilf((mxv[j] + off[j]) / 3.0f / d)) : 0;
+            p[j]           = (uint8_t)(sc | (mn[j] << 4));
+            const float st = d * (float)sc, inv = st > 0.f ? 1.0f / st : 0.f;
+            const int hf = j >> 3, c = (j >> 1) & 3, l0 = 16 * (j & 1);
+            for (int l = 0; l < 16; ++l) {
+                const int v = std::max(0, std::min(3, (int)lrintf((x[16 * j + l] + off[j]) * inv)));
+                p[16 + 32 * hf + l0 + l] |= (uint8_t)(v << (2 * c));
+            }
+        }
+    }
+}
+static void quantize_row_q3_K(const float* x, uint8_t* y, int64_t k) {
+    for (int64_t blk = 0; blk < k / 256; ++blk, x += 256) {
+        uint8_t* p = y + blk * 110;
+        memset(p, 0, 110);
+        float need[16], sgn[16], maxneed = 0.f;
+        for (int j = 0; j < 16; ++j) {
+            float amax = 0.f, at = 0.f;
+            for (int l = 0; l < 16; ++l)
+                if (fabsf(x[16 * j + l]) > amax) amax = fabsf(x[16 * j + l]), at = x[16 * j + l];
+            need[j] = amax / 4.0f;
+            sgn[j]  = at > 0.f ? -1.f : 1.f;
+            maxneed = std::max(maxneed, need[j]);
+        }
+        ggml_fp16_t dh = ggml_fp32_to_fp16(maxneed / 31.0f);
+        if (ggml_fp16_to_fp32(dh) * 31.0f < maxneed && dh < 0x7BFF) ++dh;  // d rounded UP: code -4 reaches the absolute maximum
+        const float d = ggml_fp16_to_fp32(dh);
+        memcpy(p + 108, &dh, 2);
+        uint8_t* s12 = p + 96;
+        for (int j = 0; j < 16; ++j) {
+            const int sc   = (d > 0.f ? std::min(31, (int)ceilf(need[j] / d)) : 0) * (int)sgn[j], s6 = sc + 32;
+            s12[j & 7] |= (uint8_t)((s6 & 0xF) << (j < 8 ? 0 : 4));
+            s12[8 + (j & 3)] |= (uint8_t)((s6 >> 4) << (2 * (j >> 2)));
+            const float st = d * (float)sc, inv = st != 0.f ? 1.0f / st : 0.f;
+            const int hf = j >> 3, c = (j >> 1) & 3, l0 = 16 * (j & 1);
+            for (int l = 0; l < 16; ++l) {
+                const int v = std::max(-4, std::min(3, (int)lrintf(x[16 * j + l] * inv))) + 4;
+                p[32 + 32 * hf + l0 + l] |= (uint8_t)((v & 3) << (2 * c));
+                p[l0 + l] |= (uint8_t)((v >> 2) << (4 * hf + c));
+            }
+        }
+    }
+}
+
 size_t ggml_quantize_chunk(enum ggml_type type, const float* src, void* dst, int64_t start, int64_t nrows, int64_t n_per_row, const float*) {
     GGML_ASSERT(start % n_per_row == 0);
     const size_t row_size = ggml_row_size(type, n_per_row);
@@ -712,6 +825,8 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float* src, void* dst, int
             case GGML_TYPE_Q5_0:
             case GGML_TYPE_Q5_1: quantize_row_q4_1_q5(type, x, y, n_per_row); break;
             case GGML_TYPE_IQ4_NL: quantize_row_iq4_nl(x, y, n_per_row); break;
+            case GGML_TYPE_Q2_K: quantize_row_q2_K(x, y, n_per_row); break;
+            case GGML_TYPE_Q3_K: quantize_row_q3_K(x, y, n_per_row); break;
             case GGML_TYPE_Q4_K: quantize_row_q45_K(x, y, n_per_row, false); break;
             case GGML_TYPE_Q5_K: quantize_row_q45_K(x, y, n_per_row, true); break;
             case GGML_TYPE_Q6_K: quantize_row_q6_K(x, y, n_per_row); break;
@@ -755,6 +870,8 @@ void ggml_dequantize_row(enum ggml_type type, const void* src, float* dst, int64
         case GGML_TYPE_Q5_0:
         case GGML_TYPE_Q5_1: dequantize_row_q4_1_q5(type, p, dst, n); break;
         case GGML_TYPE_IQ4_NL: dequantize_row_iq4_nl(p, dst, n); break;
+        case GGML_TYPE_Q2_K: dequantize_row_q23_K(p, dst, n, false); break;
+        case GGML_TYPE_Q3_K: dequantize_row_q23_K(p, dst, n, true); break;
         case GGML_TYPE_Q4_K: dequantize_row_q45_K(p, dst, n, false); break;
         case GGML_TYPE_Q5_K: dequantize_row_q45_K(p, dst, n, true); break;
         case GGML_TYPE_Q6_K: dequantize_row_q6_K(p, dst, n); break;

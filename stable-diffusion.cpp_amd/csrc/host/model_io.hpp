@@ -27,7 +27,7 @@ namespace sdmi {
 // decoded to f32 at load time and re-encoded in the parameter's type, like convert_tensor does for every source type (src/model_loader.cpp:155-205)
 // K-quants (Q2_K .. Q6_K: super-blocks of 256 weights with 4- / 6-bit sub-block scales — the q2_k / q3_k / q4_k FLUX and SD3.5 files docs/flux.md:36-38
 // points its users at) and IQ4_NL (32 weights, non-linear 4-bit code book) take the same route: decoded to f32 at load, re-encoded in the parameter's type —
-// except a q4_1 / q5_0 / q5_1 / iq4_nl / q4_K / q5_K / q6_K tensor whose parameter has that very type (context wtype): its blocks are copied raw (engine.cpp, FileTensor::src_type).
+// except a q4_1 / q5_0 / q5_1 / iq4_nl / q2_K .. q6_K tensor whose parameter has that very type (context wtype): its blocks are copied raw (engine.cpp, FileTensor::src_type).
 enum class SrcKind { NATIVE, F64, I64, F8_E4M3, F8_E5M2, Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL };
 
 // ggml type id -> (kind, weights per block, bytes per block) of the block formats decoded at load time; false for every other type
@@ -202,60 +202,9 @@ inline void decode_src_kind(SrcKind kind, const uint8_t* raw, int64_t n, float* 
         case SrcKind::Q5_0: ggml_dequantize_row(GGML_TYPE_Q5_0, raw, dst, n); break;
         case SrcKind::Q5_1: ggml_dequantize_row(GGML_TYPE_Q5_1, raw, dst, n); break;
         case SrcKind::IQ4_NL: ggml_dequantize_row(GGML_TYPE_IQ4_NL, raw, dst, n); break;
-        // ---- K-quants (ggml-common.h block_q{2,3,4,5,6}_K; QK_K = 256; all fields little-endian).  Values follow upstream's dequantize_row_q*_K.
-        //   q2_K {u8 scales[16] (low nibble: scale, high nibble: min, per 16 weights); u8 qs[64] (2 bits per weight); f16 d; f16 dmin}
-        //        x = d * sc * q - dmin * mn.  Weight order: per 128-weight half, bit pairs 0..3 of qs[0..31]: pair s covers weights 32 s .. 32 s + 31
-        case SrcKind::Q2_K:
-            for (int64_t blk = 0; blk < n / 256; ++blk) {
-                const uint8_t* p  = raw + blk * 84;
-                const uint8_t* sc = p;
-                const uint8_t* q  = p + 16;
-                ggml_fp16_t dh, mh;
-                memcpy(&dh, p + 80, 2);
-                memcpy(&mh, p + 82, 2);
-                const float d = ggml_fp16_to_fp32(dh), dmin = ggml_fp16_to_fp32(mh);
-                float* y = dst + blk * 256;
-                int is   = 0;
-                for (int half = 0; half < 2; ++half, q += 32)
-                    for (int shift = 0; shift < 8; shift += 2)
-                        for (int part = 0; part < 2; ++part, ++is) {
-                            const float dl = d * (float)(sc[is] & 0xF), ml = dmin * (float)(sc[is] >> 4);
-                            for (int l = 0; l < 16; ++l) *y++ = dl * (float)((q[l + 16 * part] >> shift) & 3) - ml;
-                        }
-            }
-            break;
-        //   q3_K {u8 hmask[32] (bit b of hmask[l]: high bit of weight 32 b + l); u8 qs[64] (low 2 bits, order as q2_K); u8 scales[12] (16 six-bit scales:
-        //        low 4 bits in bytes 0..7 (nibbles), high 2 bits in bytes 8..11); f16 d}     x = d * (scale - 32) * (q2 - (hbit ? 0 : 4))
-        case SrcKind::Q3_K:
-            for (int64_t blk = 0; blk < n / 256; ++blk) {
-                const uint8_t* p  = raw + blk * 110;
-                const uint8_t* hm = p;
-                const uint8_t* q  = p + 32;
-                const uint8_t* s8 = p + 96;
-                ggml_fp16_t dh;
-                memcpy(&dh, p + 108, 2);
-                const float d = ggml_fp16_to_fp32(dh);
-                int scales[16];
-                for (int j = 0; j < 16; ++j) {
-                    const int lo = j < 8 ? (s8[j] & 0xF) : (s8[j - 8] >> 4);
-                    const int hi = (s8[8 + (j & 3)] >> (2 * (j >> 2))) & 3;
-                    scales[j]    = (lo | (hi << 4)) - 32;
-                }
-                float* y  = dst + blk * 256;
-                int is    = 0;
-                uint8_t m = 1;
-                for (int half = 0; half < 2; ++half, q += 32)
-                    for (int shift = 0; shift < 8; shift += 2, m = (uint8_t)(m << 1))
-                        for (int part = 0; part < 2; ++part, ++is) {
-                            const float dl = d * (float)scales[is];
-                            for (int l = 0; l < 16; ++l) {
-                                const int k = l + 16 * part;
-                                *y++        = dl * (float)((int)((q[k] >> shift) & 3) - ((hm[k] & m) ? 0 : 4));
-                            }
-                        }
-            }
-            break;
-        //   q4_K / q5_K / q6_K: the front-end's decoders (ggml.cpp), the one host restatement of these formats
+        //   K-quants (256 weights per super-block): likewise
+        case SrcKind::Q2_K: ggml_dequantize_row(GGML_TYPE_Q2_K, raw, dst, n); break;
+        case SrcKind::Q3_K: ggml_dequantize_row(GGML_TYPE_Q3_K, raw, dst, n); break;
         case SrcKind::Q4_K: ggml_dequantize_row(GGML_TYPE_Q4_K, raw, dst, n); break;
         case SrcKind::Q5_K: ggml_dequantize_row(GGML_TYPE_Q5_K, raw, dst, n); break;
         case SrcKind::Q6_K: ggml_dequantize_row(GGML_TYPE_Q6_K, raw, dst, n); break;

@@ -368,11 +368,12 @@ int qgemm16_rb();
 // dst[i] = sum_s ws[s * n + i] + bias[i % C] + residual[i] (gemm16.hip's k_splitk_reduce on a row-major [rows][C] output)
 void splitk_reduce_rows(hipStream_t s, float* dst, const float* ws, int S, int64_t n, const float* bias, int64_t C, const float* residual);
 
-// ---- kquant.hip: Linears over RAW q4_K (wtype 12) / q5_K (13) / q6_K (14) super-blocks; every route multiplies by w16 = f16(ggml's dequantised f32 value) ----
+// ---- kquant.hip: Linears over RAW q2_K (wtype 10) / q3_K (11) / q4_K (12) / q5_K (13) / q6_K (14) super-blocks; every route multiplies by w16 = f16(ggml's dequantised f32 value) ----
 bool kq_type(int wtype);
 // k_kq_gemm: 1 .. qgemm16_max_rows activation rows, the super-blocks decoded in registers into MFMA fragments (no image).  Exactly one of a16 (f16 operand image
 // [rows][lda]) and x32 (f32 rows, stride xs floats, staged as f16(silu?(x) * pre_scale): the deferred SiLU / ggml_ext_linear scale of launch_qgemv) is given.
-// Epilogues as launch_qgemm16; split-K (S slices, workspace of S * rows * M floats) only for plain outputs.  wraw 16-byte aligned for q4_K / q5_K.
+// Epilogues as launch_qgemm16; split-K (S slices, workspace of S * rows * M floats) only for plain outputs.  wraw 16-byte aligned for q4_K / q5_K (the rows of the other types are 2- / 4-byte aligned).
+// Row range: qgemm16_max_rows, half of it for q3_K and q6_K (profiles/kquant_probe.txt, profiles/kquant_low_probe.txt).
 bool kq_gemm_supported(int wtype, int64_t rows, int64_t K, int64_t M);
 int kq_gemm_split_k(int64_t rows, int64_t K, int64_t M);
 void launch_kq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const void* a16, int64_t lda, int64_t rows, const void* wraw, int wtype, int64_t K, int64_t M,

@@ -1,8 +1,9 @@
-// kquant.hip — Linear layers whose weights are K-quant super-blocks (q4_K / q5_K / q6_K: 256 weights with packed 6-bit sub-block scales, the types the
-// Q4_K_S / Q4_K_M / Q5_K_S / Q6_K GGUF files of FLUX, SD3.5 and SDXL store), kept RAW in HBM (0.5625 / 0.6875 / 0.82 B per weight).
+// kquant.hip — Linear layers whose weights are K-quant super-blocks (q2_K .. q6_K: 256 weights with packed 4- / 6-bit sub-block scales, the types the
+// Q2_K / Q3_K / Q4_K_S / Q4_K_M / Q5_K_S / Q6_K GGUF files of FLUX, SD3.5 and SDXL store), kept RAW in HBM (0.33 / 0.43 / 0.5625 / 0.6875 / 0.82 B per weight).
 //
-// ONE weight value on every route: w16 = f16(y), y = the f32 value ggml's dequantize_row_q{4,5,6}_K produces with its operations in ggml's order, unfused:
+// ONE weight value on every route: w16 = f16(y), y = the f32 value ggml's dequantize_row_q{2..6}_K produces with its operations in ggml's order, unfused:
 //   q4_K / q5_K   d1 = d * sc;  m1 = dmin * m;  y = d1 * q - m1          q6_K   y = (d * sc) * q
+//   q2_K          dl = d * (s & 15);  ml = dmin * (s >> 4);  y = dl * q - ml          q3_K   dl = d * (sc - 32);  y = dl * (q2 - (hbit ? 0 : 4))
 // (kq_w8 / kq_w8s below: separately rounded operations under fp contract(off), never an FMA).  The few-row kernel and the image kernel share these decoders, so a Linear differs between its
 // routes by f32 summation order only.
 //
@@ -14,14 +15,25 @@
 //                                      step), their high nibbles weights 64 g + 32 + 8 r + i (the next step); q5_K adds bit 2 g / 2 g + 1 of qh[8 r + i]
 //                         q6_K         half hf (128 weights), t: ql[64 hf + 8 r ..], ql[64 hf + 32 + 8 r ..], qh[32 hf + 8 r ..] give the four steps c = 0 .. 3,
 //                                      weights 128 hf + 32 c + 8 r + i
+//                         q2_K / q3_K  2-bit planes in q6_K's weight order: half hf, t: the 8 bytes qs[32 hf + 8 r ..] are read ONCE and their four bit pairs
+//                                      c = 0 .. 3 are the four steps, weights 128 hf + 32 c + 8 r + i; q3_K adds bit 4 hf + c of hmask[8 r + i], 8 bytes read once
+//                                      per segment and run for both halves, and unpacks its six-bit scales from 12 bytes held as three dwords.  The step's
+//                                      sub-block scale is 8 hf + 2 c + t: each of the 16 is needed at exactly one (hf, t, c), so it is unpacked where it is used
+//                                      (4 x (dl, ml) live, not 16) at no extra work.
 //                       and the A fragment of each step is read from LDS at the same permuted k offset: no lane shuffles.
 //                       q6_K rows are only 2-byte aligned (210 K / 256 bytes): the fetch takes the 14 ALIGNED 16-byte granules that cover the piece (they share
 //                       their first and last valid byte's granule with it, so they never touch a page the tensor does not) and the LDS reads re-align with v_alignbit.
+//                       q2_K rows are 4-byte aligned (84 K / 256 bytes), q3_K rows 2-byte aligned (110 K / 256): the same rule, only granules that hold a valid
+//                       byte: always 6 for q2_K (phase + 84 > 80), 7 for q3_K at phase 0 / 2 and 8 from phase 4 on.  q2_K fields are read as dwords, q3_K's
+//                       through v_alignbit.  Strip stride per column: not the natural 96 / 128 bytes (24 / 32 dwords: the 32 columns of a wave would start on 8 / 2
+//                       of the 64 banks) but 104 / 136 bytes = 13 / 17 x 8: 26 / 34 dwords, 2 x odd, so the 32 columns start on 32 different even banks (the
+//                       stash is two 8-byte LDS stores per granule).  LDS: strips 4 x (32 x 104 + 16) = 13376 B / 4 x (32 x 136 + 16) = 17472 B, plus the A
+//                       tile of 16.5 KiB per 32 rows: 47168 / 51264 B at 64-row tiles.
 //                       Tile: 32 RB rows x 128 columns (4 waves x 32), next segment's global loads in flight during the MFMAs; split-K over gridDim.z into f32 slabs.
 //                       A = the f16 operand image, or for 1 .. 4 rows the f32 rows themselves (SiLU and pre_scale applied while they are staged).
 //   k_kq_image<KT>      raw super-blocks -> the f16 fragment-order image [col/32][K/16][64 lanes][8 halfs] of k_gemm16 (plain row order and both GEGLU orders of
 //                       k_wswz_linear): a workgroup owns 32 image rows x 256 k, loads the 32 super-blocks coalesced into LDS, wave w decodes ITS group g = w
-//                       (q4_K / q5_K: two sub-block scales per lane) / (half, t) = (w / 2, w % 2) (q6_K: four scales) and writes four whole 1 KiB fragments.
+//                       (q4_K / q5_K: two sub-block scales per lane) / (half, t) = (w / 2, w % 2) (q6_K, q2_K, q3_K: four scales) and writes four whole 1 KiB fragments.
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -36,18 +48,50 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 template <int KT>
 struct KQ;
+// BS: bytes per super-block; NGC: aligned 16-byte granules that cover one at its worst phase; CP: bytes between the columns of an LDS strip; PH: the rows
+// are not 16-byte aligned (the fetch starts at the granule that holds the super-block's first byte, the LDS reads add its phase)
+template <>
+struct KQ<2> {
+    static constexpr int BS = 84, NGC = 6, CP = 104, QS = 16, QH = 0;  // 4-byte phases: 12 + 84 = 96; 13 x 8 bytes (see the header)
+    static constexpr bool PH = true;
+};
+template <>
+struct KQ<3> {
+    static constexpr int BS = 110, NGC = 8, CP = 136, QS = 32, QH = 0;  // 2-byte phases: 7 granules at phase 0 / 2, else 8 (14 + 110 = 124); 17 x 8 bytes
+    static constexpr bool PH = true;
+};
 template <>
 struct KQ<4> {
-    static constexpr int BS = 144, NGC = 9, QS = 16, QH = 0;
+    static constexpr int BS = 144, NGC = 9, CP = 144, QS = 16, QH = 0;
+    static constexpr bool PH = false;
 };
 template <>
 struct KQ<5> {
-    static constexpr int BS = 176, NGC = 11, QS = 48, QH = 16;
+    static constexpr int BS = 176, NGC = 11, CP = 176, QS = 48, QH = 16;
+    static constexpr bool PH = false;
 };
 template <>
 struct KQ<6> {
-    static constexpr int BS = 210, NGC = 14, QS = 0, QH = 128;  // NGC: aligned granules covering 210 bytes at any even phase (14 + 210 = 224)
+    static constexpr int BS = 210, NGC = 14, CP = 224, QS = 0, QH = 128;  // NGC: aligned granules covering 210 bytes at any even phase (14 + 210 = 224)
+    static constexpr bool PH = true;
 };
+// the granule gr of a super-block at phase ph holds one of its bytes (q3_K alone has a granule that some phases do not need)
+template <int KT>
+__device__ __forceinline__ bool kq_granule_valid(int gr, uint32_t ph) {
+    return KT != 3 || gr * 16 < (int)ph + KQ<KT>::BS;
+}
+// a fetched granule into its place in a strip: CP is a multiple of 16 for q4_K .. q6_K, of 8 only for q2_K / q3_K (two 8-byte stores)
+template <int KT>
+__device__ __forceinline__ void kq_stash(char* strip, int idx, const u32x4_t& v) {
+    if constexpr (KQ<KT>::CP == KQ<KT>::NGC * 16) {
+        *(u32x4_t*)(strip + idx * 16) = v;
+    } else {
+        const int col = idx / KQ<KT>::NGC, gr = idx - col * KQ<KT>::NGC;
+        uint2* q = (uint2*)(strip + col * KQ<KT>::CP + gr * 16);
+        q[0]     = make_uint2(v[0], v[1]);
+        q[1]     = make_uint2(v[2], v[3]);
+    }
+}
 
 // 8 bytes at byte offset off of an LDS strip: 8-byte aligned (q4_K / q5_K fields), or 2-byte aligned (q6_K) through three dwords and v_alignbit
 template <bool ALIGNED>
@@ -77,13 +121,14 @@ __device__ __forceinline__ half8_t kq_w8(uint32_t a, uint32_t b, float d1, float
     }
     return o;
 }
-// q6_K: eight 6-bit values -> f16(ds * (v - 32)), ds = d * sc already rounded
+// q6_K: eight 6-bit values -> f16(ds * (v - 32)), ds = d * sc already rounded; q3_K: eight 3-bit values, BIAS 4
+template <int BIAS = 32>
 __device__ __forceinline__ half8_t kq_w8s(uint32_t a, uint32_t b, float ds) {
 #pragma clang fp contract(off)  // plain operators under this pragma (the rounding intrinsics of the HIP headers are inlined WITH their contract flag: v_fma_mix)
     half8_t o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float qa = (float)((a >> (8 * j)) & 0xFFu) - 32.0f, qb = (float)((b >> (8 * j)) & 0xFFu) - 32.0f;
+        const float qa = (float)((a >> (8 * j)) & 0xFFu) - (float)BIAS, qb = (float)((b >> (8 * j)) & 0xFFu) - (float)BIAS;
         o[j]     = (_Float16)(ds * qa);
         o[4 + j] = (_Float16)(ds * qb);
     }
@@ -153,6 +198,73 @@ __device__ __forceinline__ float kq_ds6(const char* strip, uint32_t off, int idx
     return __fmul_rn(d, (float)(int)*(const int8_t*)(strip + off + 192 + idx));
 }
 
+// ---- q2_K {u8 scales[16]; u8 qs[64]; f16 d; f16 dmin} at any 4-byte phase, q3_K {u8 hmask[32]; u8 qs[64]; u8 scales[12]; f16 d} at any 2-byte phase
+// the packed sub-block scales of the super-block at strip + off as aligned dwords (q2_K: 16 bytes, q3_K: 12), d and dmin
+struct KQHead23 {
+    float d, dmin;
+    uint32_t s[4];
+};
+template <int KT>
+__device__ __forceinline__ KQHead23 kq_head23(const char* strip, uint32_t off) {
+    KQHead23 h;
+    if (KT == 2) {
+        const uint32_t* b = (const uint32_t*)(strip + off);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) h.s[i] = b[i];
+        const uint32_t dd = b[20];
+        h.d    = (float)__builtin_bit_cast(_Float16, (uint16_t)(dd & 0xFFFFu));
+        h.dmin = (float)__builtin_bit_cast(_Float16, (uint16_t)(dd >> 16));
+    } else {
+        const uint32_t* b = (const uint32_t*)(strip + ((off + 96) & ~3u));
+        const uint32_t sh = (off & 2u) * 8u, r0 = b[0], r1 = b[1], r2 = b[2], r3 = b[3];
+        h.s[0] = __builtin_amdgcn_alignbit(r1, r0, sh);
+        h.s[1] = __builtin_amdgcn_alignbit(r2, r1, sh);
+        h.s[2] = __builtin_amdgcn_alignbit(r3, r2, sh);
+        h.s[3] = 0;
+        h.d    = (float)*(const _Float16*)(strip + off + 108);
+        h.dmin = 0.f;
+    }
+    return h;
+}
+// sub-block j (16 weights): q2_K dl = d * (scales[j] & 0xF), ml = dmin * (scales[j] >> 4); q3_K dl = d * (six-bit scale j - 32), its low four bits the low
+// (j < 8) or high nibble of byte j & 7, its high two bits at bit 2 (j >> 2) of byte 8 + (j & 3)
+template <int KT>
+__device__ __forceinline__ void kq_scale23(const KQHead23& h, int j, float& dl, float& ml) {
+    if (KT == 2) {
+        // (selects, not h.s[j >> 2]: in the image kernel j depends on the wave, and an indexed private array is moved to LDS)
+        const uint32_t sw = (j & 8) ? ((j & 4) ? h.s[3] : h.s[2]) : ((j & 4) ? h.s[1] : h.s[0]);
+        const uint32_t sb = (sw >> (8 * (j & 3))) & 0xFFu;
+        dl = __fmul_rn(h.d, (float)(sb & 0xFu));
+        ml = __fmul_rn(h.dmin, (float)(sb >> 4));
+    } else {
+        const uint32_t lo = (((j & 4) ? h.s[1] : h.s[0]) >> (8 * (j & 3) + (j < 8 ? 0 : 4))) & 0xFu, hi = (h.s[2] >> (8 * (j & 3) + 2 * (j >> 2))) & 3u;
+        dl = __fmul_rn(h.d, (float)((int)(lo | (hi << 4)) - 32));
+        ml = 0.f;
+    }
+}
+// half hf, run r = 2 t + kg of the super-block at strip + off: the 8 bytes qs[32 hf + 8 r ..] hold four MFMA steps as their four bit pairs, o[c] = weights
+// 128 hf + 32 c + 8 r + i with sub-block scale 8 hf + 2 c + t.  q3_K: ha, hb = hmask[8 r .. 8 r + 7] (the same bytes for both halves), third bit = bit 4 hf + c
+template <int KT>
+__device__ __forceinline__ void kq_dec23(const char* strip, uint32_t off, const KQHead23& h, int hf, int t, int r, uint32_t ha, uint32_t hb, half8_t (&o)[4]) {
+    const uint32_t m2 = 0x03030303u, m1 = 0x01010101u;
+    uint32_t qa, qb;
+    if (KT == 2) {  // 4-byte aligned: two dwords
+        const uint32_t* q = (const uint32_t*)(strip + off + KQ<2>::QS + 32 * hf + 8 * r);
+        qa = q[0];
+        qb = q[1];
+    } else {
+        kq_ld8<false>(strip, off + KQ<3>::QS + 32 * hf + 8 * r, qa, qb);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float dl, ml;
+        kq_scale23<KT>(h, 8 * hf + 2 * c + t, dl, ml);
+        const uint32_t va = (qa >> (2 * c)) & m2, vb = (qb >> (2 * c)) & m2;
+        if (KT == 2) o[c] = kq_w8(va, vb, dl, ml);
+        else o[c] = kq_w8s<4>(va | (((ha >> (4 * hf + c)) & m1) << 2), vb | (((hb >> (4 * hf + c)) & m1) << 2), dl);
+    }
+}
+
 // =====================================================================================================
 // k_kq_gemm
 // =====================================================================================================
@@ -184,9 +296,9 @@ template <int KT, int RB>
 __global__ __launch_bounds__(256) void k_kq_gemm(KQArgs g) {
     constexpr int BS  = KQ<KT>::BS;
     constexpr int NGC = KQ<KT>::NGC;
-    constexpr int CP  = NGC * 16;          // bytes between the columns of a strip
+    constexpr int CP  = KQ<KT>::CP;        // bytes between the columns of a strip
     constexpr int NGW = 32 * NGC;          // granules of a wave's strip
-    constexpr int NLW = (NGW + 63) / 64;   // loads per lane: 5 / 6 / 7
+    constexpr int NLW = (NGW + 63) / 64;   // loads per lane: 3 / 4 (q2_K / q3_K), 5 / 6 / 7
     constexpr int RT  = RB * 32;
     constexpr int AS  = 256 * 2 + 16;      // bytes between A rows in LDS
     constexpr int NLA = RT * 32 / 256;     // A granules per thread
@@ -216,7 +328,7 @@ __global__ __launch_bounds__(256) void k_kq_gemm(KQArgs g) {
 #pragma unroll
         for (int i = 0; i < NLW; ++i) {
             const int idx = i * 64 + lane;
-            if (idx < NGW) *(u32x4_t*)(Ws + idx * 16) = wreg[i];
+            if (idx < NGW) kq_stash<KT>(Ws, idx, wreg[i]);
         }
 #pragma unroll
         for (int i = 0; i < NLA; ++i) {
@@ -232,9 +344,9 @@ __global__ __launch_bounds__(256) void k_kq_gemm(KQArgs g) {
             const int cc  = min(colw + col, g.M - 1);
             wreg[i]       = (u32x4_t){0, 0, 0, 0};
             if (idx < NGW) {
-                const char* p = g.W + (int64_t)cc * g.row_bytes + (int64_t)seg * BS;
-                if (KT == 6) p = (const char*)((uintptr_t)p & ~(uintptr_t)15);
-                wreg[i] = *(const u32x4_t*)(p + gr * 16);
+                const char* p     = g.W + (int64_t)cc * g.row_bytes + (int64_t)seg * BS;
+                const uint32_t ph = KQ<KT>::PH ? (uint32_t)((uintptr_t)p & 15) : 0;
+                if (kq_granule_valid<KT>(gr, ph)) wreg[i] = *(const u32x4_t*)(p - ph + gr * 16);
             }
         }
 #pragma unroll
@@ -284,6 +396,22 @@ __global__ __launch_bounds__(256) void k_kq_gemm(KQArgs g) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) step(o[c], 128 * hf + 32 * c + 8 * r);
                 }
+        } else if constexpr (KT == 2 || KT == 3) {
+            const uint32_t off = (uint32_t)n * CP + (uint32_t)((uintptr_t)(mycol + (int64_t)seg * BS) & 15);
+            const KQHead23 h   = kq_head23<KT>(Ws, off);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int r = 2 * t + kg;
+                uint32_t ha = 0, hb = 0;
+                if (KT == 3) kq_ld8<false>(Ws, off + 8 * r, ha, hb);  // once per segment and run: both halves
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    half8_t o[4];
+                    kq_dec23<KT>(Ws, off, h, hf, t, r, ha, hb, o);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) step(o[c], 128 * hf + 32 * c + 8 * r);
+                }
+            }
         } else {
             const uint32_t off = (uint32_t)n * CP;
             const KQHead h     = kq_head45(Ws + off);
@@ -372,7 +500,7 @@ template <int KT>
 __global__ __launch_bounds__(256) void k_kq_image(half8_t* __restrict__ dst, const char* __restrict__ W, int64_t row_bytes, int64_t R, int64_t kfr, int64_t geglu_inner) {
     constexpr int BS  = KQ<KT>::BS;
     constexpr int NGC = KQ<KT>::NGC;
-    constexpr int CP  = NGC * 16;
+    constexpr int CP  = KQ<KT>::CP;
     constexpr int NGW = 32 * NGC;
     __shared__ __attribute__((aligned(16))) char Ws[32 * CP + 16];
     const int lane = threadIdx.x & 63;
@@ -383,9 +511,9 @@ __global__ __launch_bounds__(256) void k_kq_image(half8_t* __restrict__ dst, con
     for (int idx = threadIdx.x; idx < NGW; idx += 256) {
         const int col    = idx / NGC, gr = idx - col * NGC;
         const int64_t rr = min(kq_image_row(rb, col, R, geglu_inner), R - 1);
-        const char* p    = W + rr * row_bytes + (int64_t)seg * BS;
-        if (KT == 6) p = (const char*)((uintptr_t)p & ~(uintptr_t)15);
-        *(u32x4_t*)(Ws + idx * 16) = *(const u32x4_t*)(p + gr * 16);
+        const char* p     = W + rr * row_bytes + (int64_t)seg * BS;
+        const uint32_t ph = KQ<KT>::PH ? (uint32_t)((uintptr_t)p & 15) : 0;
+        if (kq_granule_valid<KT>(gr, ph)) kq_stash<KT>(Ws, idx, *(const u32x4_t*)(p - ph + gr * 16));
     }
     __syncthreads();
     const int64_t src = kq_image_row(rb, n, R, geglu_inner);
@@ -402,6 +530,16 @@ __global__ __launch_bounds__(256) void k_kq_image(half8_t* __restrict__ dst, con
         kq_dec6(Ws, off, hf, r, ds, o);
 #pragma unroll
         for (int c = 0; c < 4; ++c) out[(8 * hf + 2 * c + t) * 64] = real ? o[c] : z;  // weights 128 hf + 32 c + 16 t + 8 hi + i
+    } else if constexpr (KT == 2 || KT == 3) {  // the same (half, t) per wave and the same four fragments
+        const uint32_t off = (uint32_t)n * CP + (uint32_t)((uintptr_t)(W + min(src, R - 1) * row_bytes + (int64_t)seg * BS) & 15);
+        const int hf = wave >> 1, t = wave & 1, r = 2 * t + hi;
+        const KQHead23 h = kq_head23<KT>(Ws, off);
+        uint32_t ha = 0, hb = 0;
+        if (KT == 3) kq_ld8<false>(Ws, off + 8 * r, ha, hb);
+        half8_t o[4];
+        kq_dec23<KT>(Ws, off, h, hf, t, r, ha, hb, o);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out[(8 * hf + 2 * c + t) * 64] = real ? o[c] : z;
     } else {
         const uint32_t off = (uint32_t)n * CP;
         const KQHead h     = kq_head45(Ws + off);
@@ -429,8 +567,9 @@ static std::atomic<int64_t> g_kq_route_launches[KQ_ROUTE_COUNT];
 int64_t kq_route_launches(int route) { return route >= 0 && route < KQ_ROUTE_COUNT ? g_kq_route_launches[route].load(std::memory_order_relaxed) : 0; }
 static void kq_route_taken(KQRoute r) { g_kq_route_launches[r].fetch_add(1, std::memory_order_relaxed); }
 
-bool kq_type(int wtype) { return wtype == 12 || wtype == 13 || wtype == 14; }
-static int64_t kq_block_bytes(int wtype) { return wtype == 12 ? 144 : wtype == 13 ? 176 : 210; }
+bool kq_type(int wtype) { return wtype >= 10 && wtype <= 14; }
+static int64_t kq_block_bytes(int wtype) { return wtype == 10 ? 84 : wtype == 11 ? 110 : wtype == 12 ? 144 : wtype == 13 ? 176 : 210; }
+static bool kq_rows_aligned16(int wtype) { return wtype == 12 || wtype == 13; }
 
 // The row range is k_qgemv's and k_qgemm16's together (options qgemm16_max_rows / qgemm16_rb are shared with k_qgemm16); the hand-over to the image route is
 // set by profiles/kquant_probe.txt (one Linear, weights cache-warm, us):    4096 -> 3072 at 256 / 512 rows      3072 -> 9216 at 256 / 512 rows
@@ -442,8 +581,13 @@ static int64_t kq_block_bytes(int wtype) { return wtype == 12 ? 144 : wtype == 1
 // stream is 3.6x smaller than the image; the cache-warm image route measures 34 .. 64 us for every type).  q6_K is on a par with q8_0 up to 256 rows and 1.2 ..
 // 1.5x slower at 512 (its decode reads three byte runs through v_alignbit per four fragments): it hands over at HALF the option, 256 rows.  q5_K (not probed:
 // q4_K's decode plus one bit plane) takes q4_K's range.
+// q2_K / q3_K against q4_K from the same run (profiles/kquant_low_probe.txt), k_kq_gemm at 512 rows, median [min .. max]:
+//   q4_K   75.0 [74.5 .. 80.7]       100.8 [100.5 .. 100.9]
+//   q2_K   74.0 [73.9 .. 77.1]        99.6 [ 99.6 ..  99.7]      no slower: the full range
+//   q3_K   82.8 [80.3 .. 99.5]       113.4 [113.1 .. 115.4]      13 us slower on 3072 -> 9216 where the spreads are 0.4 .. 2.3 us (unaligned 8-byte reads
+//                                                                  and the hmask plane per four fragments): half the option, 256 rows, as q6_K
 bool kq_gemm_supported(int wtype, int64_t rows, int64_t K, int64_t M) {
-    const int64_t max_rows = wtype == 14 ? qgemm16_max_rows() / 2 : qgemm16_max_rows();
+    const int64_t max_rows = (wtype == 14 || wtype == 11) ? qgemm16_max_rows() / 2 : qgemm16_max_rows();
     return kq_type(wtype) && rows >= 1 && rows <= max_rows && K % 256 == 0 && K >= 256 && M >= 1 && M < (1ll << 30);
 }
 bool kq_image_supported(int wtype, int64_t K) { return kq_type(wtype) && K % 256 == 0 && K >= 256; }
@@ -476,7 +620,7 @@ int kq_gemm_split_k(int64_t rows, int64_t K, int64_t M) {
 void launch_kq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const void* a16, int64_t lda, int64_t rows, const void* wraw, int wtype, int64_t K, int64_t M,
                     const Epilogue& ep, float* splitk_ws, int splitk_S, const float* x32, int64_t xs, float pre_scale, bool pre_silu) {
     if (!kq_gemm_supported(wtype, rows, K, M) || (a16 == nullptr) == (x32 == nullptr) || (ep.gelu && !dst16) || (!ep.gelu && !dst) || (ep.gate && !ep.residual) ||
-        (wtype != 14 && ((uintptr_t)wraw & 15))) {
+        (kq_rows_aligned16(wtype) && ((uintptr_t)wraw & 15))) {
         fprintf(stderr, "ggml-mi355x: invalid k_kq_gemm request\n");
         abort();
     }
@@ -515,7 +659,9 @@ void launch_kq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const
         else if (rb == 2) k_kq_gemm<KT_, 2><<<grid, 256, 0, s>>>(g); \
         else k_kq_gemm<KT_, 4><<<grid, 256, 0, s>>>(g);       \
     } while (0)
-    if (wtype == 12) KQ_LAUNCH(4);
+    if (wtype == 10) KQ_LAUNCH(2);
+    else if (wtype == 11) KQ_LAUNCH(3);
+    else if (wtype == 12) KQ_LAUNCH(4);
     else if (wtype == 13) KQ_LAUNCH(5);
     else KQ_LAUNCH(6);
 #undef KQ_LAUNCH
@@ -527,7 +673,7 @@ void launch_kq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const
 
 // dst: image of wswz_bytes(R, K) bytes (rows padded to 128); geglu_inner as launch_wswz_linear takes it
 void launch_kq_image(hipStream_t s, void* dst, const void* wraw, int wtype, int64_t K, int64_t R, int64_t geglu_inner) {
-    if (!kq_image_supported(wtype, K) || R < 1 || (wtype != 14 && ((uintptr_t)wraw & 15))) {
+    if (!kq_image_supported(wtype, K) || R < 1 || (kq_rows_aligned16(wtype) && ((uintptr_t)wraw & 15))) {
         fprintf(stderr, "ggml-mi355x: invalid k_kq_image request\n");
         abort();
     }
@@ -535,7 +681,9 @@ void launch_kq_image(hipStream_t s, void* dst, const void* wraw, int wtype, int6
     KScope ks_(s, KF_PACK_F16, 0.0, (double)R * rowb + (double)Rp * K * 2.0);
     const dim3 grid((unsigned)(Rp / 32), (unsigned)(K / 256));
     kq_route_taken(KQ_IMAGE);
-    if (wtype == 12) k_kq_image<4><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, rowb, R, K / 16, geglu_inner);
+    if (wtype == 10) k_kq_image<2><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, rowb, R, K / 16, geglu_inner);
+    else if (wtype == 11) k_kq_image<3><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, rowb, R, K / 16, geglu_inner);
+    else if (wtype == 12) k_kq_image<4><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, rowb, R, K / 16, geglu_inner);
     else if (wtype == 13) k_kq_image<5><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, rowb, R, K / 16, geglu_inner);
     else k_kq_image<6><<<grid, 256, 0, s>>>((half8_t*)dst, (const char*)wraw, rowb, R, K / 16, geglu_inner);
 }
