@@ -447,6 +447,7 @@ static inline int64_t ggml_abi_blck_size(enum ggml_type t) {
         case GGML_TYPE_Q8_0:
         case GGML_TYPE_Q8_1:
         case GGML_TYPE_IQ4_NL:
+        case GGML_TYPE_MXFP4:
             return 32;
         case GGML_TYPE_Q2_K:
         case GGML_TYPE_Q3_K:
@@ -468,6 +469,7 @@ static inline size_t ggml_abi_type_size(enum ggml_type t) {
         case GGML_TYPE_Q5_0: return 22; /* half d; uint8 qh[4]; uint8 qs[16] */
         case GGML_TYPE_Q5_1: return 24; /* half d, m; uint8 qh[4]; uint8 qs[16] */
         case GGML_TYPE_IQ4_NL: return 18; /* half d; uint8 qs[16] (codes into a 16-entry table) */
+        case GGML_TYPE_MXFP4: return 17; /* uint8 e (E8M0 exponent); uint8 qs[16] (e2m1 codes) */
         case GGML_TYPE_Q8_0: return 34; /* half d; int8 qs[32] */
         case GGML_TYPE_Q8_1: return 36;
         case GGML_TYPE_Q2_K: return 84;  /* uint8 scales[16]; uint8 qs[64]; half d, dmin */

@@ -191,12 +191,12 @@ struct ggml_backend_mi355x_stats {
     int64_t lin_kq_gemm_reduce;      /* the slab reduce behind a split launch_kq_gemm */
     int64_t lin_kq_image;            /* launch_kq_image: the f16 weight image of a K-quant weight (cached once per weight, or just in time under option jit_qimages) */
     int64_t kquant_linears;          /* Linears with a q2_K .. q6_K weight (per plan, whatever route they take) */
-    /* 32-weight block Linear weights (q4_1 / q5_0 / q5_1 / iq4_nl raw in HBM, kernels/bquant.hip); lin_bq_*: per launch call, in the order of BQRoute */
+    /* 32-weight block Linear weights (q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4 raw in HBM, kernels/bquant.hip); lin_bq_*: per launch call, in the order of BQRoute */
     int64_t lin_bq_gemm_rb1;         /* launch_bq_gemm: k_bq_gemm<BT, 1> (32-row tiles; 1 .. 4 rows read their f32 rows themselves) */
     int64_t lin_bq_gemm_rb2;         /* ... k_bq_gemm<BT, 2> */
     int64_t lin_bq_gemm_reduce;      /* the slab reduce behind a split launch_bq_gemm */
     int64_t lin_bq_image;            /* launch_bq_image: the f16 weight image of such a weight (cached once per weight, or just in time under option jit_qimages) */
-    int64_t bquant_linears;          /* Linears with a q4_1 / q5_0 / q5_1 / iq4_nl weight (per plan, whatever route they take) */
+    int64_t bquant_linears;          /* Linears with a q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4 weight (per plan, whatever route they take) */
     /* FLASH_ATTN_EXT beyond head dim 160 (kernels/flash_wide.hip) */
     int64_t flash_wide_launches;     /* launch_flash_attn calls that took k_flash_wide (160 < d <= 512, d % 64 == 0, f16 K / V; per launch call, as flash_short_launches) */
 };

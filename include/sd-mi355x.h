@@ -85,6 +85,7 @@ enum sdm_type_t {
     SDM_TYPE_Q6_K = 14,
     SDM_TYPE_IQ4_NL = 20, /* 32-weight blocks of 4-bit codes into ggml's 16-entry table; raw on the device like q4_1 */
     SDM_TYPE_BF16 = 30,
+    SDM_TYPE_MXFP4 = 39, /* OCP microscaling blocks: 32 e2m1 codes under one E8M0 exponent byte, 17 bytes; raw on the device like q4_1 */
 };
 
 /* SDM_SAMPLE_METHOD_COUNT = "the family's default" like the reference's SAMPLE_METHOD_COUNT (sd_get_default_sample_method,
@@ -220,13 +221,14 @@ SD_API bool sd_set_tensor_f32(sdm_ctx_t* ctx, const char* name, const float* src
 
 /* ---- checkpoint files, told apart by their first bytes:
  *   safetensors          F32 / F16 / BF16 native; F64 / I64 / F8_E4M3 / F8_E5M2 widened at load
- *   GGUF v2 / v3         F32 / F16 / BF16 / Q8_0 / Q4_0 native; Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_NL decoded at load —
- *                        except a tensor stored in its parameter's own type (wtype Q4_1 / Q5_0 / Q5_1 / IQ4_NL / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K): its blocks are copied raw
+ *   GGUF v2 / v3         F32 / F16 / BF16 / Q8_0 / Q4_0 native; Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_NL / MXFP4 decoded at load —
+ *                        except a tensor stored in its parameter's own type (wtype Q4_1 / Q5_0 / Q5_1 / IQ4_NL / MXFP4 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K): its blocks are copied raw
  *                          type    block (little-endian)                       bytes / 32 weights   value
  *                          Q4_1    f16 d, f16 m, u8 qs[16]                     20                   q * d + m
  *                          Q5_0    f16 d, u8 qh[4], u8 qs[16]                  22                   (q - 16) * d
  *                          Q5_1    f16 d, f16 m, u8 qh[4], u8 qs[16]           24                   q * d + m
  *                          IQ4_NL  f16 d, u8 qs[16]                            18                   d * kvalues[q]
+ *                          MXFP4   u8 e, u8 qs[16]                             17                   kvalues[q] * 2^(e - 128)   (e2m1 values doubled)
  *   PyTorch checkpoints  torch.save's zip container (.ckpt / .pt / .pth / .bin, PyTorch >= 1.6) and the legacy stream: float / half / bfloat16 /
  *                        double / long storages of contiguous tensors, found in the root dictionary and the dictionaries nested in it ("state_dict");
  *                        the pickle is interpreted, never executed (csrc/host/torch_ckpt_io.hpp)

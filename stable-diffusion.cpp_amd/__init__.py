@@ -24,7 +24,7 @@ BACKEND_LIB = Path(os.environ.get("SDCPP_BACKEND_LIB", str(LIB_DIR / "libggml-mi
 # ggml_type numeric values (include/ggml-abi.h)
 F32, F16, Q4_0, Q8_0, I32, BF16 = 0, 1, 2, 8, 26, 30
 Q2_K, Q3_K, Q4_K, Q5_K, Q6_K = 10, 11, 12, 13, 14  # K-quant super-blocks (256 weights): Linear weights only
-Q4_1, Q5_0, Q5_1, IQ4_NL = 3, 6, 7, 20  # 32-weight blocks kept raw on the device (kernels/bquant.hip): Linear weights only
+Q4_1, Q5_0, Q5_1, IQ4_NL, MXFP4 = 3, 6, 7, 20, 39  # 32-weight blocks kept raw on the device (kernels/bquant.hip): Linear weights only
 TYPE_SIZE = {F32: 4, F16: 2, BF16: 2, I32: 4}
 
 # sd_model_family_t

@@ -273,12 +273,12 @@ inline bool kq_weight_ok(const ggml_tensor* w) {
     return kq_type((int)w->type) && w->ne[0] >= 256 && w->ne[0] % 256 == 0 && w->ne[2] == 1 && w->ne[3] == 1 && w->nb[0] == ggml_abi_type_size(w->type) &&
            (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, w->ne[0]);
 }
-// a q4_1 / q5_0 / q5_1 / iq4_nl Linear weight the block kernels (kernels/bquant.hip) take: whole 32-weight blocks per row, rows packed
+// a q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4 Linear weight the block kernels (kernels/bquant.hip) take: whole 32-weight blocks per row, rows packed
 inline bool bq_weight_ok(const ggml_tensor* w) {
     return bq_type((int)w->type) && w->ne[0] >= 32 && w->ne[0] % 32 == 0 && w->ne[2] == 1 && w->ne[3] == 1 && w->nb[0] == ggml_abi_type_size(w->type) &&
            (int64_t)w->nb[1] == (int64_t)ggml_abi_row_size(w->type, w->ne[0]);
 }
-inline const char* bq_type_name(int t) { return t == GGML_TYPE_Q4_1 ? "q4_1" : t == GGML_TYPE_Q5_0 ? "q5_0" : t == GGML_TYPE_Q5_1 ? "q5_1" : "iq4_nl"; }
+inline const char* bq_type_name(int t) { return t == GGML_TYPE_Q4_1 ? "q4_1" : t == GGML_TYPE_Q5_0 ? "q5_0" : t == GGML_TYPE_Q5_1 ? "q5_1" : t == GGML_TYPE_MXFP4 ? "mxfp4" : "iq4_nl"; }
 
 uint64_t fnv(uint64_t h, const void* p, size_t n) {
     const unsigned char* c = (const unsigned char*)p;
@@ -3092,7 +3092,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                         kq_type_name((int)n->src[0]->type));
                 return false;
             }
-            if (bq_type((int)n->src[0]->type)) {  // ... nor over q4_1 / q5_0 / q5_1 / iq4_nl blocks
+            if (bq_type((int)n->src[0]->type)) {  // ... nor over q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4 blocks
                 fprintf(stderr, "[ggml-mi355x] node %d: MUL_MAT with a %s weight outside the Linear path (weight not in a WEIGHTS buffer, unaligned rows, or option mfma_gemm = 0)\n", i,
                         bq_type_name((int)n->src[0]->type));
                 return false;
@@ -4717,7 +4717,7 @@ bool planner_supports_op(const ggml_tensor* n) {
             const bool bt = b->type == GGML_TYPE_F32 || b->type == GGML_TYPE_F16;
             // q2_K .. q6_K: Linear weights only (the K-quant kernels; there is no generic matmul over super-blocks)
             // — and what linear_fast_ok asks that is known here; what is not (the weight's buffer usage, the addresses) makes the plan fail loudly (plan_single)
-            // q4_1 / q5_0 / q5_1 / iq4_nl (kernels/bquant.hip): the same, with whole 32-weight blocks per row
+            // q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4 (kernels/bquant.hip): the same, with whole 32-weight blocks per row
             if (kq_type((int)a->type) || bq_type((int)a->type))
                 return g_opt.mfma_gemm && (kq_weight_ok(a) || bq_weight_ok(a)) && ggml_abi_is_contiguous(a) && b->type == GGML_TYPE_F32 && b->nb[0] == 4 && b->ne[0] % 4 == 0 && b->nb[1] % 16 == 0 &&
                        ggml_abi_is_contiguous(n);

@@ -137,6 +137,7 @@ const char* ggml_type_name(enum ggml_type type) {
         case GGML_TYPE_Q5_0: return "q5_0";
         case GGML_TYPE_Q5_1: return "q5_1";
         case GGML_TYPE_IQ4_NL: return "iq4_nl";
+        case GGML_TYPE_MXFP4: return "mxfp4";
         case GGML_TYPE_Q8_0: return "q8_0";
         case GGML_TYPE_Q2_K: return "q2_K";
         case GGML_TYPE_Q3_K: return "q3_K";
@@ -552,6 +553,53 @@ static void quantize_row_iq4_nl(const float* x, uint8_t* y, int64_t k) {
     }
 }
 
+// ---- mxfp4 (OCP microscaling: block_mxfp4 {u8 e; u8 qs[16]}, 32 weights in 17 bytes; nibble order as above).  x = kvalues[q] * d with the e2m1 values
+// doubled in the table and d = GGML_E8M0_TO_FP32_HALF(e) = 2^(e - 128) (f32 subnormals for e = 0 and 1): a small integer times a power of two, exact in f32.
+static const int8_t kvalues_mxfp4[16] = {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12};
+static inline float e8m0_to_fp32_half(uint8_t e) {
+    const uint32_t bits = e < 2 ? 0x00200000u << e : (uint32_t)(e - 1) << 23;
+    float d;
+    memcpy(&d, &bits, 4);
+    return d;
+}
+static void dequantize_row_mxfp4(const uint8_t* raw, float* dst, int64_t n) {
+    for (int64_t b = 0; b < n / 32; ++b) {
+        const uint8_t* p = raw + b * 17;
+        const float d    = e8m0_to_fp32_half(p[0]);
+        float* y         = dst + b * 32;
+        for (int j = 0; j < 16; ++j) {
+            y[j]      = (float)kvalues_mxfp4[p[1 + j] & 0xF] * d;
+            y[j + 16] = (float)kvalues_mxfp4[p[1 + j] >> 4] * d;
+        }
+    }
+}
+// A PLAIN encoder by the rule of ggml's quantize_row_mxfp4_ref: e = floor(log2(amax)) - 2 + 127 (0 for an all-zero block), then the nearest table entry for
+// each weight, ties to the smaller index.  Where it differs: floor(log2) is taken from the f32 exponent (frexp), not from log2f, and e is clamped to 0 .. 254,
+// so amax just below a power of two or outside 2^-125 .. 2^127 may get another exponent than upstream's.  Under the chosen scale the largest weight lies in
+// [8, 16) d: values above 12 d saturate at the last code.  A block whose weights are k * d for table entries k round-trips exactly (an exact distance of 0 wins).
+static void quantize_row_mxfp4(const float* x, uint8_t* y, int64_t k) {
+    for (int64_t i = 0; i < k / 32; ++i, x += 32) {
+        uint8_t* p = y + i * 17;
+        float amax = 0.f;
+        for (int j = 0; j < 32; ++j) amax = std::max(amax, fabsf(x[j]));
+        int e = 0;
+        if (amax > 0.f && std::isfinite(amax)) {
+            int ex;
+            frexpf(amax, &ex);  // amax = m * 2^ex, m in [0.5, 1): floor(log2(amax)) = ex - 1
+            e = std::max(0, std::min(254, ex - 1 - 2 + 127));
+        }
+        p[0]          = (uint8_t)e;
+        const float d = e8m0_to_fp32_half((uint8_t)e);
+        auto nearest  = [&](float v) {
+            int best = 0;
+            for (int c = 1; c < 16; ++c)
+                if (fabsf((float)kvalues_mxfp4[c] * d - v) < fabsf((float)kvalues_mxfp4[best] * d - v)) best = c;
+            return best;
+        };
+        for (int j = 0; j < 16; ++j) p[1 + j] = (uint8_t)(nearest(x[j]) | (nearest(x[j + 16]) << 4));
+    }
+}
+
 // ---- K-quants (ggml-common.h block_q{4,5,6}_K; 256 weights per super-block, little-endian fields).  The decoders restate upstream's dequantize_row_q*_K with
 // its operations in its order, each rounded on its own (d1 = d * sc; m1 = dmin * m; y = d1 * q - m1 / y = d * sc * q): the values the device kernels
 // (kernels/kquant.hip) round to f16, and what the model loader decodes a file tensor of these types with.
@@ -825,6 +873,7 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float* src, void* dst, int
             case GGML_TYPE_Q5_0:
             case GGML_TYPE_Q5_1: quantize_row_q4_1_q5(type, x, y, n_per_row); break;
             case GGML_TYPE_IQ4_NL: quantize_row_iq4_nl(x, y, n_per_row); break;
+            case GGML_TYPE_MXFP4: quantize_row_mxfp4(x, y, n_per_row); break;
             case GGML_TYPE_Q2_K: quantize_row_q2_K(x, y, n_per_row); break;
             case GGML_TYPE_Q3_K: quantize_row_q3_K(x, y, n_per_row); break;
             case GGML_TYPE_Q4_K: quantize_row_q45_K(x, y, n_per_row, false); break;
@@ -870,6 +919,7 @@ void ggml_dequantize_row(enum ggml_type type, const void* src, float* dst, int64
         case GGML_TYPE_Q5_0:
         case GGML_TYPE_Q5_1: dequantize_row_q4_1_q5(type, p, dst, n); break;
         case GGML_TYPE_IQ4_NL: dequantize_row_iq4_nl(p, dst, n); break;
+        case GGML_TYPE_MXFP4: dequantize_row_mxfp4(p, dst, n); break;
         case GGML_TYPE_Q2_K: dequantize_row_q23_K(p, dst, n, false); break;
         case GGML_TYPE_Q3_K: dequantize_row_q23_K(p, dst, n, true); break;
         case GGML_TYPE_Q4_K: dequantize_row_q45_K(p, dst, n, false); break;

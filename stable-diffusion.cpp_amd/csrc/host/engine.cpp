@@ -1118,7 +1118,7 @@ static int64_t load_weights_scoped(sdm_ctx_t* ctx, const char* path, const char*
             return -1;
         }
         if (ft.kind != SrcKind::NATIVE && ft.src_type == (int)t->type && !lin_as_conv1x1 && ft.nbytes == ggml_nbytes(t)) {
-            // stored in the parameter's own block type (K-quants, q4_1 / q5_0 / q5_1 / iq4_nl): the blocks arrive byte for byte (no decode, no second quantisation)
+            // stored in the parameter's own block type (K-quants, q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4): the blocks arrive byte for byte (no decode, no second quantisation)
             ggml_backend_tensor_set(t, raw.data(), 0, ggml_nbytes(t));
         } else if (ft.kind != SrcKind::NATIVE) {
             f32.resize(n);

@@ -27,8 +27,9 @@ namespace sdmi {
 // decoded to f32 at load time and re-encoded in the parameter's type, like convert_tensor does for every source type (src/model_loader.cpp:155-205)
 // K-quants (Q2_K .. Q6_K: super-blocks of 256 weights with 4- / 6-bit sub-block scales — the q2_k / q3_k / q4_k FLUX and SD3.5 files docs/flux.md:36-38
 // points its users at) and IQ4_NL (32 weights, non-linear 4-bit code book) take the same route: decoded to f32 at load, re-encoded in the parameter's type —
-// except a q4_1 / q5_0 / q5_1 / iq4_nl / q2_K .. q6_K tensor whose parameter has that very type (context wtype): its blocks are copied raw (engine.cpp, FileTensor::src_type).
-enum class SrcKind { NATIVE, F64, I64, F8_E4M3, F8_E5M2, Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL };
+// MXFP4 (32 e2m1 codes under one E8M0 exponent byte) likewise —
+// except a q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4 / q2_K .. q6_K tensor whose parameter has that very type (context wtype): its blocks are copied raw (engine.cpp, FileTensor::src_type).
+enum class SrcKind { NATIVE, F64, I64, F8_E4M3, F8_E5M2, Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, MXFP4 };
 
 // ggml type id -> (kind, weights per block, bytes per block) of the block formats decoded at load time; false for every other type
 inline bool gguf_decoded_kind(int ggml_type_id, SrcKind& kind, int& blck, int& bytes) {
@@ -42,6 +43,7 @@ inline bool gguf_decoded_kind(int ggml_type_id, SrcKind& kind, int& blck, int& b
         case 13: kind = SrcKind::Q5_K, blck = 256, bytes = 176; return true;
         case 14: kind = SrcKind::Q6_K, blck = 256, bytes = 210; return true;
         case 20: kind = SrcKind::IQ4_NL, blck = 32, bytes = 18; return true;
+        case 39: kind = SrcKind::MXFP4, blck = 32, bytes = 17; return true;
         default: return false;
     }
 }
@@ -197,11 +199,12 @@ inline void decode_src_kind(SrcKind kind, const uint8_t* raw, int64_t n, float* 
         case SrcKind::F8_E5M2:
             for (int64_t i = 0; i < n; ++i) dst[i] = f8_e5m2_to_f32(raw[i]);
             break;
-        //   q4_1 / q5_0 / q5_1 / iq4_nl (32 weights per block): the front-end's decoders (ggml.cpp), the one host restatement of these formats
+        //   q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4 (32 weights per block): the front-end's decoders (ggml.cpp), the one host restatement of these formats
         case SrcKind::Q4_1: ggml_dequantize_row(GGML_TYPE_Q4_1, raw, dst, n); break;
         case SrcKind::Q5_0: ggml_dequantize_row(GGML_TYPE_Q5_0, raw, dst, n); break;
         case SrcKind::Q5_1: ggml_dequantize_row(GGML_TYPE_Q5_1, raw, dst, n); break;
         case SrcKind::IQ4_NL: ggml_dequantize_row(GGML_TYPE_IQ4_NL, raw, dst, n); break;
+        case SrcKind::MXFP4: ggml_dequantize_row(GGML_TYPE_MXFP4, raw, dst, n); break;
         //   K-quants (256 weights per super-block): likewise
         case SrcKind::Q2_K: ggml_dequantize_row(GGML_TYPE_Q2_K, raw, dst, n); break;
         case SrcKind::Q3_K: ggml_dequantize_row(GGML_TYPE_Q3_K, raw, dst, n); break;
@@ -426,7 +429,7 @@ inline bool read_gguf(const std::string& path, ModelFile& mf) {
         const int ty = (int)t.type;
         SrcKind dk;
         int dblck = 0, dbytes = 0;
-        if (gguf_decoded_kind(ty, dk, dblck, dbytes)) {  // q4_1 / q5_0 / q5_1 / K-quants / iq4_nl: decoded to f32 when the tensor is read
+        if (gguf_decoded_kind(ty, dk, dblck, dbytes)) {  // q4_1 / q5_0 / q5_1 / K-quants / iq4_nl / mxfp4: decoded to f32 when the tensor is read
             const uint64_t bs = (uint64_t)dbytes;
             uint64_t n        = 1;
             bool dims_ok      = t.ne[0] > 0 && t.ne[0] % dblck == 0 && t.ne[0] < (1ll << 40);
@@ -448,7 +451,7 @@ inline bool read_gguf(const std::string& path, ModelFile& mf) {
             continue;
         }
         const bool known = t.type == GGML_TYPE_F32 || t.type == GGML_TYPE_F16 || t.type == GGML_TYPE_BF16 || t.type == GGML_TYPE_Q8_0 || t.type == GGML_TYPE_Q4_0;
-        if (!known) {  // IQ types other than iq4_nl, ternary / MX types, integer tensors: not decodable by this build — an ERROR if a declared parameter needs one
+        if (!known) {  // IQ types other than iq4_nl, ternary types, integer tensors: not decodable by this build — an ERROR if a declared parameter needs one
             mf.undecodable[t.name] = "ggml type " + std::to_string((int)t.type);
             continue;
         }

@@ -7,6 +7,8 @@
 //   q5_0   {f16 d, u8 qh[4], u8 qs[16]}         22 B   y = (q - 16) * d
 //   q5_1   {f16 d, f16 m, u8 qh[4], u8 qs[16]}  24 B   y = q * d + m
 //   iq4_nl {f16 d, u8 qs[16]}                   18 B   y = d * kvalues[q]      (ggml's 16-entry table -127 .. 113)
+//   mxfp4  {u8 e, u8 qs[16]}                    17 B   y = kvalues[q] * 2^(e - 128)   (the e2m1 values doubled; rows at ANY byte phase: BQ<39>, BQStrip<39>,
+//                                                      bq_block<39> below and mxfp4_decode.h)
 // element j of a block: low nibble of qs[j], element j + 16: high nibble; fifth bit = bit j / j + 16 of the little-endian u32 qh.
 // Every product is EXACT in f32 (an integer of at most 7 bits times an f16 of 11), so y carries at most one f32 rounding, the "+ m": fused or unfused evaluation
 // give the same y, and bit equality with a NumPy float32 restatement is well defined.  f32 -> f16 is a SECOND rounding and stays one: y is formed with plain f32
@@ -42,6 +44,7 @@
 #include "device_utils.h"
 #include "kernels.h"
 #include "ktime.h"
+#include "mxfp4_decode.h"
 
 namespace mi355x {
 
@@ -70,6 +73,11 @@ struct BQ<20> {  // iq4_nl
     static constexpr int BS = 18, QH = -1, QS = 2;
     static constexpr bool HASM = false, A4 = false;
 };
+template <>
+struct BQ<39> {  // mxfp4: {u8 e, u8 qs[16]}, no f16 field; rows start at any byte
+    static constexpr int BS = 17, QH = -1, QS = 1;
+    static constexpr bool HASM = false, A4 = false;
+};
 // a full piece is 8 BS bytes at a phase of at most 14 (BS even): 8 BS / 16 + 1 aligned granules cover it
 template <int BT>
 struct BQStrip {
@@ -77,6 +85,17 @@ struct BQStrip {
     static constexpr int CP  = 16 * NGC + 8;   // bytes between the columns of a strip: 2 x odd dwords (file header)
     static constexpr int NGW = 32 * NGC;       // granules of a 32-column strip
     static constexpr int BYTES = 32 * CP + 16; // (+ 16: the third dword of an unaligned 8-byte read at the strip's end)
+};
+
+// mxfp4: a full piece is 136 bytes at a phase of 0 .. 15: ceil((15 + 136) / 16) = 10 aligned granules cover it.  Stride 168 bytes = 42 dwords = 2 x 21: column n
+// starts on bank 42 n mod 64, 32 different even banks (21 is odd).  The farthest read, the third dword of block 7's upper code half at phase 15, ends at byte
+// 152 of its column.
+template <>
+struct BQStrip<39> {
+    static constexpr int NGC = 10;
+    static constexpr int CP  = 16 * NGC + 8;
+    static constexpr int NGW = 32 * NGC;
+    static constexpr int BYTES = 32 * CP + 16;
 };
 
 constexpr int8_t kIQ4NL[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
@@ -153,6 +172,28 @@ __device__ __forceinline__ void bq_block(const char* strip, uint32_t off, int kg
     }
     lo = bq_w8<BT>(la, lb, d, m);
     hi = bq_w8<BT>(ua, ub, d, m);
+}
+
+// mxfp4: the exponent byte gives the block's table registers and f16 scale (mxfp4_decode.h); the eight code bytes lie at ANY byte offset: three dwords and
+// v_alignbit by 0 / 8 / 16 / 24 bits.  Four codes -> two half2, in k order
+template <>
+__device__ __forceinline__ void bq_block<39>(const char* strip, uint32_t off, int kg, half8_t& lo, half8_t& hi) {
+    const MX4Scale m  = mx4_prep(*(const uint8_t*)(strip + off));
+    const uint32_t o  = off + 1 + 8 * kg;
+    const char* p     = strip + (o & ~3u);
+    const uint32_t sh = (o & 3u) * 8u;
+    const uint32_t r0 = *(const uint32_t*)p, r1 = *(const uint32_t*)(p + 4), r2 = *(const uint32_t*)(p + 8);
+    const uint32_t a = __builtin_amdgcn_alignbit(r1, r0, sh), b = __builtin_amdgcn_alignbit(r2, r1, sh);
+    mx4_half2_t l[4], u[4];
+    mx4_w4(a & 0x0F0F0F0Fu, m, l[0], l[1]);
+    mx4_w4(b & 0x0F0F0F0Fu, m, l[2], l[3]);
+    mx4_w4((a >> 4) & 0x0F0F0F0Fu, m, u[0], u[1]);
+    mx4_w4((b >> 4) & 0x0F0F0F0Fu, m, u[2], u[3]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        lo[2 * j] = l[j][0], lo[2 * j + 1] = l[j][1];
+        hi[2 * j] = u[j][0], hi[2 * j + 1] = u[j][1];
+    }
 }
 
 // granule gr of the covering fetch of the nb-block piece at p: loaded only if it holds a valid byte (else zero, never read as a weight)
@@ -402,10 +443,10 @@ static std::atomic<int64_t> g_bq_route_launches[BQ_ROUTE_COUNT];
 int64_t bq_route_launches(int route) { return route >= 0 && route < BQ_ROUTE_COUNT ? g_bq_route_launches[route].load(std::memory_order_relaxed) : 0; }
 static void bq_route_taken(BQRoute r) { g_bq_route_launches[r].fetch_add(1, std::memory_order_relaxed); }
 
-bool bq_type(int wtype) { return wtype == 3 || wtype == 6 || wtype == 7 || wtype == 20; }
-static int64_t bq_block_bytes(int wtype) { return wtype == 3 ? 20 : wtype == 6 ? 22 : wtype == 7 ? 24 : 18; }
+bool bq_type(int wtype) { return wtype == 3 || wtype == 6 || wtype == 7 || wtype == 20 || wtype == 39; }
+static int64_t bq_block_bytes(int wtype) { return wtype == 3 ? 20 : wtype == 6 ? 22 : wtype == 7 ? 24 : wtype == 39 ? 17 : 18; }
 
-// The row range is shared with k_qgemm16 and k_kq_gemm (option qgemm16_max_rows, 512), one value for the four types.  profiles/bquant_probe.txt (one Linear,
+// The row range is shared with k_qgemm16 and k_kq_gemm (option qgemm16_max_rows, 512), one value for the five types (mxfp4: profiles/mxfp4_probe.txt, at or below iq4_nl at every row count).  profiles/bquant_probe.txt (one Linear,
 // weights cache-warm, us) does NOT show the kernel ahead of its own cached-image route: 4096 -> 3072 at 256 / 512 rows 58 / 78 (q5_0 60 / 84) against 34 / 45,
 // 1280 -> 1280 at 1 row 29 against 20; a tie at 768 -> 320 and at 3072 -> 18432, 1 row.  q4_0's k_qgemm16 (parent commit: 56.7 / 70.0) loses to its image alike;
 // this kernel is 1.01 .. 1.12x of it (q5_0 1.06 .. 1.20x).  The range is kept for what it is kept for there: no f16 image (2 B per weight) exists for such a Linear.
@@ -482,6 +523,7 @@ void launch_bq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const
     if (wtype == 3) BQ_LAUNCH(3);
     else if (wtype == 6) BQ_LAUNCH(6);
     else if (wtype == 7) BQ_LAUNCH(7);
+    else if (wtype == 39) BQ_LAUNCH(39);
     else BQ_LAUNCH(20);
 #undef BQ_LAUNCH
     if (S > 1) {
@@ -505,6 +547,7 @@ void launch_bq_image(hipStream_t s, void* dst, const void* wraw, int wtype, int6
     if (wtype == 3) k_bq_image<3><<<grid, 256, 0, s>>>(d, w, rowb, R, (int)(K / 32), Kp / 16, geglu_inner);
     else if (wtype == 6) k_bq_image<6><<<grid, 256, 0, s>>>(d, w, rowb, R, (int)(K / 32), Kp / 16, geglu_inner);
     else if (wtype == 7) k_bq_image<7><<<grid, 256, 0, s>>>(d, w, rowb, R, (int)(K / 32), Kp / 16, geglu_inner);
+    else if (wtype == 39) k_bq_image<39><<<grid, 256, 0, s>>>(d, w, rowb, R, (int)(K / 32), Kp / 16, geglu_inner);
     else k_bq_image<20><<<grid, 256, 0, s>>>(d, w, rowb, R, (int)(K / 32), Kp / 16, geglu_inner);
 }
 

@@ -385,7 +385,7 @@ void launch_kq_image(hipStream_t s, void* dst, const void* wraw, int wtype, int6
 enum KQRoute { KQ_GEMM_RB1 = 0, KQ_GEMM_RB2, KQ_GEMM_RB4, KQ_GEMM_REDUCE, KQ_IMAGE, KQ_ROUTE_COUNT };
 int64_t kq_route_launches(int route);
 
-// ---- bquant.hip: Linears over RAW q4_1 (wtype 3) / q5_0 (6) / q5_1 (7) / iq4_nl (20) blocks of 32 weights, any K % 32 == 0; every route multiplies by
+// ---- bquant.hip: Linears over RAW q4_1 (wtype 3) / q5_0 (6) / q5_1 (7) / iq4_nl (20) / mxfp4 (39) blocks of 32 weights, any K % 32 == 0; every route multiplies by
 // w16 = f16(ggml's dequantised f32 value) ----
 bool bq_type(int wtype);
 // k_bq_gemm: 1 .. bq_gemm_max_rows(wtype) activation rows, the blocks decoded in registers into MFMA fragments (no image).  Operands, epilogues and split-K as
