@@ -199,6 +199,8 @@ struct ggml_backend_mi355x_stats {
     int64_t bquant_linears;          /* Linears with a q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4 weight (per plan, whatever route they take) */
     /* FLASH_ATTN_EXT beyond head dim 160 (kernels/flash_wide.hip) */
     int64_t flash_wide_launches;     /* launch_flash_attn calls that took k_flash_wide (160 < d <= 512, d % 64 == 0, f16 K / V; per launch call, as flash_short_launches) */
+    /* masked FLASH_ATTN_EXT (kernels/flash_mask.hip) */
+    int64_t flash_mask_launches;     /* launch_flash_attn calls that took k_flash_mask (f16 mask in src[3], d = 64 / 128, f16 K / V; per launch call) */
 };
 GGML_MI355X_API void ggml_backend_mi355x_get_stats(struct ggml_backend_mi355x_stats* out);
 /* Host enum numbering, resolved BY NAME.  The numeric values of `enum ggml_op` / `enum ggml_unary_op` in ggml-abi.h are a recollection of upstream, and

@@ -237,8 +237,8 @@ inline bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
 // reader is the flash node for the next allocation of that size — which is this CONT.
 bool flash_out_aliases_operand(const ggml_tensor* ct, const ggml_tensor* fa, bool q_in_arena, bool k_in_arena, bool v_in_arena) {
     const size_t on = ggml_abi_nbytes(ct);
-    const bool skip[3] = {q_in_arena, k_in_arena, v_in_arena};
-    for (int j = 0; j < 3; ++j) {
+    const bool skip[4] = {q_in_arena, k_in_arena, v_in_arena, false};  // src[3], the mask of a masked node: a CAST that dies at the flash node like Q / K / V do
+    for (int j = 0; j < 4; ++j) {
         const ggml_tensor* o = fa->src[j];
         if (!o || skip[j]) continue;
         const ggml_tensor* root = o->view_src ? o->view_src : o;  // a view's bytes lie inside the tensor it aliases: test that whole block
@@ -1753,7 +1753,7 @@ void plan_hoisted_kv(Builder& B, hipStream_t s) {
                 jf = c;
                 ++nread;
             }
-        if (nread != 1 || (gi.node(j5)->flags & GGML_TENSOR_FLAG_OUTPUT) || xop(gi.node(jf)) != GGML_OP_FLASH_ATTN_EXT || !planner_supports_op(gi.node(jf)) ||
+        if (nread != 1 || (gi.node(j5)->flags & GGML_TENSOR_FLAG_OUTPUT) || xop(gi.node(jf)) != GGML_OP_FLASH_ATTN_EXT || gi.node(jf)->src[3] || !planner_supports_op(gi.node(jf)) ||
             !flash_attn_supported(gi.node(jf)->src[0]->ne[0], gi.node(jf)->src[2]->ne[0]))  // (the wide kernel, d > 160, reads K / V where the graph puts them)
             continue;
         const ggml_tensor* f = gi.node(jf);
@@ -3191,6 +3191,10 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
             const auto qal         = B.q_alias.find(n->src[0]);
             const ggml_tensor* qsrc = qal != B.q_alias.end() ? qal->second : n->src[0];
             View4 q = view_of(qsrc), k = view_of(n->src[1]), v = view_of(n->src[2]);
+            // masked node (k_flash_mask): f32 Q where the graph puts it (every Q pattern tests !src[3]) and the f32 output forms only — the node's own output, or the
+            // VIEW -> CONT tail written in its final layout; the f16 operand-image forms below are the unmasked kernels'
+            const bool masked = n->src[3] != nullptr;
+            const View4 mk    = masked ? view_of(n->src[3]) : q;
             float* dst       = (float*)n->data;
             const float sc   = ggml_abi_op_param_f32(n, 0);
             const auto q16it = B.q16.find(qsrc);
@@ -3324,7 +3328,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                             fprintf(stderr, "[plan flash] node %d of %d (view %d): d %lld H %lld Lq %lld N %lld -> %s; q16 %d kmoved %d vmoved %d; cont %p q %p k %p v %p\n", i, gi.g->n_nodes, (int)gi.is_view,
                                     (long long)d, (long long)H, (long long)Lq, (long long)Nimg, cpart != B.cat16_part.end() && C % 8 == 0 ? "cat16 column range" : all_consumers_gemm16(gi, j2, false) ? "f16 operand image" : "f32 final layout",
                                     (int)q16, (int)kmoved, (int)vmoved, ct->data, n->src[0]->data, n->src[1]->data, n->src[2]->data);
-                        if (cpart != B.cat16_part.end() && C % 8 == 0) {
+                        if (!masked && cpart != B.cat16_part.end() && C % 8 == 0) {
                             // the output is one column range of a Linear's operand image (plan_cat_rows16): store it there as f16, nothing else reads it
                             const Builder::Cat16Part pt = cpart->second;
                             Planner* P                  = B.P;
@@ -3337,7 +3341,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                                 launch_flash_attn(st, f2, qfix(q), kfix(k), vfix(v), sc);
                             });
                             B.cat16[pt.cat].written[pt.part] = true;
-                        } else if (std::vector<FlashSlice> slices; all_consumers_gemm16(gi, j2, false) || flash_out_token_slices(gi, j2, C, Lq, Nimg, slices)) {
+                        } else if (std::vector<FlashSlice> slices; !masked && (all_consumers_gemm16(gi, j2, false) || flash_out_token_slices(gi, j2, C, Lq, Nimg, slices))) {
                             // every reader is a weight GEMM (to_out) — directly, or through token slices of the [C, Lq, N] tensor (MMDiT block_mixing, mmdit.hpp:651-667;
                             // FLUX double blocks: the txt / img rows of the joint attention go to two proj Linears): emit only the f16 operand image [tok][C]; a slice's
                             // Linear reads its rows out of it (runs of L rows, Lq apart: Epilogue::a_run_L / a_run_S) — no f32 tensor, no pack pass, and the image lives
@@ -3374,14 +3378,14 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                                 f2.nb_q = C * 4;
                                 f2.nb_h = d * 4;
                                 f2.nb_n = Lq * C * 4;
-                                launch_flash_attn(st, f2, qfix(q), kfix(k), vfix(v), sc);
+                                launch_flash_attn(st, f2, qfix(q), kfix(k), vfix(v), sc, masked ? &mk : nullptr);
                             });
                         } else {
                             // the graph allocator handed the CONT the block of a Q / K / V operand that dies at the flash node (found at SD3.5-large batch 2, where the
                             // CONT got V's block: every output was NaN): writing the final layout from inside the kernel would overwrite operand rows other
                             // workgroups still read.  The node's own output never aliases its operands: run it plain, VIEW -> CONT as a copy
                             STAT(flash_out_alias)++;
-                            B.emit([=](hipStream_t st) { launch_flash_attn(st, fo, qfix(q), kfix(k), vfix(v), sc); });
+                            B.emit([=](hipStream_t st) { launch_flash_attn(st, fo, qfix(q), kfix(k), vfix(v), sc, masked ? &mk : nullptr); });
                             STAT(fused_attention)++;
                             return true;
                         }
@@ -3393,7 +3397,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
             }
             // one image: the node's own [d, H, Lq] output IS the token-major [C, Lq] tensor (ggml_ext_attention_ext reshapes it without a CONT; FLUX at batch 1).  Read
             // only through token slices feeding weight GEMMs (flux.hpp:560-575: txt_attn_out / img_attn_out -> proj): the f16 operand image again, no f32 tensor
-            if (g_opt.fusion && n->ne[3] == 1 && contig(n) && !(n->flags & GGML_TENSOR_FLAG_OUTPUT)) {
+            if (g_opt.fusion && !masked && n->ne[3] == 1 && contig(n) && !(n->flags & GGML_TENSOR_FLAG_OUTPUT)) {
                 const int64_t d = n->ne[0], HN = n->ne[1], Lq = n->ne[2], C = d * HN;
                 std::vector<FlashSlice> slices;
                 if (flash_out_token_slices(gi, i, C, Lq, 1, slices)) {
@@ -3417,7 +3421,7 @@ bool plan_single(Builder& B, int i, hipStream_t s) {
                     return true;
                 }
             }
-            B.emit([=](hipStream_t st) { launch_flash_attn(st, fo, qfix(q), kfix(k), vfix(v), sc); });
+            B.emit([=](hipStream_t st) { launch_flash_attn(st, fo, qfix(q), kfix(k), vfix(v), sc, masked ? &mk : nullptr); });
             STAT(fused_attention)++;
             return true;
         }
@@ -4750,7 +4754,11 @@ bool planner_supports_op(const ggml_tensor* n) {
             return f32c(n) && f32c(n->src[0]);
         case GGML_OP_FLASH_ATTN_EXT: {
             const ggml_tensor *q = n->src[0], *k = n->src[1], *v = n->src[2];
-            if (!q || !k || !v || n->src[3] != nullptr) return false;  // no mask on the hot path
+            if (!q || !k || !v) return false;
+            if (const ggml_tensor* m = n->src[3]) {  // masked (k_flash_mask): an f16 contiguous mask, d = 64 / 128, f32 Q, f16 K / V in the fast form, no ALiBi, no softcap
+                if (ggml_abi_op_param_f32(n, 1) != 0.0f || ggml_abi_op_param_f32(n, 2) != 0.0f || n->type != GGML_TYPE_F32) return false;
+                return m->type == GGML_TYPE_F16 && ggml_abi_is_contiguous(m) && flash_attn_mask_operands_ok(view_of(q), view_of(k), view_of(v), view_of(m));
+            }
             if (!f32c(q) || !(k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_F32) || v->type != k->type) return false;
             if (ggml_abi_op_param_f32(n, 1) != 0.0f || ggml_abi_op_param_f32(n, 2) != 0.0f) return false;
             if (q->nb[0] != 4 || k->nb[0] != ggml_abi_type_size(k->type) || v->nb[0] != ggml_abi_type_size(v->type)) return false;
@@ -4774,6 +4782,7 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
     o->flash_generic_launches = flash_attn_variant_launches(FLASH_VAR_GENERIC);
     o->flash_short_ip_launches = flash_attn_variant_launches(FLASH_VAR_SHORT_IP);
     o->flash_wide_launches     = flash_attn_variant_launches(FLASH_VAR_WIDE);
+    o->flash_mask_launches     = flash_attn_variant_launches(FLASH_VAR_MASK);
     // ... and where the elementwise launchers choose theirs: the ew_* fields lie in the order of EwRoute
     static_assert(offsetof(ggml_backend_mi355x_stats, ew_tile_merge_v1) - offsetof(ggml_backend_mi355x_stats, ew_bin_same) == (EW_ROUTE_COUNT - 1) * sizeof(int64_t),
                   "ggml_backend_mi355x_stats: one ew_* field per EwRoute, in its order");

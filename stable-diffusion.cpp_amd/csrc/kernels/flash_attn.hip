@@ -1,5 +1,5 @@
-// flash_attn.hip — fused scaled-dot-product attention forward for gfx950 (no mask, no GQA broadcast needed on
-// the UNet / VAE path): softmax(scale * Q K^T) V with online softmax, never materialising the [Lk, Lq] scores.
+// flash_attn.hip — fused scaled-dot-product attention forward for gfx950 (no GQA broadcast needed on the UNet / VAE path; the kernels here take no mask —
+// a FLASH_ATTN_EXT node that carries one is dispatched to flash_mask.hip): softmax(scale * Q K^T) V with online softmax, never materialising the [Lk, Lq] scores.
 // Head dims 8 .. 160 here; the FLASH_ATTN_EXT node at 192 .. 512 (the VAE mid-block) is dispatched to flash_wide.hip.
 // Serves both encodings the reference emits (ggml_ext_attention_ext, src/core/ggml_extend.hpp:1349-1485):
 //   * the FLASH_ATTN_EXT node (flash flag on; K/V arrive as f16), and
@@ -1199,8 +1199,13 @@ std::atomic<int64_t> g_variant_launches[FLASH_VAR_COUNT];
 }
 int64_t flash_attn_variant_launches(int variant) { return variant >= 0 && variant < FLASH_VAR_COUNT ? g_variant_launches[variant].load() : 0; }
 
-void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale) {
+void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale, const View4* mask) {
     KScope ks_(s, KF_FLASH, 4.0 * (double)q.ne[1] * (double)k.ne[1] * (double)q.ne[2] * (double)q.ne[0], 0.0);  // 4 * Lq * Lk * (H*N) * d
+    if (mask) {  // the node's src[3] (flash_mask.hip): d = 64 / 128, f16 K / V; launch_flash_mask aborts on anything the planner should not have claimed
+        g_variant_launches[FLASH_VAR_MASK]++;
+        launch_flash_mask(s, out, q, k, v, *mask, scale);
+        return;
+    }
     if (flash_attn_wide_supported(q.ne[0], v.ne[0])) {  // 160 < d <= 512 (flash_wide.hip): a plan of its own, the same operand and output forms
         g_variant_launches[FLASH_VAR_WIDE]++;
         launch_flash_wide(s, out, q, k, v, scale);

@@ -421,9 +421,10 @@ void gemm16_set_t256p_min_nt_sk(int v);     // option "t256p_min_nt_sk" (64): le
 void gemm16_set_t256p_min_tiles_sk(int v);  // option "t256p_min_tiles_sk" (192): least tiles, same condition
 bool gemm16_split_col_supported(int64_t rows, int64_t M, int64_t K);  // a Linear of this shape may carry Epilogue::split_col (it takes the pipelined 256 x 256 tile, no K slices)
 void gemm16_set_streamk(int v);    // option "streamk" (0; 1 = launches of two rounds or more, 2 = every candidate): Linears whose tile count leaves the last round of a one-workgroup-per-CU tile mostly empty run as one round of persistent workgroups over equal (tile, K-tile) ranges
-void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale);
+// mask (the node's src[3]; nullptr: none): dispatched to launch_flash_mask, which takes f32 output only
+void launch_flash_attn(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale, const View4* mask = nullptr);
 // which instantiation launch_flash_attn chose, counted per call (statistics flash_*_launches; the other FAST tile kernels are not counted)
-enum FlashVariant { FLASH_VAR_SHORT = 0, FLASH_VAR_QB2, FLASH_VAR_MSLOT, FLASH_VAR_GENERIC, FLASH_VAR_SHORT_IP, FLASH_VAR_WIDE, FLASH_VAR_COUNT };
+enum FlashVariant { FLASH_VAR_SHORT = 0, FLASH_VAR_QB2, FLASH_VAR_MSLOT, FLASH_VAR_GENERIC, FLASH_VAR_SHORT_IP, FLASH_VAR_WIDE, FLASH_VAR_MASK, FLASH_VAR_COUNT };
 // flash_wide.hip — head dims beyond flash_attn_supported: 160 < D = DV <= 512, D % 64 == 0 (the KL-VAE mid-block: one head of d = 512).  Only the FLASH_ATTN_EXT node
 // asks this (supports_op and its planner case); the manual chain beyond d = 160 stays the GEMM composition (plan_manual_attention branches on flash_attn_supported).
 // Operands: Q f32 rows, d-contiguous, any row / head stride; K and V f16, d-contiguous, rows and heads 16-byte aligned, Lk rows within 2 GiB
@@ -431,6 +432,12 @@ enum FlashVariant { FLASH_VAR_SHORT = 0, FLASH_VAR_QB2, FLASH_VAR_MSLOT, FLASH_V
 bool flash_attn_wide_supported(int64_t D, int64_t DV);
 bool flash_attn_wide_operands_ok(const View4& q, const View4& k, const View4& v);  // types, strides and sizes (not the base addresses: unknown before allocation)
 void launch_flash_wide(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, float scale);
+// flash_mask.hip — softmax(scale Q K^T + M) V for the FLASH_ATTN_EXT node with a mask, D = DV in {64, 128}.  Q f32 d-contiguous; K and V f16, d-contiguous, rows and heads
+// 16-byte aligned, Lk rows within 2 GiB (the FAST form of launch_flash_attn); M f16 [Lk, >= Lq, Hm, 1] contiguous within 2 GiB per plane, Hm divides the head count and
+// head hn reads plane hn % Hm (rows only 2-byte aligned); -inf entries exclude a key, a row with no live key yields zeros.  f32 output forms of FlashOut only (no dst16).
+// flash_attn_mask_operands_ok tests types, shapes and strides (not the base addresses); launch_flash_mask aborts on anything else.
+bool flash_attn_mask_operands_ok(const View4& q, const View4& k, const View4& v, const View4& m);
+void launch_flash_mask(hipStream_t s, const FlashOut& out, const View4& q, const View4& k, const View4& v, const View4& m, float scale);
 // IP-Adapter cross-attention in one launch (k_flash_short_ip): softmax(scale q k^T) v + ip_scale * softmax(scale q k_ip^T) v_ip into one output.  Text K / V as
 // k_flash_short takes them (64 < Lk <= 96), image K / V [D, Lk_ip, HN] with 1 <= Lk_ip <= 32, all f16, d-contiguous, 16-byte aligned rows; d <= 64, d % 8 == 0; Q f32
 // or an f16 image; exactly one of out.dst / out.dst16.  Anything else aborts: the planner asks flash_attn_ip_shape_ok first and runs other shapes as plain nodes.
