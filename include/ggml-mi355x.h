@@ -95,7 +95,7 @@ struct ggml_backend_mi355x_stats {
     int64_t fused_conv_scale;    /* Conv2d scales (SCALE s -> conv -> SCALE 1/s, the reference's SDXL VAE setting) folded into the operand image and the epilogue */
     int64_t view_graphs;         /* plans built for SUB-GRAPH VIEWS (sd_ggml_graph_view, src/core/ggml_extend_backend.cpp:449-463: leafs NULL / size 0) */
     int64_t plans_evicted;       /* cached plans (with their captured hipGraph) dropped by the LRU bound of the plan cache (option plan_cache_cap, default 512) */
-    int64_t hoisted_mod_linears; /* DiT modulation Linears (FLUX Modulation / SD3 adaLN: one or two rows, raw q8_0 / q4_0 weights, same input vector) computed by ONE grouped weight-streaming launch ahead of their graph position */
+    int64_t hoisted_mod_linears; /* DiT modulation Linears (FLUX Modulation / SD3 adaLN: one or two rows, raw q8_0 / q4_0 or q2_K .. q6_K weights, same input vector) computed by ONE grouped weight-streaming launch ahead of their graph position */
     int64_t view_external_nodes; /* nodes of those slices treated as read outside the slice (parent use_counts > readers inside, the slice's last node and its sources) */
     int64_t qinloop_linears;     /* q8_0 / q4_0 Linears above k_qgemm16's row range planned on the pipelined 256 x 256 tile with the raw GGUF blocks dequantised INSIDE the main loop (k_gemm16<..., QT>): no f16 weight image, resident or rebuilt */
     int64_t flash_out_alias;     /* FLASH_ATTN_EXT -> VIEW -> CONT chains NOT written by the flash kernel itself because the graph allocator gave the CONT the block of a Q / K / V operand (the node runs plain, the CONT as a copy) */
@@ -190,7 +190,8 @@ struct ggml_backend_mi355x_stats {
     int64_t lin_kq_gemm_rb4;         /* ... k_kq_gemm<KT, 4> */
     int64_t lin_kq_gemm_reduce;      /* the slab reduce behind a split launch_kq_gemm */
     int64_t lin_kq_image;            /* launch_kq_image: the f16 weight image of a K-quant weight (cached once per weight, or just in time under option jit_qimages) */
-    int64_t kquant_linears;          /* Linears with a q2_K .. q6_K weight (per plan, whatever route they take) */
+    int64_t lin_kq_gemv;             /* launch_kq_gemv / launch_kq_gemv_group: k_kq_gemv<KT, R>, the weight-streaming kernel under the hoisted modulation / embedding groups (1 .. 4 rows, option qgemv) */
+    int64_t kquant_linears;          /* Linears with a q2_K .. q6_K weight (per plan, whatever route they take; the members of a hoisted group count here, not in qgemv_linears) */
     /* 32-weight block Linear weights (q4_1 / q5_0 / q5_1 / iq4_nl / mxfp4 raw in HBM, kernels/bquant.hip); lin_bq_*: per launch call, in the order of BQRoute */
     int64_t lin_bq_gemm_rb1;         /* launch_bq_gemm: k_bq_gemm<BT, 1> (32-row tiles; 1 .. 4 rows read their f32 rows themselves) */
     int64_t lin_bq_gemm_rb2;         /* ... k_bq_gemm<BT, 2> */

@@ -428,7 +428,7 @@ _BACKEND_STAT_FIELDS = ("graphs_computed plans_built nodes_seen kernels_planned 
                         "lin_fgemv_f16 lin_fgemv_f32 lin_wswz_q "
                         "fused_ip_attn flash_short_ip_launches "
                         "fused_patch_embed patch_embed_launches "
-                        "lin_kq_gemm_rb1 lin_kq_gemm_rb2 lin_kq_gemm_rb4 lin_kq_gemm_reduce lin_kq_image kquant_linears "
+                        "lin_kq_gemm_rb1 lin_kq_gemm_rb2 lin_kq_gemm_rb4 lin_kq_gemm_reduce lin_kq_image lin_kq_gemv kquant_linears "
                         "lin_bq_gemm_rb1 lin_bq_gemm_rb2 lin_bq_gemm_reduce lin_bq_image bquant_linears "
                         "flash_wide_launches flash_mask_launches").split()
 

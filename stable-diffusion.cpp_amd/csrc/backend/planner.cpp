@@ -1861,7 +1861,7 @@ void plan_hoisted_emb(Builder& B, hipStream_t s) {
         const int64_t K = w->ne[0], M = w->ne[1], rows = x->ne[1];
         if (x->ne[2] != 1 || x->ne[3] != 1 || !aligned16(w->data) || w->nb[1] != ggml_abi_row_size(w->type, K)) continue;
         const bool fg = g_opt.fgemv && fgemv_supported((int)w->type, rows, K);
-        const bool qg = g_opt.qgemv && qgemv_supported((int)w->type, rows, K);
+        const bool qg = g_opt.qgemv && (qgemv_supported((int)w->type, rows, K) || kq_gemv_supported((int)w->type, rows, K));  // (packed K-quant rows concatenate like q8_0's)
         if (!fg && !qg) continue;
         // -> ADD bias (in place) -> RESHAPE [1,1,M,N] -> ADD(conv output, .)
         const int ja = gi.sole(j);
@@ -1931,7 +1931,9 @@ void plan_hoisted_emb(Builder& B, hipStream_t s) {
             Epilogue ep;
             ep.bias    = (const float*)(catp + wbytes);
             float* out = (float*)(P->arena + ooff);
-            if (use_q)
+            if (kq_type(wt))
+                launch_kq_gemv(st, out, Mtot, ex, xs, rows, catp, wt, K, Mtot, ep, 1.0f, true);
+            else if (use_q)
                 launch_qgemv(st, out, Mtot, ex, xs, rows, catp, wt, K, Mtot, P->arena + wsoff, ep, 1.0f, true);
             else
                 launch_fgemv(st, out, Mtot, ex, xs, rows, catp, wt, K, Mtot, ep, true);
@@ -1939,6 +1941,7 @@ void plan_hoisted_emb(Builder& B, hipStream_t s) {
         STAT(hoisted_emb_linears) += (int64_t)mem.size();
         STAT(fused_linear) += (int64_t)mem.size();
         STAT(fused_presilu) += (int64_t)mem.size();
+        if (kq_type(wt)) STAT(kquant_linears) += (int64_t)mem.size();
     }
 }
 
@@ -1975,7 +1978,7 @@ void plan_hoisted_mod(Builder& B, hipStream_t) {
         if (!e || !is_f32(e) || !contig(e) || e->ne[2] != 1 || e->ne[3] != 1 || !aligned16(e->data)) continue;
         const int64_t K = w->ne[0], M = w->ne[1], rows = x->ne[1];
         if (x->ne[2] != 1 || x->ne[3] != 1 || rows > 2 || M % 4 != 0 || !aligned16(w->data) || w->nb[1] != ggml_abi_row_size(w->type, K)) continue;
-        if (!qgemv_supported((int)w->type, rows, K)) continue;
+        if (!qgemv_supported((int)w->type, rows, K) && !kq_gemv_supported((int)w->type, rows, K)) continue;  // (k_kq_gemv: 4 rows per wave, the M % 4 above)
         const int ja = gi.sole(j);
         if (ja < 0 || gi.done[ja] || xop(gi.node(ja)) != GGML_OP_ADD || gi.node(ja)->src[0] != n || !bias_like_row(gi.node(ja)->src[1], M) || gi.node(ja)->data != n->data ||
             !is_static_weight(gi.node(ja)->src[1]) || !contig(gi.node(ja)))
@@ -2035,11 +2038,14 @@ void plan_hoisted_mod(Builder& B, hipStream_t) {
         const float* ex  = (const float*)k.e->data;
         const int64_t xs = (int64_t)k.e->nb[1] / 4, rows = k.rows, K = k.K;
         const int wt     = k.wtype, nm = (int)mem.size();
-        B.deferred[first].insert(B.deferred[first].begin(), [=](hipStream_t st) { launch_qgemv_group(st, (float*)(P->arena + ooff), Mtot, ex, xs, rows, table, nm, wt, K, 1.0f, true); });
+        B.deferred[first].insert(B.deferred[first].begin(), [=](hipStream_t st) {
+            (kq_type(wt) ? launch_kq_gemv_group : launch_qgemv_group)(st, (float*)(P->arena + ooff), Mtot, ex, xs, rows, table, nm, wt, K, 1.0f, true);
+        });
         STAT(hoisted_mod_linears) += (int64_t)mem.size();
         STAT(fused_linear) += (int64_t)mem.size();
         STAT(fused_presilu) += (int64_t)mem.size();
-        STAT(qgemv_linears) += (int64_t)mem.size();
+        if (kq_type(wt)) STAT(kquant_linears) += (int64_t)mem.size();
+        else STAT(qgemv_linears) += (int64_t)mem.size();  // (its meaning stays "q8_0 / q4_0")
     }
 }
 
@@ -4799,7 +4805,7 @@ void planner_get_stats(ggml_backend_mi355x_stats* o) {
                   "ggml_backend_mi355x_stats: one lin_* field per LinearRoute, in its order");
     for (int r = 0; r < LIN_ROUTE_COUNT; ++r) (&o->lin_t128)[r] = linear_route_launches(r);
     // ... and the K-quant launchers (kernels/kquant.hip): the lin_kq_* fields lie in the order of KQRoute
-    static_assert(offsetof(ggml_backend_mi355x_stats, lin_kq_image) - offsetof(ggml_backend_mi355x_stats, lin_kq_gemm_rb1) == (KQ_ROUTE_COUNT - 1) * sizeof(int64_t),
+    static_assert(offsetof(ggml_backend_mi355x_stats, lin_kq_gemv) - offsetof(ggml_backend_mi355x_stats, lin_kq_gemm_rb1) == (KQ_ROUTE_COUNT - 1) * sizeof(int64_t),
                   "ggml_backend_mi355x_stats: one lin_kq_* field per KQRoute, in its order");
     for (int r = 0; r < KQ_ROUTE_COUNT; ++r) (&o->lin_kq_gemm_rb1)[r] = kq_route_launches(r);
     // ... and the 32-weight block launchers (kernels/bquant.hip): the lin_bq_* fields lie in the order of BQRoute

@@ -101,6 +101,31 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// Sum NV per-lane partial values over the 64 lanes of a wave with NV - 1 + (6 - log2 NV) cross-lane exchanges instead of 6 NV: every halving
+// step sends the half of the values the partner lane keeps (lanes with bit o set keep the upper half).  Afterwards value index
+// (lane >> (6 - log2 NV)) is complete in every lane of its group.  (k_fgemv's epilogue did 32 butterfly sums = 192 dependent ds_bpermute
+// round trips: a third of its 32 us, profiles/r02u_kernel_stats.csv.)
+template <int NV>
+__device__ __forceinline__ float wave_sum_transpose(float (&v)[NV], int lane) {
+    static_assert(NV >= 1 && NV <= 32 && (NV & (NV - 1)) == 0, "NV must be a power of two <= 32");
+    constexpr int LOG = NV == 1 ? 0 : NV == 2 ? 1 : NV == 4 ? 2 : NV == 8 ? 3 : NV == 16 ? 4 : 5;
+#pragma unroll
+    for (int st = 0; st < LOG; ++st) {
+        const int n = NV >> st, o = 32 >> st;
+        const bool up = (lane & o) != 0;
+#pragma unroll
+        for (int i = 0; i < n / 2; ++i) {
+            const float send = up ? v[i] : v[i + n / 2];
+            const float keep = up ? v[i + n / 2] : v[i];
+            v[i]             = keep + __shfl_xor(send, o, 64);
+        }
+    }
+    float r = v[0];
+#pragma unroll
+    for (int o = 32 >> LOG; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+    return r;
+}
+
 // block reduction of two values with NW waves; scratch must hold 2*NW floats
 template <int NW>
 __device__ __forceinline__ void block_sum2(float& a, float& b, float* scratch) {

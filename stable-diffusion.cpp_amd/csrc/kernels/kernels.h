@@ -337,6 +337,7 @@ void launch_nchw_to_nhwc_f16(hipStream_t s, void* dst, const float* x, int64_t h
 // ---- qgemm.hip: q8_0 / q4_0 Linear with <= 4 activation rows: raw quantised blocks streamed once, in-register dequant ----------------
 bool qgemv_supported(int wtype, int64_t rows, int64_t K);
 void qgemv_set_max_rows(int v);
+int qgemv_max_rows();
 size_t qgemv_workspace_bytes(int64_t rows, int64_t K);
 // grouped weight-streaming launch (qgemm.hip): members_dev = device table of n_members entries written with qgemv_fill_member / qgemv_member_bytes
 void launch_qgemv_group(hipStream_t s, float* dst, int64_t Mtot, const float* x, int64_t xs, int64_t rows, const void* members_dev, int n_members, int wtype, int64_t K,
@@ -345,6 +346,27 @@ size_t qgemv_member_bytes();
 void qgemv_fill_member(void* host_entry, const void* W, const float* bias, int start);
 void launch_qgemv(hipStream_t s, float* dst, int64_t ldd, const float* x, int64_t xs, int64_t rows, const void* wraw, int wtype, int64_t K, int64_t M, void* ws,
                   const Epilogue& ep, float pre_scale, bool pre_silu = false);
+// grouped launch (launch_qgemv_group): the M output columns are the concatenation of several Linears that read the SAME activation rows — output column
+// `start` .. of the concatenation is row 0 .. of member weight W, with its own bias.  No concatenated copy of the weights exists: the wave finds its member.
+struct QGMember {
+    const char* W;
+    const float* bias;
+    int start, pad_;
+};
+struct QGArgs {
+    const QGMember* members = nullptr;  // device table, sorted by start; nullptr: one weight (W / bias below)
+    int n_members           = 0;
+    const char* W;       // raw quantised rows
+    int64_t row_bytes;
+    const float* x;      // activation rows, f32 (rounded to f16 in the kernel)
+    int64_t xs;          // row stride in floats
+    float* dst;
+    int64_t ldd;
+    const float* bias;
+    const float* residual;  // same layout as dst
+    float scale, pre_scale;
+    int K, M, rows, pre_silu;
+};
 
 // k_fgemv: f16 / f32 weights under <= 16 activation rows (time-embedding MLP, ResBlock embedding projections): one launch, optional SiLU on the
 // activation rows (the UNARY node in front of the Linear is not executed), f32 x f32 for f32 weights
@@ -378,11 +400,20 @@ bool kq_gemm_supported(int wtype, int64_t rows, int64_t K, int64_t M);
 int kq_gemm_split_k(int64_t rows, int64_t K, int64_t M);
 void launch_kq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const void* a16, int64_t lda, int64_t rows, const void* wraw, int wtype, int64_t K, int64_t M,
                     const Epilogue& ep, float* splitk_ws = nullptr, int splitk_S = 1, const float* x32 = nullptr, int64_t xs = 0, float pre_scale = 1.0f, bool pre_silu = false);
+// k_kq_gemv: the weight-streaming kernel for 1 .. 4 f32 activation rows (no matrix instruction), single and grouped as launch_qgemv / launch_qgemv_group (same
+// member table).  The planner takes it for the hoisted groups (plan_hoisted_mod / plan_hoisted_emb); a single Linear of 1 .. 4 rows stays on k_kq_gemm.
+// Contract of the grouped form: EVERY member has a multiple of 4 rows (a wave takes its four rows from one member's base pointer; the launcher can only check their
+// sum, the table is device memory) and q4_K / q5_K members are 16-byte aligned; the other types need 4- (q2_K) / 2-byte alignment.  launch_kq_gemv takes any M.
+bool kq_gemv_supported(int wtype, int64_t rows, int64_t K);
+void launch_kq_gemv(hipStream_t s, float* dst, int64_t ldd, const float* x, int64_t xs, int64_t rows, const void* wraw, int wtype, int64_t K, int64_t M, const Epilogue& ep,
+                    float pre_scale, bool pre_silu);
+void launch_kq_gemv_group(hipStream_t s, float* dst, int64_t Mtot, const float* x, int64_t xs, int64_t rows, const void* members_dev, int n_members, int wtype, int64_t K,
+                          float pre_scale, bool pre_silu);
 // k_kq_image: raw super-blocks -> the f16 MFMA weight image (wswz_bytes(R, K)); geglu_inner as launch_wswz_linear: 0 plain, > 0 128-column pairing, < 0 16-column interleave
 bool kq_image_supported(int wtype, int64_t K);
 void launch_kq_image(hipStream_t s, void* dst, const void* wraw, int wtype, int64_t K, int64_t R, int64_t geglu_inner = 0);
 // launches counted where the launchers choose (statistics lin_kq_*)
-enum KQRoute { KQ_GEMM_RB1 = 0, KQ_GEMM_RB2, KQ_GEMM_RB4, KQ_GEMM_REDUCE, KQ_IMAGE, KQ_ROUTE_COUNT };
+enum KQRoute { KQ_GEMM_RB1 = 0, KQ_GEMM_RB2, KQ_GEMM_RB4, KQ_GEMM_REDUCE, KQ_IMAGE, KQ_GEMV, KQ_ROUTE_COUNT };
 int64_t kq_route_launches(int route);
 
 // ---- bquant.hip: Linears over RAW q4_1 (wtype 3) / q5_0 (6) / q5_1 (7) / iq4_nl (20) / mxfp4 (39) blocks of 32 weights, any K % 32 == 0; every route multiplies by

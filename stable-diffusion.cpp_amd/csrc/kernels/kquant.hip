@@ -31,6 +31,8 @@
 //                       tile of 16.5 KiB per 32 rows: 47168 / 51264 B at 64-row tiles.
 //                       Tile: 32 RB rows x 128 columns (4 waves x 32), next segment's global loads in flight during the MFMAs; split-K over gridDim.z into f32 slabs.
 //                       A = the f16 operand image, or for 1 .. 4 rows the f32 rows themselves (SiLU and pre_scale applied while they are staged).
+//   k_kq_gemv<KT, R>    1 .. 4 activation rows of the HOISTED groups (modulation / embedding Linears that share one input: one launch for all of them): a weight
+//                       stream on the VALUs, lanes own 8-weight runs of the same walk, no matrix instruction (its own header below)
 //   k_kq_image<KT>      raw super-blocks -> the f16 fragment-order image [col/32][K/16][64 lanes][8 halfs] of k_gemm16 (plain row order and both GEGLU orders of
 //                       k_wswz_linear): a workgroup owns 32 image rows x 256 k, loads the 32 super-blocks coalesced into LDS, wave w decodes ITS group g = w
 //                       (q4_K / q5_K: two sub-block scales per lane) / (half, t) = (w / 2, w % 2) (q6_K, q2_K, q3_K: four scales) and writes four whole 1 KiB fragments.
@@ -481,6 +483,198 @@ __global__ __launch_bounds__(256) void k_kq_gemm(KQArgs g) {
 }
 
 // =====================================================================================================
+// k_kq_gemv
+// =====================================================================================================
+// 1 .. 4 activation rows against raw K-quant rows as a pure weight stream: no matrix instruction, no workgroup barrier inside the K loop.
+//   lanes     a super-block is cut into lane TASKS along its quant bytes, so that a lane reads its bytes once and one decode serves all R activation rows:
+//               q4_K / q5_K  16 tasks (g, r): bytes qs[32 g + 8 r ..] -> weights 64 g + 8 r + i (low nibbles) and 64 g + 32 + 8 r + i (high): 16 weights
+//               q6_K          8 tasks (hf, r): ql[64 hf + 8 r ..], ql[64 hf + 32 + 8 r ..], qh[32 hf + 8 r ..] -> weights 128 hf + 32 c + 8 r + i, c = 0 .. 3
+//               q2_K / q3_K   8 tasks (hf, r): qs[32 hf + 8 r ..] -> the same 32 weights from its four bit pairs (q3_K: + hmask[8 r ..])
+//             (the walk of k_kq_gemm above with (t, kg) = (r / 2, r % 2); each sub-block scale is unpacked by the task that uses it).  Lane l of a wave takes
+//             task l % TPS of super-block l / TPS of the step: a wave step covers SPS = 4 (q4_K / q5_K) or 8 super-blocks of ONE weight row.
+//   waves     a wave owns 4 consecutive weight rows (= output columns; members of a grouped launch are multiples of 4 rows, so the four belong to one member) and
+//             walks K in steps; a workgroup's four waves take 1 .. 4 such groups each (gpw: 64 columns per workgroup once that still gives 1024 workgroups), so
+//             the staged activation rows are amortised over 16 .. 64 columns.
+//   weights   the SPS super-blocks of a row step are contiguous in HBM: the wave copies the ALIGNED 16-byte granules that hold one of their bytes (phase = address
+//             & 15 for the 2- / 4-byte aligned rows of q2_K / q3_K / q6_K: the first and last granule share a valid byte with the row, so no granule lies outside
+//             the tensor) linearly into its private strip, one granule per lane and load: 36 / 44 granules (q4_K / q5_K), <= 43 / 56 (q2_K / q3_K), <= 106 (q6_K, two
+//             loads).  The loads of all four rows are issued before the first is consumed, and a row's registers are refilled with the NEXT step's granules as soon
+//             as they are stashed: four row steps are in flight per wave at any time.  The strip is private to the wave: wavefront-scope fences only.
+//             Strip stride between super-blocks = their stride in memory (a linear copy cannot pad it): 36 / 44 dwords (q4_K / q5_K: a task's 8 bytes are dwords
+//             4 + 2 u of its super-block, the 16 tasks 32 consecutive dwords; the two super-blocks of a 32-lane half start 36 / 44 dwords apart, so 28 / 20 of
+//             their 32 banks are distinct); 21 / 27.5 / 52.5 dwords (q2_K / q3_K / q6_K: a super-block's 8 tasks read two runs of 8 consecutive dwords 8 apart,
+//             the 8 super-blocks start on banks 21 j / 27.5 j / 52.5 j mod 64: odd or half-odd strides, no two on the same bank).
+//   x         staged once per workgroup into LDS as f16(silu?(x) * pre_scale) (k_qgemv's rounding point).  A task reads 16-byte chunks (8 k) 8 g + r and + 4
+//             (q4_K / q5_K) or 16 hf + 4 c + r: chunk ci of a row sits at slot ci ^ (bit 4 of ci << 2) ^ (bit 5 of ci << 3), so the 16 lanes of a quarter wave (one
+//             super-block of 16 tasks, or two of 8) read 16 different 16-byte slots modulo 256 bytes: all 64 banks once.  Read once per step, used by all four rows.
+//   sums      w16 from the shared decoders, (float)w16 * (float)x16 accumulated with f32 FMAs (v_fma_mix_f32: the conversions ride in the FMA) in two chains per
+//             (row, activation row); v_dot2_f32_f16 would halve these R operations per weight, but how it treats subnormal f16 operands was not verified
+//             against the MFMA's, and the decode (about 4 operations per weight), not the FMAs, is the larger share.  wave_sum_transpose over the 4 R sums.
+template <int KT>
+struct KQV {
+    static constexpr int TPS  = (KT == 4 || KT == 5) ? 16 : 8;  // lane tasks per super-block
+    static constexpr int SPS  = 64 / TPS;                       // super-blocks of a row per wave step
+    static constexpr int NCH  = 32 / TPS;                       // 8-weight runs per task
+    static constexpr int SEGB = SPS * KQ<KT>::BS;               // bytes of a full row step
+    static constexpr int NG   = (SEGB + (KQ<KT>::PH ? 15 : 0) + 15) / 16;
+    static constexpr int NLD  = (NG + 63) / 64;                 // loads per lane and row step
+};
+constexpr int KQV_CPW = 4;
+__device__ __forceinline__ int kqv_xslot(int ci) { return ci ^ (((ci >> 4) & 1) << 2) ^ (((ci >> 5) & 1) << 3); }
+
+struct KQVArgs {
+    QGArgs q;
+    int gpw;  // column groups of 4 per wave
+};
+
+template <int KT, int R>
+__global__ __launch_bounds__(256) void k_kq_gemv(KQVArgs a) {
+    using V = KQV<KT>;
+    const QGArgs& g = a.q;
+    constexpr int BS = KQ<KT>::BS, CPW = KQV_CPW, NLD = V::NLD, TPS = V::TPS, SPS = V::SPS, NCH = V::NCH;
+    __shared__ __attribute__((aligned(16))) char strip[4][NLD * 64 * 16 + 16];  // (+ 16: the third dword of an unaligned 8-byte read at the strip's end)
+    extern __shared__ __attribute__((aligned(16))) char xlds[];                 // [R][K] halfs, chunk ci at slot kqv_xslot(ci)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    char* my       = strip[wave];
+    const int nsb  = g.K / 256;
+    const int nseg = (nsb + SPS - 1) / SPS;
+    for (int c8 = threadIdx.x; c8 < g.K / 8; c8 += 256) {  // all R rows of a chunk column in flight together
+        float4 xa[R], xb[R];
+#pragma unroll
+        for (int t = 0; t < R; ++t) {
+            const float* xr = g.x + (int64_t)(t < g.rows ? t : 0) * g.xs + c8 * 8;
+            xa[t]           = *(const float4*)xr;
+            xb[t]           = *(const float4*)(xr + 4);
+        }
+#pragma unroll
+        for (int t = 0; t < R; ++t) {
+            const float v[8] = {xa[t].x, xa[t].y, xa[t].z, xa[t].w, xb[t].x, xb[t].y, xb[t].z, xb[t].w};
+            half8_t h;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float u = g.pre_silu ? act_apply<UN_SILU>(v[i]) : v[i];
+                h[i]          = (_Float16)(u * g.pre_scale);
+            }
+            *(half8_t*)(xlds + ((size_t)t * g.K + (size_t)kqv_xslot(c8) * 8) * 2) = h;
+        }
+    }
+    __syncthreads();
+    const int j = lane / TPS, u = lane % TPS;  // this lane's super-block of the step and its task
+    const int hi2 = u >> 2, r = u & 3;         // (g, r) / (hf, r)
+    for (int it = 0; it < a.gpw; ++it) {
+        const int col0 = ((int)blockIdx.x * a.gpw * 4 + it * 4 + wave) * CPW;
+        if (col0 >= g.M) break;
+        // this wave's weight rows: of the single weight, or of the member of a grouped launch that owns output column col0; Wb / bb are biased so that they
+        // are indexed by the GLOBAL column (k_qgemv)
+        const char* Wb  = g.W;
+        const float* bb = g.bias;
+        if (g.members) {
+            int m = 0;  // (a linear scan of the table, once per column group: the planner's groups have 3 .. a few dozen members; a binary search if they ever grow)
+            while (m + 1 < g.n_members && g.members[m + 1].start <= col0) ++m;
+            const QGMember mem = g.members[m];
+            Wb = mem.W - (int64_t)mem.start * g.row_bytes;
+            bb = mem.bias ? mem.bias - mem.start : nullptr;
+        }
+        float acc[CPW][R];
+#pragma unroll
+        for (int c = 0; c < CPW; ++c)
+#pragma unroll
+            for (int t = 0; t < R; ++t) acc[c][t] = 0.f;
+        u32x4_t gl[CPW][NLD];
+        auto rowp = [&](int c, int seg) { return Wb + (int64_t)min(col0 + c, g.M - 1) * g.row_bytes + (int64_t)seg * V::SEGB; };  // (the clamp only bites in a single weight's last group)
+        auto fetch = [&](int c, int seg) {
+            const char* p     = rowp(c, seg);
+            const uint32_t ph = KQ<KT>::PH ? (uint32_t)((uintptr_t)p & 15) : 0;
+            const int ng      = (int)(ph + (uint32_t)min(SPS, nsb - seg * SPS) * BS + 15) / 16;  // granules that hold a byte of this row step
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) {
+                const int gidx = i * 64 + lane;
+                gl[c][i]       = gidx < ng ? *(const u32x4_t*)(p - ph + (int64_t)gidx * 16) : (u32x4_t){0, 0, 0, 0};
+            }
+        };
+#pragma unroll
+        for (int c = 0; c < CPW; ++c) fetch(c, 0);
+        for (int seg = 0; seg < nseg; ++seg) {
+            const int sb    = seg * SPS + j;
+            const bool have = sb < nsb;
+            // the activation values of this lane's task: registers, shared by the four weight rows
+            half8_t xh[R][NCH];
+#pragma unroll
+            for (int t = 0; t < R; ++t)
+#pragma unroll
+                for (int cc = 0; cc < NCH; ++cc) {
+                    const int ci = 32 * (have ? sb : 0) + (TPS == 16 ? 8 * hi2 + 4 * cc + r : 16 * hi2 + 4 * cc + r);
+                    xh[t][cc]    = *(const half8_t*)(xlds + ((size_t)t * g.K + (size_t)kqv_xslot(ci) * 8) * 2);
+                }
+#pragma unroll
+            for (int c = 0; c < CPW; ++c) {
+                const uint32_t ph = KQ<KT>::PH ? (uint32_t)((uintptr_t)rowp(c, seg) & 15) : 0;
+                // LDS operations of one wave execute in order: the wavefront-scope fences only stop the compiler from moving the task reads across other
+                // lanes' stores (k_qgemv)
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int i = 0; i < NLD; ++i) *(u32x4_t*)(my + (i * 64 + lane) * 16) = gl[c][i];
+                if (seg + 1 < nseg) fetch(c, seg + 1);  // in flight for a whole step
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (have) {  // (a lane past the row's last super-block would decode stale strip bytes)
+                    const uint32_t off = ph + (uint32_t)j * BS;
+                    half8_t o[NCH];
+                    if constexpr (KT == 4 || KT == 5) {
+                        const KQHead h = kq_head45(my + off);
+                        float d1lo, m1lo, d1hi, m1hi;
+                        kq_scale45(h, 2 * hi2, d1lo, m1lo);
+                        kq_scale45(h, 2 * hi2 + 1, d1hi, m1hi);
+                        uint32_t ha = 0, hb = 0;
+                        if (KT == 5) kq_ld8<true>(my, off + KQ<KT>::QH + 8 * r, ha, hb);
+                        kq_dec45<KT>(my, off, hi2, r, ha, hb, d1lo, m1lo, d1hi, m1hi, o[0], o[1]);
+                    } else if constexpr (KT == 6) {
+                        float ds[4];
+#pragma unroll
+                        for (int cc = 0; cc < 4; ++cc) ds[cc] = kq_ds6(my, off, 8 * hi2 + 2 * cc + (r >> 1));
+                        kq_dec6(my, off, hi2, r, ds, o);
+                    } else {
+                        const KQHead23 h = kq_head23<KT>(my, off);
+                        uint32_t ha = 0, hb = 0;
+                        if (KT == 3) kq_ld8<false>(my, off + 8 * r, ha, hb);
+                        kq_dec23<KT>(my, off, h, hi2, r >> 1, r, ha, hb, o);
+                    }
+#pragma unroll
+                    for (int t = 0; t < R; ++t) {
+                        float sa = 0.f, sb2 = 0.f;
+#pragma unroll
+                        for (int cc = 0; cc < NCH; ++cc)
+#pragma unroll
+                            for (int i = 0; i < 8; i += 2) {
+                                sa  = fmaf((float)o[cc][i], (float)xh[t][cc][i], sa);
+                                sb2 = fmaf((float)o[cc][i + 1], (float)xh[t][cc][i + 1], sb2);
+                            }
+                        acc[c][t] += sa + sb2;
+                    }
+                }
+            }
+        }
+        // ---- cross-lane sums and store: value c * R + t ends up complete in the lanes of group (c * R + t)
+        constexpr int NV  = CPW * R;
+        constexpr int GRP = 64 / NV;
+        float v[NV];
+#pragma unroll
+        for (int c = 0; c < CPW; ++c)
+#pragma unroll
+            for (int t = 0; t < R; ++t) v[c * R + t] = acc[c][t];
+        const float tot = wave_sum_transpose<NV>(v, lane);
+        const int idx = lane / GRP, c = idx / R, t = idx - c * R, col = col0 + c;
+        if ((lane & (GRP - 1)) == 0 && t < g.rows && col < g.M) {
+            float out = tot * g.scale + (bb ? bb[col] : 0.f);
+            if (g.residual) out += g.residual[(int64_t)t * g.ldd + col];
+            g.dst[(int64_t)t * g.ldd + col] = out;
+        }
+    }
+}
+
+// =====================================================================================================
 // k_kq_image
 // =====================================================================================================
 // source row of image row (32-row block rb, n) under k_wswz_linear's three orders; >= R: a zero row
@@ -669,6 +863,72 @@ void launch_kq_gemm(hipStream_t s, float* dst, void* dst16, int64_t ldd16, const
         kq_route_taken(KQ_GEMM_REDUCE);
         splitk_reduce_rows(s, dst, splitk_ws, S, rows * M, ep.bias, M, ep.residual);
     }
+}
+
+// k_kq_gemv: 1 .. 4 rows (option qgemv_max_rows), R x K halfs of staged rows within 48 KB (R = 1, 2, 4), whole super-blocks.  Every type ships: by the HIP-event
+// sums its grouped launch beat the parent commit's separate k_kq_gemm launches on every probed shape (profiles/kq_gemv_probe.txt; by the host
+// clock q3_K does not gain on the 3072-wide groups and loses 5 % on one of them).
+bool kq_gemv_supported(int wtype, int64_t rows, int64_t K) {
+    if (!kq_type(wtype) || rows < 1 || rows > std::min(4, qgemv_max_rows()) || K % 256 != 0 || K < 256) return false;
+    return (rows <= 2 ? rows : 4) * K * 2 <= 48 * 1024;
+}
+static void kq_gemv_run(hipStream_t s, QGArgs& g, int wtype, int64_t rows, int64_t K, int64_t M) {
+    if (!kq_gemv_supported(wtype, rows, K) || M < 1 || M >= (1ll << 31) || (!g.members && kq_rows_aligned16(wtype) && ((uintptr_t)g.W & 15))) {
+        fprintf(stderr, "ggml-mi355x: invalid k_kq_gemv request\n");
+        abort();
+    }
+    g.row_bytes = K / 256 * kq_block_bytes(wtype);
+    g.K = (int)K; g.M = (int)M; g.rows = (int)rows;
+    KScope ks_(s, KF_QGEMM, 2.0 * rows * K * M, (double)M * g.row_bytes + (double)rows * K * 4.0 + (double)rows * M * 4.0);
+    KQVArgs a{g, (int)std::min<int64_t>(4, std::max<int64_t>(1, M / (16 * 1024)))};
+    const unsigned grid = (unsigned)((M + 16 * a.gpw - 1) / (16 * a.gpw));
+    const int r         = rows <= 2 ? (int)rows : 4;
+    const size_t lds    = (size_t)r * K * 2;
+    kq_route_taken(KQ_GEMV);
+#define KQV_LAUNCH(KT_)                                              \
+    do {                                                             \
+        if (r == 1) k_kq_gemv<KT_, 1><<<grid, 256, lds, s>>>(a);      \
+        else if (r == 2) k_kq_gemv<KT_, 2><<<grid, 256, lds, s>>>(a); \
+        else k_kq_gemv<KT_, 4><<<grid, 256, lds, s>>>(a);             \
+    } while (0)
+    if (wtype == 10) KQV_LAUNCH(2);
+    else if (wtype == 11) KQV_LAUNCH(3);
+    else if (wtype == 12) KQV_LAUNCH(4);
+    else if (wtype == 13) KQV_LAUNCH(5);
+    else KQV_LAUNCH(6);
+#undef KQV_LAUNCH
+}
+// x: f32 rows (stride xs floats, 16-byte aligned), staged as f16(silu?(x) * pre_scale); ep: scale, bias, residual (launch_qgemv's epilogue)
+void launch_kq_gemv(hipStream_t s, float* dst, int64_t ldd, const float* x, int64_t xs, int64_t rows, const void* wraw, int wtype, int64_t K, int64_t M, const Epilogue& ep,
+                    float pre_scale, bool pre_silu) {
+    if (ep.gate || ep.gelu) {
+        fprintf(stderr, "ggml-mi355x: k_kq_gemv has no gate / GELU epilogue\n");
+        abort();
+    }
+    QGArgs g;
+    g.W = (const char*)wraw;
+    g.x = x; g.xs = xs;
+    g.dst = dst; g.ldd = ldd;
+    g.bias = ep.bias; g.residual = ep.residual; g.scale = ep.scale; g.pre_scale = pre_scale; g.pre_silu = pre_silu ? 1 : 0;
+    kq_gemv_run(s, g, wtype, rows, K, M);
+}
+// the grouped form of launch_qgemv_group (same member table: qgemv_fill_member; every member a multiple of 4 rows, q4_K / q5_K members 16-byte aligned)
+void launch_kq_gemv_group(hipStream_t s, float* dst, int64_t Mtot, const float* x, int64_t xs, int64_t rows, const void* members_dev, int n_members, int wtype, int64_t K,
+                          float pre_scale, bool pre_silu) {
+    // the table lives in device memory: only the sum of the members' sizes can be checked here; each member being a multiple of 4 rows (a wave's four rows come
+    // from ONE base pointer) and 16-byte aligned for q4_K / q5_K is the caller's contract (kernels.h; plan_hoisted_mod enforces both)
+    if (!members_dev || n_members < 1 || Mtot % KQV_CPW != 0) {
+        fprintf(stderr, "ggml-mi355x: invalid k_kq_gemv group (%d members, %lld columns: every member must be a multiple of %d rows)\n", n_members, (long long)Mtot, KQV_CPW);
+        abort();
+    }
+    QGArgs g;
+    g.members   = (const QGMember*)members_dev;
+    g.n_members = n_members;
+    g.W         = nullptr;
+    g.x = x; g.xs = xs;
+    g.dst = dst; g.ldd = Mtot;
+    g.bias = nullptr; g.residual = nullptr; g.scale = 1.f; g.pre_scale = pre_scale; g.pre_silu = pre_silu ? 1 : 0;
+    kq_gemv_run(s, g, wtype, rows, K, Mtot);
 }
 
 // dst: image of wswz_bytes(R, K) bytes (rows padded to 128); geglu_inner as launch_wswz_linear takes it

@@ -27,53 +27,7 @@
 
 namespace mi355x {
 
-// Sum NV per-lane partial values over the 64 lanes of a wave with NV - 1 + (6 - log2 NV) cross-lane exchanges instead of 6 NV: every halving
-// step sends the half of the values the partner lane keeps (lanes with bit o set keep the upper half).  Afterwards value index
-// (lane >> (6 - log2 NV)) is complete in every lane of its group.  (k_fgemv's epilogue did 32 butterfly sums = 192 dependent ds_bpermute
-// round trips: a third of its 32 us, profiles/r02u_kernel_stats.csv.)
-template <int NV>
-__device__ __forceinline__ float wave_sum_transpose(float (&v)[NV], int lane) {
-    static_assert(NV >= 1 && NV <= 32 && (NV & (NV - 1)) == 0, "NV must be a power of two <= 32");
-    constexpr int LOG = NV == 1 ? 0 : NV == 2 ? 1 : NV == 4 ? 2 : NV == 8 ? 3 : NV == 16 ? 4 : 5;
-#pragma unroll
-    for (int st = 0; st < LOG; ++st) {
-        const int n = NV >> st, o = 32 >> st;
-        const bool up = (lane & o) != 0;
-#pragma unroll
-        for (int i = 0; i < n / 2; ++i) {
-            const float send = up ? v[i] : v[i + n / 2];
-            const float keep = up ? v[i + n / 2] : v[i];
-            v[i]             = keep + __shfl_xor(send, o, 64);
-        }
-    }
-    float r = v[0];
-#pragma unroll
-    for (int o = 32 >> LOG; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
-    return r;
-}
-
-// grouped launch (launch_qgemv_group): the M output columns are the concatenation of several Linears that read the SAME activation rows — output column
-// `start` .. of the concatenation is row 0 .. of member weight W, with its own bias.  No concatenated copy of the weights exists: the wave finds its member.
-struct QGMember {
-    const char* W;
-    const float* bias;
-    int start, pad_;
-};
-struct QGArgs {
-    const QGMember* members = nullptr;  // device table, sorted by start; nullptr: one weight (W / bias below)
-    int n_members           = 0;
-    const char* W;       // raw quantised rows
-    int64_t row_bytes;
-    const float* x;      // activation rows, f32 (rounded to f16 in the kernel)
-    int64_t xs;          // row stride in floats
-    float* dst;
-    int64_t ldd;
-    const float* bias;
-    const float* residual;  // same layout as dst
-    float scale, pre_scale;
-    int K, M, rows, pre_silu;
-};
-
+// (QGMember / QGArgs: kernels.h, shared with k_kq_gemv of kquant.hip)
 // QT: 8 = q8_0 (34-byte blocks), 4 = q4_0 (18-byte blocks).  R = activation rows held in registers (rows <= R), CPW = weight rows per wave.
 template <int QT, int R, int CPW>
 __global__ __launch_bounds__(256) void k_qgemv(QGArgs g) {
@@ -399,6 +353,7 @@ __global__ __launch_bounds__(256) void k_qgemv_rows(QGArgs g) {
 // and loses from 8 rows on (36 vs 28 us, 16 rows 89 vs 33 us) — profiles/r02s_qgemm_paths_probe.txt
 static int g_qgemv_max_rows = 4;
 void qgemv_set_max_rows(int v) { g_qgemv_max_rows = v > 16 ? 16 : (v < 1 ? 1 : v); }
+int qgemv_max_rows() { return g_qgemv_max_rows; }
 
 size_t qgemv_workspace_bytes(int64_t, int64_t) { return 0; }  // (the first version quantised the activations into a workspace)
 
